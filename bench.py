@@ -14,6 +14,12 @@ cycled to fill the batch.
 
 Launch: python bench.py [--gpus N --steps K --warmup W]; for N>1 under torch.distributed.run
 (one rank per GPU; RANK/LOCAL_RANK/WORLD_SIZE/MASTER_* from the env). Rank 0 prints ONE JSON line.
+
+A plain run generates the inputs, warms up, times the K steps and prints the line (value,
+ms_per_step, the roofline from the last step's stage events). --full adds what takes work of its
+own: the CPU baseline, the bit-exact comparison of the outputs with the oracle, the per-image
+records gather and its checks, and the PCIe-inclusive sub-batch. --dump-outputs DIR writes the last
+timed step's outputs to DIR/<name>.npy (inputs are seeded, so two builds compare file for file).
 """
 from __future__ import annotations
 
@@ -208,6 +214,55 @@ def cpu_baseline_encode(images, w, h, q, sub, target_s, cores):
                                       f"oracle/ or_jpeg_encode, {wall:.1f} s wall"}, hashes
 
 
+DUMP_SAMPLE = 8 << 20  # elements written of an output too large to write whole (32 MiB as float32)
+
+
+def _sample(t, seed=0):
+    """A device tensor's elements, flat: all of them, or DUMP_SAMPLE at fixed (seeded) positions."""
+    import torch
+    t = t.reshape(-1)
+    if t.numel() > DUMP_SAMPLE:
+        idx = np.random.default_rng(seed).integers(0, t.numel(), DUMP_SAMPLE)
+        t = t[torch.from_numpy(idx).to(t.device)]
+    return t.cpu().numpy()
+
+
+def _row_sums(rows):
+    """Exact per-row sums of a list of 1-D device tensors, so that a change outside the sampled
+    positions shows too. uint8 rows: the sum of the bytes. float32 rows: the sums of the low and
+    of the high 16 bits of every element's bit pattern (two columns). All below 2^53."""
+    import torch
+    out = []
+    for r in rows:
+        if r.dtype == torch.uint8:
+            out.append([int(r.sum(dtype=torch.int64))])
+        else:
+            b = r.view(torch.int32)
+            out.append([int((b & 0xFFFF).sum(dtype=torch.int64)), int(((b >> 16) & 0xFFFF).sum(dtype=torch.int64))])
+    return np.array(out, np.int64)
+
+
+def _sample_files(d_out, sizes):
+    """Bytes of the n files in d_out (n x cap, file i in its first sizes[i] bytes) at the same
+    seeded fractions of every file's length (0 for an empty file)."""
+    import torch
+    n, cap = d_out.shape
+    u = np.random.default_rng(0).random(max(1, DUMP_SAMPLE // n))
+    pos = (u[None, :] * sizes[:, None]).astype(np.int64) + np.arange(n, dtype=np.int64)[:, None] * cap
+    got = d_out.reshape(-1)[torch.from_numpy(pos.reshape(-1)).to(d_out.device)].cpu().numpy().reshape(n, -1)
+    return np.where(sizes[:, None] > 0, got, 0)
+
+
+def dump_outputs(dirname, rank, arrays):
+    """--dump-outputs: DIR/<name>.npy per array (rank r > 0: <name>.rank<r>.npy); 8- and 16-bit values
+    and float32 as float32, wider integers as float64 (statuses, sizes and sums are exact there)."""
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        a = a.astype(np.float32 if a.dtype == np.float32 or a.dtype.itemsize <= 2 else np.float64)
+        np.save(os.path.join(dirname, name + ("" if rank == 0 else f".rank{rank}") + ".npy"), a)
+
+
 def main_encode(args, wl, world, rank, local):
     """C4: device-resident encode of a per-rank batch of RGB images (one icx_jpeg_encode_device_batch
     call per step, inputs resident in HBM, files written to HBM)."""
@@ -268,6 +323,10 @@ def main_encode(args, wl, world, rank, local):
     torch.cuda.synchronize(dev)
     elapsed = time.perf_counter() - t0
     stages = {k: v / args.steps for k, v in enc.stage_times().items()}  # ms per step
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, rank, {
+            "status": last.cpu().numpy(), "sizes": sizes, "file_bytes": _sample_files(d_out, sizes),
+            "file_sums": _row_sums([d_out[i, : sizes[i]] for i in range(n)])})
     if world > 1:  # the final gather of every rank's statuses, after the timed steps
         last = shard.gather_results(last, dist)
     el = torch.tensor([elapsed], dtype=torch.float64, device=dev)
@@ -415,6 +474,10 @@ def main_png(args, wl, world, rank, local):
     if world > 1:
         dist.all_reduce(el, op=dist.ReduceOp.MAX)
     elapsed = float(el.item())
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, rank, {
+            "status": d_st.cpu().numpy(), "sizes": sizes, "file_bytes": _sample_files(d_out, sizes),
+            "file_sums": _row_sums([d_out[i, : sizes[i]] for i in range(n)])})
     ok_all = bool((last.cpu().numpy() == 0).all())
     checked = mismatches = 0
     if rank == 0 and not args.no_cpu:
@@ -570,6 +633,10 @@ def main_hdr(args, wl, world, rank, local):
         dist.barrier()
     torch.cuda.synchronize(dev)
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, rank, {
+            "status": d_st.cpu().numpy(), "dims": d_dims.cpu().numpy(), "pixels": _sample(d_out),
+            "pixel_sums": _row_sums([d_out[i * stride: (i + 1) * stride] for i in range(n)])})
     last = shard.gather_results(d_st, dist) if world > 1 else d_st
     el = torch.tensor([elapsed], dtype=torch.float64, device=dev)
     if world > 1:
@@ -732,6 +799,10 @@ def main_exr(args, wl, world, rank, local):
     if world > 1:
         dist.all_reduce(el, op=dist.ReduceOp.MAX)
     elapsed = float(el.item())
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, rank, {
+            "status": codes, "dims": np.stack([ws_, hs_], 1), "pixels": _sample(d_out),
+            "pixel_sums": _row_sums([d_out[i * per_img: (i + 1) * per_img] for i in range(n)])})
     ok_all = bool((codes == 0).all())
     if world > 1:
         st = torch.from_numpy(codes.copy()).to(dev)
@@ -780,8 +851,15 @@ def main():
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="CPU baseline budget (rank 0)")
     ap.add_argument("--cpu-cores", type=int, default=min(16, os.cpu_count() or 1),
                     help="CPU-baseline workers (default: the 16-core share of a GPU box)")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-pcie", action="store_true", help="skip the PCIe-inclusive sub-batch (decode workloads)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline figure does not need: the CPU baseline, the "
+                         "comparison of the outputs with the oracle, the records gather, the PCIe-inclusive sub-batch")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the last step's outputs (statuses, dimensions or sizes, exact "
+                         "per-image sums, a fixed seeded sample of the pixels or file bytes) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu", action="store_true", help="--full without the CPU baseline and oracle comparison")
+    ap.add_argument("--no-pcie", action="store_true",
+                    help="--full without the PCIe-inclusive sub-batch (decode workloads)")
     ap.add_argument("--png-single", action="store_true", help="C5: one encode call per image (no batch entry)")
     ap.add_argument("--graph", action="store_true",
                     help="decode workloads: capture one step (the whole batch call) in a HIP graph and replay it "
@@ -791,6 +869,8 @@ def main():
                          "k %% M with its own stream and output buffers, so one step's back half overlaps the "
                          "next step's front half")
     args = ap.parse_args()
+    if not args.full:  # a plain run: the timed steps and their result line only
+        args.no_cpu = args.no_pcie = True
 
     # --gpus N: one rank per GPU. Without a launcher (WORLD_SIZE unset) the bench starts
     # torch.distributed.run itself -- as a child, before anything touches the GPU -- and exits
@@ -920,38 +1000,46 @@ def main():
     elapsed = time.perf_counter() - t0
     stages = batch.stage_times()  # HIP events on this stream, last step
     paths = batch.path_stats()
+    if args.dump_outputs:
+        k = 0 if args.graph else (seq[0] - 1) % M  # the set that the last timed step wrote
+        dump_outputs(args.dump_outputs, rank, {
+            "status": d_st[k].cpu().numpy(), "dims": d_dims[k].cpu().numpy(), "pixels": _sample(d_out[k]),
+            "pixel_sums": _row_sums([d_out[k][i * stride: (i + 1) * stride] for i in range(n)])})
     # (outputs of the last step on set 0: every set decodes the same images)
     d_out, d_st, d_dims, last = d_out[0], d_st[0], d_dims[0], d_st[0]
 
-    # Final gather: every rank's per-image records {status, w, h, ncomp,
-    # checksum64}, computed on its device (icx_jpeg_records) from the last step's outputs,
-    # gathered over RCCL with padding to the largest shard. Outside the timed region.
-    d_rec = torch.empty(n * 24, dtype=torch.uint8, device=dev)
-    icx.records_device(ctx, n, d_out.data_ptr(), stride, d_st.data_ptr(), d_dims.data_ptr(), W, H, d_rec.data_ptr(),
-                       stream.cuda_stream)
-    r32 = d_rec.view(torch.int32).reshape(n, 6).to(torch.int64)
-    rec = torch.cat([r32[:, :4], ((r32[:, 5] << 32) | (r32[:, 4] & 0xFFFFFFFF))[:, None]], dim=1)
-    allrec, counts = shard.gather_records(rec, dist) if world > 1 else (rec, [n])
-    allrec = allrec.cpu().numpy()
-    # the pool is cycled: every repeat of an image must carry the same checksum (per rank)
-    consistent = True
-    o = 0
-    for r, c in enumerate(counts):
-        cs = allrec[o: o + c, 4]
-        p = min(args.pool, c)
-        consistent &= bool(all((cs[k::p] == cs[k]).all() for k in range(p)))
-        o += c
-    records = {"gathered": int(allrec.shape[0]), "per_rank": counts, "status_ok": bool((allrec[:, 0] == 0).all()),
-               "repeats_consistent": consistent}
+    records = None
+    if args.full:
+        # Final gather: every rank's per-image records {status, w, h, ncomp,
+        # checksum64}, computed on its device (icx_jpeg_records) from the last step's outputs,
+        # gathered over RCCL with padding to the largest shard. Outside the timed region.
+        d_rec = torch.empty(n * 24, dtype=torch.uint8, device=dev)
+        icx.records_device(ctx, n, d_out.data_ptr(), stride, d_st.data_ptr(), d_dims.data_ptr(), W, H,
+                           d_rec.data_ptr(), stream.cuda_stream)
+        r32 = d_rec.view(torch.int32).reshape(n, 6).to(torch.int64)
+        rec = torch.cat([r32[:, :4], ((r32[:, 5] << 32) | (r32[:, 4] & 0xFFFFFFFF))[:, None]], dim=1)
+        allrec, counts = shard.gather_records(rec, dist) if world > 1 else (rec, [n])
+        allrec = allrec.cpu().numpy()
+        # the pool is cycled: every repeat of an image must carry the same checksum (per rank)
+        consistent = True
+        o = 0
+        for r, c in enumerate(counts):
+            cs = allrec[o: o + c, 4]
+            p = min(args.pool, c)
+            consistent &= bool(all((cs[k::p] == cs[k]).all() for k in range(p)))
+            o += c
+        records = {"gathered": int(allrec.shape[0]), "per_rank": counts,
+                   "status_ok": bool((allrec[:, 0] == 0).all()), "repeats_consistent": consistent}
 
     el = torch.tensor([elapsed], dtype=torch.float64, device=dev)
     if world > 1:
         dist.all_reduce(el, op=dist.ReduceOp.MAX)
     elapsed = float(el.item())
 
-    # correctness of the measured run: every image of the job OK (the gathered records carry every
-    # rank's statuses); this rank's pool images bit-exact vs the oracle
-    ok_all = bool((last.cpu().numpy() == 0).all()) and records["status_ok"]
+    # correctness of the measured run: this rank's statuses and, with --full, every image of the job
+    # OK (the gathered records carry every rank's statuses) and this rank's pool images bit-exact
+    # vs the oracle
+    ok_all = bool((last.cpu().numpy() == 0).all()) and (records is None or records["status_ok"])
     checked = 0
     mismatches = 0
     if rank == 0 and cpu_hashes:

@@ -2,8 +2,8 @@
 
 png_encoder.cpp includes libpng's png.h (absent here), so the reference is unbuildable; the
 restatement is pinned by (1) the reference's own data/test.png, whose lodepng encode SURVEY.md
-§8(c) records as palette, 8-bit, filter 0 for every row (container-only: /root/reference is
-read in place, never copied), and (2) rule checks on synthetic images for every branch of
+§8(c) records as palette, 8-bit, filter 0 for every row (the image is kept as the fixture
+tests/golden/png/test.png), and (2) rule checks on synthetic images for every branch of
 auto_choose_color (png_encoder.cpp:3552-3616).
 """
 import os
@@ -12,13 +12,13 @@ import zlib
 import numpy as np
 import pytest
 
+from conftest import GOLDEN
 from oracle import pyoracle as O
 import pngutil as P
 
-REF_PNG = "/root/reference/data/test.png"
+REF_PNG = os.path.join(GOLDEN, "png", "test.png")  # the reference's data/test.png, byte for byte
 
 
-@pytest.mark.skipif(not os.path.exists(REF_PNG), reason="reference data only in the build container")
 def test_oracle_png_reference_fixture():
     px = P.read_fixture_png(REF_PNG)  # opaque RGBA, 499 x 289
     h, w = px.shape[:2]

@@ -6,7 +6,7 @@ R="$GRAFT_REPO_ROOT"; [ -n "$R" ] || R=$(pwd)
 O="$R/gpurun_out/meas"; mkdir -p "$O"
 cd /tmp && export TMPDIR=/tmp
 ARGS="${BENCH_ARGS:-}"
-timeout -k 10 600 python3 "$R/bench.py" $ARGS > "$O/bench.json" 2> "$O/bench.err"
+timeout -k 10 600 python3 "$R/bench.py" --full $ARGS > "$O/bench.json" 2> "$O/bench.err"
 echo "bench: $(cut -c1-200 $O/bench.json)"
 # same command without the CPU-baseline leg (its fork pool does not survive the profiler's preload)
 timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/trace" -o run -- python3 "$R/bench.py" $ARGS --no-cpu --no-pcie > "$O/bench_rocprof.json" 2> "$O/rocprof.err"

@@ -7,7 +7,7 @@ R="$GRAFT_REPO_ROOT"; [ -n "$R" ] || R=$(pwd)
 O="$R/gpurun_out/side"; mkdir -p "$O"
 cd /tmp && export TMPDIR=/tmp
 for w in ${SIDE_WORKLOADS:-c2 c3dri c4 c5 hdr hdrflat}; do
-  timeout -k 10 300 python3 "$R/bench.py" --workload $w --steps 3 > "$O/bench_$w.json" 2> "$O/bench_$w.err"
+  timeout -k 10 300 python3 "$R/bench.py" --full --workload $w --steps 3 > "$O/bench_$w.json" 2> "$O/bench_$w.err"
   echo "$w: $(cut -c1-160 $O/bench_$w.json)"
 done
 for w in ${SIDE_PROF:-c4 c5}; do
