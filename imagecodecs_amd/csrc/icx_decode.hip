@@ -59,25 +59,17 @@ __global__ __launch_bounds__(64) void k_parse(int n, const uint8_t* __restrict__
 // One wave per image that neither parallel path takes (a stream whose restart markers NanoJPEG
 // reads where no lane starts, more than kSpecMaxBpm blocks per MCU -- beyond the JPEG limit of 10,
 // so non-conforming --, an exhausted workspace, a repair walk that never resynchronises). Lane 0
-// walks the entropy-coded segment exactly like njDecodeScan (jpeg_dec.h:643-718). The wave keeps
-// the image's four Huffman tables in LDS and the stream's next bytes in an LDS ring, refilled a KiB
-// at a time by all 64 lanes with 16-byte loads, so the serial walk runs at LDS latency instead of
-// a dependent global load per byte and per table lookup.
-// ICX_SEQ_LDS=0 (default): the tables and the stream are read from global memory (L1/L2) instead.
-// The LDS form walks ~10% faster, but a kernel holding ~14 KB of LDS per workgroup cannot be
-// dispatched while the other pipeline's entropy kernels fill every CU's LDS, and it sits in the
-// stream before the back half even when it has nothing to do (every group, every call): at C2 it
-// waited ~0.16 ms per group for LDS it then did not use.
-#ifndef ICX_SEQ_LDS
-#define ICX_SEQ_LDS 0
-#endif
-constexpr int kSeqRing = 4096;  // 4 quarters of 1 KiB; lane 0 always has >= 2 KiB loaded ahead
-struct RingBits {                // rb_fill's byte rules (icx_jpeg.h) over the ring
-    const uint8_t* ring;
-    int64_t pos, end;            // next byte, stream end (relative to the aligned ring origin)
+// walks the entropy-coded segment exactly like njDecodeScan (jpeg_dec.h:643-718), reading the
+// tables and the stream from global memory (L1/L2). (Tables and a stream ring in LDS walked ~10%
+// faster, but a kernel holding ~14 KB of LDS per workgroup cannot be dispatched while the other
+// pipeline's entropy kernels fill every CU's LDS, and it sits in the stream before the back half
+// even when it has nothing to do: at C2 it waited ~0.16 ms per group for LDS it then did not use.)
+struct SeqBits {                 // rb_fill's byte rules (icx_jpeg.h) over the stream
+    const uint8_t* s;            // 16-byte aligned origin at or before the scan data
+    int64_t pos, end;            // next byte, stream end (relative to the origin)
     uint32_t acc;
     int32_t nacc, err;
-    __device__ uint32_t byte() { return ring[(pos++) & (ICX_SEQ_LDS ? kSeqRing - 1 : ~(int64_t)0)]; }
+    __device__ uint32_t byte() { return s[pos++]; }
     __device__ void fill(int want) {
         while (nacc < want) {
             if (pos >= end) { acc = (acc << 8) | 0xFFu; nacc += 8; continue; }
@@ -114,43 +106,8 @@ __global__ __launch_bounds__(64) void k_entropy_seq(int n, const uint8_t* __rest
     const int mis = (int)(reinterpret_cast<uintptr_t>(S) & 15);
     const uint8_t* S0 = S - mis;
     const int64_t end = (int64_t)(d.size - d.scan_off) + mis;
-#if !ICX_SEQ_LDS
     const Huff* HT = d.huff;
-    RingBits b{S0, mis, end, 0u, 0, 0};  // (fill never reads at or past `end`)
-    auto refill = [&](int64_t) {};
-#else
-    __shared__ Huff HT[4];
-    __shared__ uint4 ring4[kSeqRing / 16];
-    {
-        const uint32_t* src = reinterpret_cast<const uint32_t*>(d.huff);
-        uint32_t* dst = reinterpret_cast<uint32_t*>(HT);
-        for (int k = lane; k < (int)(sizeof(HT) / 4); k += 64) dst[k] = src[k];
-    }
-    // the ring holds the stream from a 16-byte aligned origin: quarter q of the ring = stream KiB qi
-    // with qi % 4 == q; quarters qlo .. qlo+3 are loaded
-    auto fill_quarter = [&](int64_t qi) {  // all lanes (bytes past the end read as FF, never used)
-        const int64_t at = qi * 1024 + lane * 16;
-        uint4 v = make_uint4(~0u, ~0u, ~0u, ~0u);
-        if (at + 16 <= end) {
-            v = *reinterpret_cast<const uint4*>(S0 + at);
-        } else if (at < end) {
-            uint8_t tb[16];
-            for (int k = 0; k < 16; ++k) tb[k] = at + k < end ? S0[at + k] : 0xFF;
-            __builtin_memcpy(&v, tb, 16);
-        }
-        ring4[(qi & 3) * 64 + lane] = v;
-    };
-    int64_t qlo = 0;
-    for (int q = 0; q < 4; ++q) fill_quarter(q);
-    __syncthreads();
-    RingBits b{reinterpret_cast<const uint8_t*>(ring4), mis, end, 0u, 0, 0};
-    auto refill = [&](int64_t pos) {
-        while (pos >= (qlo + 2) * 1024) {
-            fill_quarter(qlo + 4);
-            ++qlo;
-        }
-    };
-#endif
+    SeqBits b{S0, mis, end, 0u, 0, 0};  // (fill never reads at or past `end`)
     int16_t* A = ac + d.acbase * 64;  // (in place: the pool region k_spec_plan gave the image)
     int32_t* D = dcv + d.acbase;
     int32_t pred[3] = {0, 0, 0};
@@ -160,11 +117,6 @@ __global__ __launch_bounds__(64) void k_entropy_seq(int n, const uint8_t* __rest
     int err = 0;
     for (int64_t m = 0; m < (nmcu > 0 ? nmcu : 1) && !err; ++m) {
         for (int r = 0; r < d.bpm && !err; ++r, ++blk) {
-            // wave-uniform: keep >= 2 KiB loaded past lane 0's position (a block reads < 600 bytes)
-            const int64_t pos = __builtin_amdgcn_readfirstlane((int)b.pos) |
-                                ((int64_t)__builtin_amdgcn_readfirstlane((int)(b.pos >> 32)) << 32);
-            refill(pos);
-            __builtin_amdgcn_wave_barrier();  // (one wave: its LDS accesses stay in order)
             if (lane == 0) {
                 int sbx, sby;
                 const int ci = mcu_block_comp(d, r, sbx, sby);
@@ -344,12 +296,9 @@ __global__ __launch_bounds__(256) void k_idct_any(const Desc* __restrict__ desc,
     }
 }
 
-
-// Lane-pair IDCT helpers (k_idct420c, k_fused420): a block is transformed by two lanes in
-// registers -- lane h takes natural rows 4h..4h+3 in the row pass and columns 4h..4h+3 in the
-// column pass, the 4x4 quadrants changing hands by DPP. Full row / column formulas (no zero-AC
-// shortcuts) with 24-bit multiplies: exact whenever every dequantized coefficient is below 2^14
-// in magnitude (then no row output reaches 2^21); otherwise the reference code (idct_row /
+// In-register IDCT helpers (block_idct: k_idct420s, k_fused420s). Full row / column formulas (no
+// zero-AC shortcuts) with 24-bit multiplies: exact whenever every dequantized coefficient is below
+// 2^14 in magnitude (then no row output reaches 2^21); otherwise the reference code (idct_row /
 // idct_col, shortcuts and 32-bit wrap included) runs.
 namespace {
 constexpr uint8_t kZigOfNatC[64] = {
@@ -405,41 +354,7 @@ __device__ __forceinline__ void idct_row_full(int32_t (&r)[8]) {
     r[6] = (x3 - x2) >> 8;
     r[7] = (x7 - x1) >> 8;
 }
-__device__ __forceinline__ void idct_col_full(const int32_t (&v)[8], int32_t (&o)[8]) {
-    int32_t x0 = (v[0] << 8) + 8192, x1 = v[4] << 8, x2 = v[6], x3 = v[2];
-    int32_t x4 = v[1], x5 = v[7], x6 = v[5], x7 = v[3], x8;
-    x8 = m24(kW7, x4 + x5) + 4;
-    x4 = (x8 + m24(kW1 - kW7, x4)) >> 3;
-    x5 = (x8 - m24(kW1 + kW7, x5)) >> 3;
-    x8 = m24(kW3, x6 + x7) + 4;
-    x6 = (x8 - m24(kW3 - kW5, x6)) >> 3;
-    x7 = (x8 - m24(kW3 + kW5, x7)) >> 3;
-    x8 = x0 + x1;
-    x0 -= x1;
-    x1 = m24(kW6, x3 + x2) + 4;
-    x2 = (x1 - m24(kW2 + kW6, x2)) >> 3;
-    x3 = (x1 + m24(kW2 - kW6, x3)) >> 3;
-    x1 = x4 + x6;
-    x4 -= x6;
-    x6 = x5 + x7;
-    x5 -= x7;
-    x7 = x8 + x3;
-    x8 -= x3;
-    x3 = x0 + x2;
-    x0 -= x2;
-    x2 = (wmul(181, x4 + x5) + 128) >> 8;  // (32-bit: as in idct_col)
-    x4 = (wmul(181, x4 - x5) + 128) >> 8;
-    auto cl = [](int32_t x) { return min(max((x >> 14) + 128, 0), 255); };
-    o[0] = cl(x7 + x1);
-    o[1] = cl(x3 + x2);
-    o[2] = cl(x0 + x4);
-    o[3] = cl(x8 + x6);
-    o[4] = cl(x8 - x6);
-    o[5] = cl(x0 - x4);
-    o[6] = cl(x3 - x2);
-    o[7] = cl(x7 - x1);
-}
-// idct_col_full before its clip: o[r] = the value whose clip8(o >> 14) is the pixel, the +128
+// The column pass before its clip: o[r] = the value whose clip8(o >> 14) is the pixel, the +128
 // level shift folded into x0's rounding constant (every output holds x0's constant exactly once:
 // (x >> 14) + 128 == (x + (128 << 14)) >> 14), so sat4<14> packs four of them with the clip.
 __device__ __forceinline__ void idct_col_raw(const int32_t (&v)[8], int32_t (&o)[8]) {
@@ -475,10 +390,7 @@ __device__ __forceinline__ void idct_col_raw(const int32_t (&v)[8], int32_t (&o)
     o[6] = x3 - x2;
     o[7] = x7 - x1;
 }
-__device__ __forceinline__ int32_t pair_swap(int32_t x) {  // the other lane of the pair (DPP quad_perm [1,0,3,2])
-    return __builtin_amdgcn_mov_dpp(x, 0xB1, 0xF, 0xF, false);
-}
-__device__ __forceinline__ bool fused420(const Desc& d);  // (k_fused420 below)
+__device__ __forceinline__ bool fused420(const Desc& d);  // (the 4:2:0 back half, below)
 
 // The main IDCT kernel, for MCUs of up to kIdctUnitBlocks blocks (every sampling but the
 // exotic 8x-subsampled ones). A wave's unit of work is kUM horizontally adjacent MCUs of one MCU
@@ -896,37 +808,9 @@ struct CPl {
     const uint8_t* p;
     int w, h, s;
 };
-// Timing experiment ICX_NT_BACK (bit 0: plane and coefficient loads, bit 1: IDCT plane stores)
-// marked non-temporal (streamed past L2, so the other pipeline's entropy lanes keep their U lines).
-#ifndef ICX_NT_BACK
-#define ICX_NT_BACK 0
-#endif
-template <class T>
-__device__ __forceinline__ T nt_ld(const T* p) {
-#if ICX_NT_BACK & 1
-    return __builtin_nontemporal_load(p);
-#else
-    return *p;
-#endif
-}
-template <class T>
-__device__ __forceinline__ void nt_st(T v, T* p) {
-#if ICX_NT_BACK & 2
-    __builtin_nontemporal_store(v, p);
-#else
-    *p = v;
-#endif
-}
-__device__ __forceinline__ int4 nt_ld(const int4* p) {
-#if ICX_NT_BACK & 1
-    typedef int v4i __attribute__((ext_vector_type(4)));
-    const v4i v = __builtin_nontemporal_load(reinterpret_cast<const v4i*>(p));
-    return int4{v.x, v.y, v.z, v.w};
-#else
-    return *p;
-#endif
-}
-__device__ __forceinline__ uint32_t ld4(const uint8_t* p) { return nt_ld(reinterpret_cast<const uint32_t*>(p)); }
+__device__ __forceinline__ uint32_t ld4(const uint8_t* p) { return *reinterpret_cast<const uint32_t*>(p); }
+// (a function, like ld4: with the chunk assigned in place k_fused420s schedules differently)
+__device__ __forceinline__ int4 ld16(const int4* p) { return *p; }
 __device__ __forceinline__ int bt(uint32_t v, int i) { return (v >> (8 * i)) & 255; }
 // Packs four 0..255 values with v_perm_b32. (A shift/or pack of clamped taps lets the compiler
 // form gfx950's v_ashr_pk_u8_i32, whose result's upper half was observed to leak into the
@@ -977,10 +861,6 @@ __device__ __forceinline__ int32_t dot2_i16(uint32_t a, uint32_t b, int32_t acc)
     asm("v_dot2_i32_i16 %0, %1, %2, %3" : "=v"(r) : "v"(a), "s"(b), "v"(acc));
     return r;
 }
-__device__ __forceinline__ uint32_t dtap(uint32_t biased, int32_t k) {
-    const int32_t v = dot4_i8(biased, k, 128 * 128 + 64) >> 7;
-    return (uint32_t)min(max(v, 0), 255);
-}
 // Four clipped bytes in one dword from four int32 values: byte i = clip8(v_i >> SH), by gfx950's
 // v_ashr_pk_u8_i32 (D[7:0] = sat_u8(S0 >> S2), D[15:8] = sat_u8(S1 >> S2)). It writes only the
 // low half of D and keeps the high half, and with op_sel:[0,0,0,1] writes the high half and keeps
@@ -994,7 +874,7 @@ __device__ __forceinline__ uint32_t sat4(int32_t v0, int32_t v1, int32_t v2, int
         : "=&v"(r) : "v"(v0), "v"(v1), "v"(v2), "v"(v3), "i"(SH));
     return r;
 }
-// dtap before its shift and clip: the biased dot (sat4<7> finishes it)
+// A 4-tap output before its shift and clip: the biased dot (sat4<7> finishes it)
 __device__ __forceinline__ int32_t dtap_raw(uint32_t biased, int32_t k) { return dot4_i8(biased, k, 128 * 128 + 64); }
 
 template <bool KH>
@@ -1318,12 +1198,11 @@ __device__ __forceinline__ void stream_image(const Desc& d, const uint8_t* pslot
 constexpr int kSHE = ICX_SHE;  // rows per edge item (even): short strips, so the few border lanes fill the chip
 template <int K>
 __global__ __launch_bounds__(256) void k_convert_edge(const Desc* __restrict__ desc, const uint8_t* __restrict__ planes,
-                                                      int64_t plane_cap, uint8_t* __restrict__ out, uint64_t out_stride,
-                                                      int fuse) {
+                                                      int64_t plane_cap, uint8_t* __restrict__ out, uint64_t out_stride) {
     static_assert(K & 1, "horizontally doubled layouts only");
     const int img = blockIdx.y;
     const Desc& d = desc[img];
-    if (d.status != kOk || stream_kind(d) != K || (K == 3 && (fuse == 1 || fuse == 3) && fused420(d))) return;
+    if (d.status != kOk || stream_kind(d) != K) return;
     const uint8_t* pslot = planes + (int64_t)img * plane_cap;
     uint8_t* o = out + (int64_t)img * out_stride;
     const StreamOut so{o, d.W, ((reinterpret_cast<uintptr_t>(o) & 3) == 0) && (d.W & 3) == 0};
@@ -1351,7 +1230,7 @@ __global__ __launch_bounds__(256, ICX_CONV_MINW) void k_convert_stream(const Des
                                                         int fuse) {
     const int img = blockIdx.y;
     const Desc& d = desc[img];
-    if (d.status != kOk || stream_kind(d) != K || (K == 3 && (fuse == 1 || fuse == 3 || fuse == 5) && fused420(d))) return;
+    if (d.status != kOk || stream_kind(d) != K || (K == 3 && fuse == 5 && fused420(d))) return;  // (mode 5: k_fused420s converts)
     const uint8_t* pslot = planes + (int64_t)img * plane_cap;
     uint8_t* o = out + (int64_t)img * out_stride;
     const StreamOut so{o, d.W, ((reinterpret_cast<uintptr_t>(o) & 3) == 0) && (d.W & 3) == 0};
@@ -1360,275 +1239,39 @@ __global__ __launch_bounds__(256, ICX_CONV_MINW) void k_convert_stream(const Des
 
 // ---------------------------------------------------- 4:2:0 chroma IDCT + fused luma IDCT/convert
 // The common 4:2:0 layout (Y 2x2, Cb and Cr 1x1 per MCU) skips k_idct and k_convert_stream<3>:
-// k_idct420c writes the two chroma planes, then k_fused420 transforms each MCU row's luma
+// k_idct420s writes the two chroma planes, then k_fused420s transforms each MCU row's luma
 // blocks into LDS and converts those 16 rows from there -- the 16.8 MB luma plane per 4096^2
-// image never goes through HBM. Both use the lane-pair IDCT; the conversion is rows_kv, the same
-// code k_convert_stream runs, with the luma rows read from LDS.
+// image never goes through HBM. The conversion is kv_rows, the same code k_convert_stream runs,
+// with the luma rows read from LDS.
 __device__ __forceinline__ bool fused420_shape(const Desc& d) {
     return d.nc == 3 && d.bpm == 6 && d.c[0].hs == 2 && d.c[0].vs == 2 && d.c[1].hs == 1 && d.c[1].vs == 1 &&
            d.c[2].hs == 1 && d.c[2].vs == 1 && stream_kind(d) == 3;
 }
 __device__ __forceinline__ bool fused420(const Desc& d) { return d.status == kOk && fused420_shape(d); }
 
-
-
-// Lane-pair IDCT of one block: c = the block as stored (zig-zag int16), qw = its component's
-// dequant table (zig-zag, 4 bytes per register), h = the lane's half; rowd[r] = pixels 4h..4h+3
-// of row r. D / n: the int32 DC of a block whose cell 0 holds kDcEscape. Wave-level (the fast
-// path is a wave vote): every lane of the wave calls it.
-__device__ __forceinline__ void pair_idct(const int4 (&c)[8], const uint32_t (&qw)[16], int h, const int32_t* dcv,
-                                          const BlkLoc& loc, uint32_t (&rowd)[8]) {
-    auto qt = [&](int z) { return (int32_t)((qw[z >> 2] >> (8 * (z & 3))) & 0xFFu); };
-    auto coef = [&](int z) {
-        const int4& w = c[z >> 3];
-        const int e = z & 7;
-        const uint32_t d32 = (uint32_t)(e < 2 ? w.x : e < 4 ? w.y : e < 6 ? w.z : w.w);
-        return (int32_t)(int16_t)(d32 >> (16 * (e & 1)));
-    };
-    // row pass: natural rows 4h + i (the two candidate positions are compile-time; h selects)
-    int32_t R[4][8];
-    int32_t hi = 0, lo = 0;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const int z0 = kZigOfNatC[8 * i + j], z1 = kZigOfNatC[8 * (4 + i) + j];
-            const int32_t v0 = m24(coef(z0), qt(z0)), v1 = m24(coef(z1), qt(z1));  // int16 x 8-bit: exact
-            R[i][j] = h ? v1 : v0;
-            if (i != 0 || j != 0) {
-                hi = max(hi, R[i][j]);
-                lo = min(lo, R[i][j]);
-            }
-        }
-    }
-    // the absolute DC: the pool cell (or its int32 escape) plus the block's offset
-    if (h == 0) R[0][0] = wmul(blk_dc((int16_t)c[0].x, dcv, loc), qt(0));
-    hi = max(hi, R[0][0]);
-    lo = min(lo, R[0][0]);
-    const bool fast = __all(hi < (1 << 14) && lo > -(1 << 14));
-    if (fast) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) idct_row_full(R[i]);
-    } else {  // the reference code, shortcuts and 32-bit wrap-around included
-#pragma unroll
-        for (int i = 0; i < 4; ++i) idct_row<false>(R[i]);
-    }
-    // quadrant swap: lane h keeps columns 4h..4h+3 of its rows and gets the partner's
-    int32_t C[8][4];  // C[r][jj] = natural row r, column 4h + jj
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-#pragma unroll
-        for (int jj = 0; jj < 4; ++jj) {
-            const int32_t keep = h ? R[i][4 + jj] : R[i][jj];
-            const int32_t got = pair_swap(h ? R[i][jj] : R[i][4 + jj]);
-            C[i][jj] = h ? got : keep;
-            C[4 + i][jj] = h ? keep : got;
-        }
-    }
-    if (fast) {  // the four columns' unclipped outputs, then clip and pack a row's four bytes at once
-        int32_t o[4][8];
-#pragma unroll
-        for (int jj = 0; jj < 4; ++jj) {
-            int32_t col[8];
-#pragma unroll
-            for (int r = 0; r < 8; ++r) col[r] = C[r][jj];
-            idct_col_raw(col, o[jj]);
-        }
-#pragma unroll
-        for (int r = 0; r < 8; ++r) rowd[r] = sat4<14>(o[0][r], o[1][r], o[2][r], o[3][r]);
-        return;
-    }
-#pragma unroll
-    for (int r = 0; r < 8; ++r) rowd[r] = 0;
-#pragma unroll
-    for (int jj = 0; jj < 4; ++jj) {
-        int32_t col[8];
-#pragma unroll
-        for (int r = 0; r < 8; ++r) col[r] = C[r][jj];
-        uint8_t o[8];
-        idct_col<false>(col, o);
-#pragma unroll
-        for (int r = 0; r < 8; ++r) rowd[r] |= (uint32_t)o[r] << (8 * jj);
-    }
-}
 // A dequant table (64 bytes of Desc::q, 4-byte aligned) into registers straight from global
-// memory: the lane-pair IDCT kernels then use no LDS at all, so they can run beside the other
-// pipeline's LDS-bound entropy kernels.
+// memory: k_idct420s then uses no LDS at all, so it can run beside the other pipeline's LDS-bound
+// entropy kernels.
 __device__ __forceinline__ void load_qw_g(const uint8_t* q, uint32_t (&qw)[16]) {
     const uint32_t* p = reinterpret_cast<const uint32_t*>(q);
 #pragma unroll
     for (int k = 0; k < 16; ++k) qw[k] = p[k];
 }
-__device__ __forceinline__ void load_qw(const uint8_t* qz, uint32_t (&qw)[16]) {  // 64 bytes of LDS, 16-byte aligned
-    const uint4* qs = reinterpret_cast<const uint4*>(qz);
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const uint4 w = qs[k];
-        qw[4 * k] = w.x; qw[4 * k + 1] = w.y; qw[4 * k + 2] = w.z; qw[4 * k + 3] = w.w;
-    }
-}
-// The block's 16-byte zig-zag chunks that lane h of a pair uses: natural rows 0-3 (h = 0) lie in
-// chunks {0,1,2,3,5,6}, rows 4-7 (h = 1) in {1,2,4,5,6,7}. So a lane loads six chunks, and its
-// chunk 0 / 3 slots hold chunks 4 / 7 for h = 1 (pair_idct selects between the halves' values,
-// and a half never reads the other half's private chunks): 6 loads per lane instead of 8.
-__device__ __forceinline__ void load_block(const int16_t* ac, int64_t blk, int h, int4 (&c)[8]) {
-    const int4* src = reinterpret_cast<const int4*>(ac + blk * 64);
-    c[0] = nt_ld(src + (h ? 4 : 0));
-    c[1] = nt_ld(src + 1);
-    c[2] = nt_ld(src + 2);
-    c[3] = nt_ld(src + (h ? 7 : 3));
-    c[5] = nt_ld(src + 5);
-    c[6] = nt_ld(src + 6);
-    c[4] = c[0];
-    c[7] = c[3];
-}
-
-// A wave's units wid, wid + nw, ... (wave-uniform loop): unit u's coefficient block is at
-// pendf(u) (blk_pend: its pool block and DC offset once resolved), transformed and stored by
-// unit(u, c, loc). Software-pipelined: unit u's block is loaded during unit u - nw and its map
-// entry during the unit before that, and the loop alternates two register sets, so a wave waits
-// only for loads issued one unit earlier -- never for its own stores (unit() must issue the same
-// stores on every path, so the compiler can count them) and never for a register copy of a load
-// in flight. (Before, the next unit's map entry was waited for right after it was issued,
-// together with the unit's own block loads: one full memory latency per unit.)
-template <class PendF, class UnitF>
-__device__ __forceinline__ void idct_units(const int16_t* ac, const Desc& d, int h, uint32_t wid, uint32_t nw,
-                                           uint32_t nunits, PendF pendf, UnitF unit) {
-    if (wid >= nunits) return;
-    auto at = [&](uint32_t u) { return pendf(min(u, nunits - 1)); };  // (past the end: harmless reloads)
-    int4 ca[8], cb[8];
-    BlkLoc la = blk_resolve(d, at(wid)), lb;
-    load_block(ac, la.blk, h, ca);
-    BlkPend pa, pb = at(wid + nw);
-    auto step = [&](uint32_t u, const int4 (&D)[8], const BlkLoc& lD, int4 (&Dn)[8], BlkLoc& lDn, const BlkPend& Pn,
-                    BlkPend& Pa) {
-        lDn = blk_resolve(d, Pn);
-        load_block(ac, lDn.blk, h, Dn);
-        Pa = at(u + 2 * nw);
-        unit(u, D, lD);
-    };
-    for (uint32_t u = wid;;) {
-        step(u, ca, la, cb, lb, pb, pa);
-        if ((u += nw) >= nunits) break;
-        step(u, cb, lb, ca, la, pa, pb);
-        if ((u += nw) >= nunits) break;
-    }
-}
-
-// Waves per SIMD the 4:2:0 IDCT kernels are compiled for (timing experiments: 5 keeps them at 96
-// VGPRs, so a wave fits beside four k_gw_lane waves on a SIMD).
-#ifndef ICX_IDCT_Y_MINW
-#define ICX_IDCT_Y_MINW 4
-#endif
-#ifndef ICX_IDCT_C_MINW
-#define ICX_IDCT_C_MINW 1
-#endif
-
-// Chroma planes of fused420 images: a wave's unit is 16 MCUs of one MCU row; lane pair q < 16
-// takes Cb of MCU mx0 + q, q >= 16 Cr of MCU mx0 + q - 16, so each plane row of the unit is
-// 128 contiguous bytes written by one store instruction.
-__global__ __launch_bounds__(256, ICX_IDCT_C_MINW) void k_idct420c(const Desc* __restrict__ desc, const int16_t* __restrict__ ac,
-                                                  const int32_t* __restrict__ dcv, const uint2* __restrict__ map,
-                                                  uint8_t* __restrict__ planes, int64_t plane_cap) {
-    const int img = blockIdx.y;
-    const Desc& d = desc[img];
-    if (!fused420(d)) return;
-    const int t = threadIdx.x;
-    const int wave = __builtin_amdgcn_readfirstlane(t >> 6), lane = t & 63, q = lane >> 1, h = lane & 1, cc = q >> 4, mq = q & 15;
-    uint32_t qw[16], qb[16];
-    load_qw_g(d.q[d.c[1].tq], qw);
-    load_qw_g(d.q[d.c[2].tq], qb);
-#pragma unroll
-    for (int k = 0; k < 16; ++k) qw[k] = cc ? qb[k] : qw[k];
-    const int mbw = d.mbw, stride = d.c[1].stride;
-    // Cb plane base (wave-uniform) and the Cr lanes' 32-bit offset from it (a chroma plane is
-    // at most (65535 / 2)^2 bytes)
-    uint8_t* Pc = planes + (int64_t)img * plane_cap + comp_plane_off(d, 1);
-    const uint32_t ccoff = cc ? (uint32_t)(comp_plane_off(d, 2) - comp_plane_off(d, 1)) : 0u;
-    const uint32_t ucols = (uint32_t)((mbw + 15) >> 4), nunits = ucols * (uint32_t)d.mbh;
-    const uint32_t chunk0 = (gridDim.x & 7) ? blockIdx.x : (blockIdx.x & 7) * (gridDim.x >> 3) + (blockIdx.x >> 3);
-    const uint32_t wid = chunk0 * 4 + wave, nw = gridDim.x * 4;
-    // a lane pair past the row's last MCU transforms that MCU's block again and stores the same
-    // bytes at its place (the pair that owns it is in the same unit): every lane stores
-    auto pendf = [&](uint32_t u) {
-        const uint32_t mby = u / ucols;
-        const int mx = (int)((u - mby * ucols) << 4) + mq;
-        return blk_pend(d, map, ((int64_t)mby * mbw + min(mx, mbw - 1)) * 6 + 4 + cc);
-    };
-    auto unit = [&](uint32_t u, const int4 (&c)[8], const BlkLoc& l) {
-        const uint32_t mby = u / ucols;
-        const int mx = min((int)((u - mby * ucols) << 4) + mq, mbw - 1);
-        uint32_t rowd[8];
-        pair_idct(c, qw, h, dcv, l, rowd);
-        // the unit's row base is wave-uniform (scalar); a lane adds a 32-bit offset per row, so
-        // the stores take the SGPR-base + VGPR-offset form with one VALU add each
-        uint8_t* const rowp = Pc + (int64_t)mby * 8 * stride;
-        const uint32_t lo = ccoff + (uint32_t)(mx * 8 + 4 * h);
-#pragma unroll
-        for (int r = 0; r < 8; ++r) nt_st(rowd[r], reinterpret_cast<uint32_t*>(rowp + (lo + (uint32_t)(r * stride))));
-    };
-    idct_units(ac, d, h, wid, nw, nunits, pendf, unit);
-}
-
-// Luma planes of fused420 images when the conversion reads them from HBM (ICX_FUSE420 = 2): a
-// wave's unit is 8 MCUs of one MCU row; lane pair q takes luma block q & 3 of MCU mx0 + (q >> 2),
-// so each store instruction writes two whole 128-byte plane rows (the unit's upper and lower
-// block rows).
-__global__ __launch_bounds__(256, ICX_IDCT_Y_MINW) void k_idct420y(const Desc* __restrict__ desc, const int16_t* __restrict__ ac,
-                                                  const int32_t* __restrict__ dcv, const uint2* __restrict__ map,
-                                                  uint8_t* __restrict__ planes, int64_t plane_cap) {
-    const int img = blockIdx.y;
-    const Desc& d = desc[img];
-    if (!fused420(d)) return;
-    const int t = threadIdx.x;
-    const int wave = __builtin_amdgcn_readfirstlane(t >> 6), lane = t & 63, q = lane >> 1, h = lane & 1, mq = q >> 2, k = q & 3;
-    int sbx, sby;
-    (void)mcu_block_comp(d, k, sbx, sby);
-    uint32_t qw[16];
-    load_qw_g(d.q[d.c[0].tq], qw);
-    const int mbw = d.mbw, stride = d.c[0].stride;
-    uint8_t* Py = planes + (int64_t)img * plane_cap;  // component 0 is first in the slot
-    const uint32_t ucols = (uint32_t)((mbw + 7) >> 3), nunits = ucols * (uint32_t)d.mbh;
-    const uint32_t chunk0 = (gridDim.x & 7) ? blockIdx.x : (blockIdx.x & 7) * (gridDim.x >> 3) + (blockIdx.x >> 3);
-    const uint32_t wid = chunk0 * 4 + wave, nw = gridDim.x * 4;
-    auto pendf = [&](uint32_t u) {  // (past the row's last MCU: that MCU again, as in k_idct420c)
-        const uint32_t mby = u / ucols;
-        const int mx = (int)((u - mby * ucols) << 3) + mq;
-        return blk_pend(d, map, ((int64_t)mby * mbw + min(mx, mbw - 1)) * 6 + k);
-    };
-    auto unit = [&](uint32_t u, const int4 (&c)[8], const BlkLoc& l) {
-        const uint32_t mby = u / ucols;
-        const int mx = min((int)((u - mby * ucols) << 3) + mq, mbw - 1);
-        uint32_t rowd[8];
-        pair_idct(c, qw, h, dcv, l, rowd);
-        uint8_t* const rowp = Py + (int64_t)mby * 16 * stride;  // (as in k_idct420c)
-        const uint32_t lo = (uint32_t)(sby * 8 * stride + mx * 16 + sbx * 8 + 4 * h);
-#pragma unroll
-        for (int r = 0; r < 8; ++r) nt_st(rowd[r], reinterpret_cast<uint32_t*>(rowp + (lo + (uint32_t)(r * stride))));
-    };
-    idct_units(ac, d, h, wid, nw, nunits, pendf, unit);
-}
-
 #ifndef ICX_IDCT1_MINW
 #define ICX_IDCT1_MINW 4
 #endif
-#ifndef ICX_IDCT1_PF
-#define ICX_IDCT1_PF 0
-#endif
 // ---------------------------------------------------- one-lane-per-block 4:2:0 IDCT (mode 4)
-// One lane transforms one whole block in registers: no pair hand-off (the lane-pair IDCT spends
-// a select per coefficient on which half of the block a lane holds, and a DPP swap plus two
-// selects per output of the row pass on the quadrant exchange), every row and column pass
-// within the lane. A wave's unit is 64 horizontally adjacent blocks of one block row of a plane
-// (512 pixels), so each of the block's 8 row stores is one 8-byte store per lane and the wave
+// One lane transforms one whole block in registers, every row and column pass within the lane
+// (no hand-off between lanes). A wave's unit is 64 horizontally adjacent blocks of one block row
+// of a plane (512 pixels), so each of the block's 8 row stores is one 8-byte store per lane and the wave
 // writes 512 contiguous bytes per instruction. Dequant reads the int16 cell and the 8-bit table
 // entry by SDWA into one 24-bit multiply; clip and pack by sat4<14>. NanoJPEG's own row / column
 // code (shortcuts and 32-bit wrap-around, jpeg_dec.h:350-442) runs for a block whose dequantized
-// coefficients reach 2^14, as in pair_idct (a per-lane branch: valid streams do not take it).
+// coefficients reach 2^14 (a per-lane branch: valid streams do not take it).
 __device__ __forceinline__ void load_block8(const int16_t* ac, int64_t blk, int4 (&c)[8]) {
     const int4* src = reinterpret_cast<const int4*>(ac + blk * 64);
 #pragma unroll
-    for (int k = 0; k < 8; ++k) c[k] = nt_ld(src + k);
+    for (int k = 0; k < 8; ++k) c[k] = ld16(src + k);
 }
 // Dequant of one block into R (natural order, the absolute DC at R[0][0]) and the range of its
 // values (the fast-path test of block_transform).
@@ -1698,8 +1341,7 @@ __device__ __forceinline__ void block_idct(const int4 (&c)[8], const uint32_t (&
 // Units of one plane: `ucols` units of 64 blocks per block row, `nby` block rows; unit u's lane
 // takes block column bx = (u % ucols) * 64 + lane, clamped to the row (a lane past the row's end
 // transforms its last block again and stores the same bytes at the same place: every lane
-// stores). blkn(bx, by) = the block's index in the image's MCU order. Software-pipelined like
-// idct_units: the next unit's block is loaded during this one, its map entry the unit before.
+// stores). blkn(bx, by) = the block's index in the image's MCU order.
 template <class BlkN>
 __device__ __forceinline__ void plane_units(const Desc& d, const int16_t* ac, const int32_t* dcv, const uint2* map,
                                             const uint32_t (&qw)[16], uint8_t* P, int stride, uint32_t nbx,
@@ -1724,28 +1366,12 @@ __device__ __forceinline__ void plane_units(const Desc& d, const int16_t* ac, co
 #pragma unroll
         for (int r = 0; r < 8; ++r) {
             const uint2 v = make_uint2(rowd[2 * r], rowd[2 * r + 1]);
-            nt_st(v, reinterpret_cast<uint2*>(rowp + (lo + (uint32_t)(r * stride))));
+            *reinterpret_cast<uint2*>(rowp + (lo + (uint32_t)(r * stride))) = v;
         }
     };
-#if ICX_IDCT1_PF  // the next unit's block loaded during this one (two register sets)
-    int4 ca[8], cb[8];
-    BlkLoc la = blk_resolve(d, pend(wid)), lb;
-    load_block8(ac, la.blk, ca);
-    BlkPend pa, pb = pend(wid + nw);
-    auto step = [&](uint32_t u, const int4 (&D)[8], const BlkLoc& lD, int4 (&Dn)[8], BlkLoc& lDn, const BlkPend& Pn,
-                    BlkPend& Pa) {
-        lDn = blk_resolve(d, Pn);
-        load_block8(ac, lDn.blk, Dn);
-        Pa = pend(u + 2 * nw);
-        unit(u, D, lD);
-    };
-    for (uint32_t u = wid;;) {
-        step(u, ca, la, cb, lb, pb, pa);
-        if ((u += nw) >= nunits) break;
-        step(u, cb, lb, ca, la, pa, pb);
-        if ((u += nw) >= nunits) break;
-    }
-#else  // only the map entry one unit ahead: the block's loads wait out their latency (other waves run)
+    // Only the map entry is loaded one unit ahead: the block's loads wait out their latency (other
+    // waves run). Loading the next unit's block too, in a second register set, measured slower
+    // (mode 5, 2 groups of 256: 246.3-246.8 against 249.5-250.3 GP/s).
     BlkPend p = pend(wid);
     for (uint32_t u = wid; u < nunits; u += nw) {
         const BlkLoc l = blk_resolve(d, p);
@@ -1754,7 +1380,6 @@ __device__ __forceinline__ void plane_units(const Desc& d, const int16_t* ac, co
         p = pend(u + nw);
         unit(u, c, l);
     }
-#endif
 }
 // All three planes of fused420 images: gridDim.x workgroups per image walk the luma units, then
 // the Cb and Cr units (one grid-stride sequence over the three planes' units); with luma == 0 only
@@ -1799,111 +1424,22 @@ __global__ __launch_bounds__(256, ICX_IDCT1_MINW) void k_idct420s(const Desc* __
     }
 }
 
-// Workgroup barrier for LDS hand-offs only: waits for this wave's LDS operations, not for its
-// global stores (__syncthreads would also wait vmcnt(0), i.e. for every RGB store in flight).
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
-// Luma IDCT + conversion of fused420 images. Each wave owns a strip of 16 MCUs (256 pixels) by
-// kFB MCU rows, like a k_convert_stream strip: per MCU row it transforms the row's 64 luma blocks
-// (two rounds of 32 lane pairs) into its own 16 x 256 luma rows in LDS, then converts those 16
-// rows with the chroma window carried in registers from the MCU row above (kv_rows: chroma
-// from the planes k_idct420c wrote, luma from LDS). No workgroup barriers.
-constexpr int kFB = 4;
-__global__ __launch_bounds__(256) void k_fused420(const Desc* __restrict__ desc, const int16_t* __restrict__ ac,
-                                                  const int32_t* __restrict__ dcv, const uint2* __restrict__ map,
-                                                  const uint8_t* __restrict__ planes, int64_t plane_cap, uint8_t* __restrict__ out,
-                                                  uint64_t out_stride) {
-    const int img = blockIdx.y;
-    const Desc& d = desc[img];
-    if (!fused420(d)) return;
-    __shared__ uint32_t Yl_all[4][16][64];  // per wave: its strip's 16 luma rows of the MCU row
-    __shared__ __attribute__((aligned(16))) uint8_t qz[64];
-    const int t = threadIdx.x;
-    if (t < 64) qz[t] = d.q[d.c[0].tq][t];
-    __syncthreads();
-    const int wave = __builtin_amdgcn_readfirstlane(t >> 6), lane = t & 63, h = lane & 1, k = (lane >> 1) & 3;
-    uint32_t (*Yl)[64] = Yl_all[wave];
-    int sbx, sby;
-    (void)mcu_block_comp(d, k, sbx, sby);
-    uint32_t qw[16];
-    load_qw(qz, qw);
-    const int W = d.W, H = d.H, mbw = d.mbw, mbh = d.mbh;
-    const uint8_t* pslot = planes + (int64_t)img * plane_cap;
-    const CPl c1{pslot + comp_plane_off(d, 1), d.c[1].w, d.c[1].h, d.c[1].stride};
-    const CPl c2{pslot + comp_plane_off(d, 2), d.c[2].w, d.c[2].h, d.c[2].stride};
-    uint8_t* o = out + (int64_t)img * out_stride;
-    const StreamOut so{o, W, ((reinterpret_cast<uintptr_t>(o) & 3) == 0) && (W & 3) == 0};
-    const int nsx = (mbw + 15) >> 4, nsy = (mbh + kFB - 1) / kFB, nstrip = nsx * nsy;
-    for (int strip = blockIdx.x * 4 + wave; strip < nstrip; strip += gridDim.x * 4) {
-        const int sy = strip / nsx, sx = strip - sy * nsx;
-        const int mx0 = sx << 4, mb0 = sy * kFB, mb1 = min(mbh, mb0 + kFB);
-        const int x0 = 256 * sx + 4 * lane, M = x0 >> 2;
-        const bool xl = x0 < W;
-        const int nb = min(4, W - x0) * 3;
-        const bool f1 = M >= 1 && x0 + 3 <= 2 * c1.w - 4 && 2 * M + 5 < c1.s;
-        const bool f2 = M >= 1 && x0 + 3 <= 2 * c2.w - 4 && 2 * M + 5 < c2.s;
-        KvWin w;
-        kv_init<true>(w, c1, c2, M, f1, f2, 8 * mb0);
-        for (int mby = mb0; mby < mb1; ++mby) {
-#pragma unroll
-            for (int r2 = 0; r2 < 2; ++r2) {  // the MCU row's 16 x 4 luma blocks, 32 per round
-                const int mq = (lane >> 3) + 8 * r2, mx = mx0 + mq;
-                const bool live = mx < mbw;
-                const int64_t n = ((int64_t)mby * mbw + (live ? mx : mbw - 1)) * 6 + k;
-                int4 c[8];
-                const BlkLoc l = blk_loc(d, map, n);
-                load_block(ac, l.blk, h, c);
-                uint32_t rowd[8];
-                pair_idct(c, qw, h, dcv, l, rowd);
-                if (live) {
-                    const int lc = mq * 4 + sbx * 2 + h;
-#pragma unroll
-                    for (int r = 0; r < 8; ++r) Yl[sby * 8 + r][lc] = rowd[r];
-                }
-            }
-            asm volatile("" ::: "memory");  // (a wave's LDS accesses execute in order)
-            const int Y0 = 16 * mby, Y1 = min(H, Y0 + 16);
-            if (xl) {
-                auto luma = [&](int y) { return Yl[y - Y0][lane]; };
-                auto emit = [&](int y, uint32_t yv, uint32_t cb, uint32_t cr) {
-                    uint32_t w[3];
-                    ycc4_to_rgb(yv, cb, cr, w);
-                    so.put3(y, x0, w, nb);
-                };
-                kv_rows<true>(w, c1, c2, M, f1, f2, Y0, Y1, luma, emit);
-            }
-            asm volatile("" ::: "memory");
-        }
-    }
-}
-
 // Mode 5: the luma IDCT inside the conversion with the one-lane IDCT (k_idct420s transforms only
 // the chroma planes). A wave owns a strip of 16 MCUs (256 pixels) by kFB5 MCU rows; per MCU row
 // lane l transforms luma block l & 3 of MCU mx0 + (l >> 2) -- the row's 64 blocks, one per lane
-// -- into the wave's 16 x 256 luma rows in LDS, then converts those 16 rows as k_fused420 does
-// (kv_rows: the chroma window carried in registers from the MCU row above, chroma from the planes,
+// -- into the wave's 16 x 256 luma rows in LDS, then converts those 16 rows (kv_rows: the chroma
+// window carried in registers from the MCU row above through the IDCT, chroma from the planes,
 // luma from LDS). The luma plane (16.8 MB per 4096^2 image, written and read back in mode 4) never
 // goes through HBM. The next MCU row's block is loaded before this row's conversion, its map entry
-// a row earlier. No workgroup barriers.
+// a row earlier. No workgroup barriers after the table is staged.
+// The quantisation table sits in LDS and is read into VGPRs per block, just before the
+// dequantisation (short-lived: held in SGPRs it was spilled to VGPR lanes, 63 v_readlane per block;
+// held in VGPRs throughout, 168 VGPRs and C3 -1.1%).
 #ifndef ICX_FB5
 #define ICX_FB5 4
 #endif
 #ifndef ICX_FUSED5_MINW  // 3: 152 VGPRs, no spills (4 spills; measured slower)
 #define ICX_FUSED5_MINW 3
-#endif
-// (timing variants: ICX_F5_CARRY=0 sets the chroma window up again per MCU row instead of carrying
-// it through the IDCT's registers; ICX_F5_PF=0 loads a row's block at the start of its IDCT)
-#ifndef ICX_F5_CARRY
-#define ICX_F5_CARRY 1
-#endif
-#ifndef ICX_F5_PF
-#define ICX_F5_PF 1
-#endif
-#ifndef ICX_F5_QV  // 1: the quantisation table in VGPRs (168 VGPRs, no v_readlane): C3 -1.1%
-#define ICX_F5_QV 0
-#endif
-#ifndef ICX_F5_QL  // 1: the table in LDS, into VGPRs per block (short-lived: no v_readlane of spilled SGPRs)
-#define ICX_F5_QL 1
 #endif
 constexpr int kFB5 = ICX_FB5;
 __global__ __launch_bounds__(256, ICX_FUSED5_MINW) void k_fused420s(const Desc* __restrict__ desc, const int16_t* __restrict__ ac,
@@ -1916,21 +1452,9 @@ __global__ __launch_bounds__(256, ICX_FUSED5_MINW) void k_fused420s(const Desc* 
     __shared__ __attribute__((aligned(16))) uint32_t Yl_all[4][16][64];  // per wave: 16 luma rows x 256 pixels
     const int wave = wave_index(), lane = threadIdx.x & 63, mq = lane >> 2, k = lane & 3, sbx = k & 1, sby = k >> 1;
     uint32_t (*Yl)[64] = Yl_all[wave];
-    uint32_t qw[16];
-#if ICX_F5_QL  // the table in LDS, read into VGPRs per block just before the dequantisation
     __shared__ __attribute__((aligned(16))) uint32_t qlds[16];
     if (threadIdx.x < 16) qlds[threadIdx.x] = reinterpret_cast<const uint32_t*>(d.q[d.c[0].tq])[threadIdx.x];
     __syncthreads();
-#endif
-    load_qw_g(d.q[d.c[0].tq], qw);
-#if ICX_F5_QV  // in vector registers, read by SDWA (in scalar registers they were spilled to VGPR lanes: 63 v_readlane per block)
-#pragma unroll
-    for (int k2 = 0; k2 < 16; ++k2) asm volatile("" : "+v"(qw[k2]));
-#elif ICX_F5_QL
-#else
-#pragma unroll
-    for (int k2 = 0; k2 < 16; ++k2) qw[k2] = __builtin_amdgcn_readfirstlane(qw[k2]);
-#endif
     const int W = d.W, H = d.H, mbw = d.mbw, mbh = d.mbh;
     const uint8_t* pslot = planes + (int64_t)img * plane_cap;
     const CPl c1{pslot + comp_plane_off(d, 1), d.c[1].w, d.c[1].h, d.c[1].stride};
@@ -1959,51 +1483,34 @@ __global__ __launch_bounds__(256, ICX_FUSED5_MINW) void k_fused420s(const Desc* 
         const int mxl = min(mx0 + mq, mbw - 1);
         auto nblk = [&](int mby) { return ((int64_t)min(mby, mb1 - 1) * mbw + mxl) * 6 + k; };
         BlkPend p = blk_pend(d, map, nblk(mb0));
-#if ICX_F5_CARRY
         KvWin w;
         if (conv) kv_init<true>(w, c1, c2, Mc, true, true, 8 * mb0);
-#endif
-#if ICX_F5_PF  // the next MCU row's block loaded before this row's conversion
+        // the next MCU row's block is loaded before this row's conversion
         BlkLoc l = blk_resolve(d, p);
         int4 c[8];
         load_block8(ac, l.blk, c);
         p = blk_pend(d, map, nblk(mb0 + 1));
-#endif
         for (int mby = mb0; mby < mb1; ++mby) {
             {
-#if !ICX_F5_PF
-                const BlkLoc l = blk_resolve(d, p);
-                int4 c[8];
-                load_block8(ac, l.blk, c);
-                p = blk_pend(d, map, nblk(mby + 1));
-#endif
                 uint32_t rowd[16];
-#if ICX_F5_QL
-                {
-                    asm volatile("" ::: "memory");  // (reloaded per block: not hoisted out of the loop)
-                    uint32_t qv[16];
+                asm volatile("" ::: "memory");  // (the table is reloaded per block: not hoisted out of the loop)
+                uint32_t qv[16];
 #pragma unroll
-                    for (int q4 = 0; q4 < 4; ++q4) {
-                        const uint4 t4 = reinterpret_cast<const uint4*>(qlds)[q4];
-                        qv[4 * q4] = t4.x;
-                        qv[4 * q4 + 1] = t4.y;
-                        qv[4 * q4 + 2] = t4.z;
-                        qv[4 * q4 + 3] = t4.w;
-                    }
-                    block_idct(c, qv, dcv, l, rowd);
+                for (int q4 = 0; q4 < 4; ++q4) {
+                    const uint4 t4 = reinterpret_cast<const uint4*>(qlds)[q4];
+                    qv[4 * q4] = t4.x;
+                    qv[4 * q4 + 1] = t4.y;
+                    qv[4 * q4 + 2] = t4.z;
+                    qv[4 * q4 + 3] = t4.w;
                 }
-#else
-                block_idct(c, qw, dcv, l, rowd);
-#endif
+                block_idct(c, qv, dcv, l, rowd);
                 uint2* dst = reinterpret_cast<uint2*>(&Yl[sby * 8][mq * 4 + sbx * 2]);
 #pragma unroll
                 for (int r = 0; r < 8; ++r) dst[r * 32] = make_uint2(rowd[2 * r], rowd[2 * r + 1]);
             }
-#if ICX_F5_PF
             l = blk_resolve(d, p);
             load_block8(ac, l.blk, c);
             p = blk_pend(d, map, nblk(mby + 2));
-#endif
             asm volatile("" ::: "memory");  // (a wave's LDS accesses execute in order)
             const int Y0 = 16 * mby, Y1 = min(H, Y0 + 16);
             if (border) {  // (rare: border strips only)
@@ -2017,234 +1524,10 @@ __global__ __launch_bounds__(256, ICX_FUSED5_MINW) void k_fused420s(const Desc* 
                     ycc4_to_rgb(yv, cb, cr, wo);
                     so.put3(y, 4 * Mc, wo, nb);
                 };
-#if !ICX_F5_CARRY
-                // the chroma window is set up again per MCU row (its rows were just read by this
-                // wave, so mostly from L2) rather than carried through the IDCT's registers
-                KvWin w;
-                kv_init<true>(w, c1, c2, Mc, true, true, Y0 >> 1);
-#endif
                 kv_rows<true>(w, c1, c2, Mc, true, true, Y0, Y1, luma, emit);
             }
             asm volatile("" ::: "memory");
         }
-    }
-}
-
-// ------------------------------------------------- 4:2:0 back half in one kernel (mode 3)
-// Dequant + IDCT + H/V chroma doubling + YCbCr->RGB of fused420 images without any plane in
-// HBM: the coefficient blocks are read once and the RGB written once (the plane round trip was
-// half of the back half's bytes). A workgroup owns a strip of kBW MCUs (256 output columns) by
-// `seg` MCU rows and walks down it one MCU row per step; the planes of the rows in flight live in
-// LDS rings:
-//   phase A  IDCT of luma MCU row t+1 and chroma MCU row t+2 (+ the chroma blocks of the MCUs
-//            left and right of the strip: the horizontal taps read 2 samples past each side),
-//            the lane-pair IDCT of k_idct420y/c into the luma / raw chroma rings; then the
-//            horizontal doubling (jpeg_dec.h:736-760, the stride-end quirk included) of chroma
-//            row t+1 into the doubled ring
-//   barrier
-//   phase B  vertical doubling (:762-791) from the doubled rows t-1..t+1 and the conversion
-//            (:834-853) of output rows 16t .. 16t+15; 12-byte streaming stores.
-// Ring slots are chosen so that phase A of step t+1 never writes what phase B of step t reads
-// (one LDS-only barrier per step). The vertical taps read the rows two above and below, so a
-// segment also transforms the chroma of the MCU rows above and below it.
-#ifndef ICX_BACK_PP  // two register sets for the prefetched blocks (see the loop)
-#define ICX_BACK_PP 0
-#endif
-#ifndef ICX_BACK_MINW  // waves per SIMD k_back420 is compiled for
-#define ICX_BACK_MINW 4
-#endif
-constexpr int kBW = 16;     // strip width in MCUs: 64 lanes x 4 columns
-constexpr int kBRaw = 36;   // raw chroma row (dwords): 8 halo + 128 + 8 halo samples
-struct BackLds {
-    uint32_t y[3][16][64];         // luma rows of MCU rows t-1, t, t+1 (ring of 3)
-    uint32_t raw[2][2][8][kBRaw];  // raw Cb / Cr rows of 2 MCU rows, strip + halo columns
-    uint32_t dbl[4][2][8][64];     // horizontally doubled Cb / Cr rows of 4 MCU rows
-    uint32_t q[3][16];             // dequant tables (zig-zag, bytes) of Y, Cb, Cr
-};
-__global__ __launch_bounds__(256, ICX_BACK_MINW) void k_back420(const Desc* __restrict__ desc, const int16_t* __restrict__ ac,
-                                                 const int32_t* __restrict__ dcv, const uint2* __restrict__ map,
-                                                 uint8_t* __restrict__ out, uint64_t out_stride, int seg) {
-    const int img = blockIdx.y;
-    const Desc& d = desc[img];
-    if (!fused420(d)) return;
-    __shared__ __attribute__((aligned(16))) BackLds L;
-    const int t = threadIdx.x;
-    const int wave = __builtin_amdgcn_readfirstlane(t >> 6), lane = t & 63, p = t >> 1, h = t & 1;
-    const int W = d.W, H = d.H, mbw = d.mbw, mbh = d.mbh;
-    const int cw = d.c[1].w, chh = d.c[1].h, cs = d.c[1].stride;  // Cb and Cr: same geometry (1x1)
-    if (t < 48) L.q[t >> 4][t & 15] = reinterpret_cast<const uint32_t*>(d.q[d.c[t >> 4].tq])[t & 15];
-    // pair p's block in an MCU: 0..63 luma block p & 3 of strip MCU p >> 2; 64..95 Cb / Cr of
-    // strip MCU p & 15; 96..99 Cb / Cr of the MCU left (96, 97) / right (98, 99) of the strip
-    const int kb = p < 64 ? (p & 3) : (p < 96 ? 4 + ((p - 64) >> 4) : 4 + (p & 1));
-    const int dmx = p < 64 ? (p >> 2) : (p < 96 ? (p & 15) : (p < 98 ? -1 : kBW));
-    int sbx = 0, sby = 0;
-    if (kb < 4) (void)mcu_block_comp(d, kb, sbx, sby);
-    const uint8_t* qz = reinterpret_cast<const uint8_t*>(L.q[kb < 4 ? 0 : kb - 3]);
-    uint8_t* o = out + (int64_t)img * out_stride;
-    const StreamOut so{o, W, ((reinterpret_cast<uintptr_t>(o) & 3) == 0) && (W & 3) == 0};
-    const int nsx = (mbw + kBW - 1) / kBW, nseg = (mbh + seg - 1) / seg, items = nsx * nseg;
-    for (int it = blockIdx.x; it < items; it += gridDim.x) {
-        const int sg = it / nsx, sx = it - sg * nsx;
-        const int mx0 = sx * kBW, r0 = sg * seg, r1 = min(mbh, r0 + seg);
-        const int lo = max(r0 - 1, 0), hi = min(r1, mbh - 1);  // chroma MCU rows the segment needs
-        const int M = 64 * sx + lane, x0 = 4 * M;             // the lane's output columns x0 .. x0+3
-#ifdef ICX_EXP_BACK_NOSTORE
-        uint32_t sink = 0;
-#endif
-        // step tr transforms luma MCU row tr+1 and chroma MCU row tr+2: whether the pair has a
-        // block then, and where it is (clamped into the image where it has none)
-        auto live_at = [&](int tr) {
-            const int row = kb < 4 ? tr + 1 : tr + 2, mx = mx0 + dmx;
-            return (kb < 4 ? row >= r0 && row < r1 : row >= lo && row <= hi) && p < 100 && mx >= 0 && mx < mbw;
-        };
-        auto pend_at = [&](int tr) {
-            const int row = kb < 4 ? tr + 1 : tr + 2;
-            const int mxc = min(max(mx0 + dmx, 0), mbw - 1), rowc = min(max(row, 0), mbh - 1);
-#ifdef ICX_EXP_BACK_NOMAP  // timing experiment only: blocks as if written in place (wrong pixels)
-            return BlkPend{make_uint2(0, 0), d.acbase + ((int64_t)rowc * mbw + mxc) * 6 + kb};
-#else
-            return blk_pend(d, map, ((int64_t)rowc * mbw + mxc) * 6 + kb);
-#endif
-        };
-        // One step. Software pipeline: D (this step's block) was loaded during the previous step,
-        // issued before that step's RGB stores, and its map entry one step before that; this step
-        // resolves Pn (the next step's entry), loads the next step's block into Dn and the entry
-        // after it into Pa. The loop below alternates two register sets, so no register with a
-        // load in flight is ever copied (a copy waits for it: s_waitcnt vmcnt(0)).
-        auto step = [&](int tr, const int4 (&D)[8], const BlkLoc& lD, int4 (&Dn)[8], BlkLoc& lDn, const BlkPend& Pn,
-                        BlkPend& Pa) {
-            // ---- phase A: transforms
-            const int ry = tr + 1, rc = tr + 2;
-            const bool live = live_at(tr);
-            if (__any(live)) {  // wave-uniform
-                uint32_t qw[16];
-                load_qw(qz, qw);
-                uint32_t rowd[8];
-                pair_idct(D, qw, h, dcv, lD, rowd);
-                if (live) {
-                    if (kb < 4) {
-                        uint32_t* dst = &L.y[ry % 3][sby * 8][dmx * 4 + sbx * 2 + h];
-#pragma unroll
-                        for (int r = 0; r < 8; ++r) dst[r * 64] = rowd[r];
-                    } else {
-                        uint32_t* dst = &L.raw[rc & 1][kb - 4][0][(dmx + 1) * 2 + h];
-#pragma unroll
-                        for (int r = 0; r < 8; ++r) dst[r * kBRaw] = rowd[r];
-                    }
-                }
-            }
-            lDn = blk_resolve(d, Pn);
-#ifndef ICX_EXP_BACK_NOLOAD  // timing experiment only: keep transforming the first block (no loads)
-            load_block(ac, lDn.blk, h, Dn);  // (past the last step: a harmless reload)
-#endif
-            Pa = pend_at(tr + 2);
-            const int rd = tr + 1;  // horizontal doubling of chroma MCU row rd (written last step)
-            if (rd >= lo && rd <= hi) {
-                const bool interior = M >= 1 && x0 + 3 <= 2 * cw - 4;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const int task = wave * 4 + j, cc = task >> 3, r = task & 7;
-                    const uint32_t* rw = L.raw[rd & 1][cc][r];
-                    uint32_t v;
-                    if (interior) {  // samples 2M-2 .. 2M+3 at raw bytes 2 lane + 6 ..
-                        const int b0 = ((2 * lane + 6) >> 2);
-                        const uint64_t w = ((uint64_t)rw[b0] | ((uint64_t)rw[b0 + 1] << 32)) ^ 0x8080808080808080ull;
-                        const uint64_t b = w >> ((lane & 1) ? 0 : 16);
-                        const uint32_t w0 = (uint32_t)b, w1 = (uint32_t)(b >> 8), w2 = (uint32_t)(b >> 16);
-                        v = pack4(dtap(w0, kTapRev), dtap(w1, kTapFwd), dtap(w1, kTapRev), dtap(w2, kTapFwd));
-                    } else {  // image edges: the generic taps (the right edge reads from the stride end)
-                        const uint8_t* rb = reinterpret_cast<const uint8_t*>(rw);
-                        const int sh = 8 * mx0 - 8;  // chroma column of raw byte 0
-                        auto at = [&](int g) { return (int)rb[min(max(g - sh, 0), 4 * kBRaw - 1)]; };
-                        v = pmap([&](int i) {
-                            const int x = x0 + i;
-                            if (x >= 2 * cw) return 0;
-                            return (int)double_tap(x, cw, at, [&](int jj) { return at(cs - jj); });
-                        });
-                    }
-                    L.dbl[rd & 3][cc][r][lane] = v;
-                }
-            }
-#ifndef ICX_EXP_BACK_NOBAR  // timing experiment only: no barrier (wrong pixels)
-            lds_barrier();
-#endif
-            // ---- phase B: vertical doubling + conversion of output rows 16 tr + 4 wave .. + 3
-            const int y0 = 16 * tr + 4 * wave;
-            if (tr >= r0 && y0 < H) {  // wave-uniform
-                const int k0 = y0 >> 1;
-                const int nb = x0 < W ? min(4, W - x0) * 3 : 0;
-                uint32_t A[2][6];
-#pragma unroll
-                for (int cc = 0; cc < 2; ++cc)
-#pragma unroll
-                    for (int i = 0; i < 6; ++i) {
-                        const int r = min(max(k0 - 2 + i, 0), chh - 1);
-                        A[cc][i] = L.dbl[(r >> 3) & 3][cc][r & 7][lane];
-                    }
-#pragma unroll
-                for (int u = 0; u < 2; ++u) {
-                    const int k = k0 + u, y = 2 * k;
-                    if (y >= H) break;  // wave-uniform
-                    uint32_t ev[2], od[2];
-#pragma unroll
-                    for (int cc = 0; cc < 2; ++cc) {
-                        const uint32_t w0 = A[cc][u], w1 = A[cc][u + 1], w2 = A[cc][u + 2], w3 = A[cc][u + 3],
-                                       w4 = A[cc][u + 4];
-                        if (k >= 2 && k <= chh - 3) {
-                            uint32_t e[4], f[4];
-#pragma unroll
-                            for (int i = 0; i < 4; ++i) {
-                                e[i] = dtap(kv_column(w0, w1, w2, w3, i) ^ kBias8, kTapRev);
-                                f[i] = dtap(kv_column(w1, w2, w3, w4, i) ^ kBias8, kTapFwd);
-                            }
-                            ev[cc] = pack4(e[0], e[1], e[2], e[3]);
-                            od[cc] = pack4(f[0], f[1], f[2], f[3]);
-                        } else {
-                            ev[cc] = vtap_even(k, chh, w0, w1, w2, w3);
-                            od[cc] = vtap_odd(k, chh, w1, w2, w3, w4);
-                        }
-                    }
-                    const uint32_t(*Y)[64] = L.y[tr % 3];
-                    uint32_t wv[3];
-                    ycc4_to_rgb(Y[y - 16 * tr][lane], ev[0], ev[1], wv);
-#ifdef ICX_EXP_BACK_NOSTORE  // timing experiment only: no RGB stores (one per item keeps the work)
-                    sink ^= wv[0] ^ wv[1] ^ wv[2];
-#else
-                    so.put3(y, x0, wv, nb);
-#endif
-                    if (y + 1 < H) {
-                        ycc4_to_rgb(Y[y + 1 - 16 * tr][lane], od[0], od[1], wv);
-#ifdef ICX_EXP_BACK_NOSTORE
-                        sink ^= wv[0] ^ wv[1] ^ wv[2];
-#else
-                        so.put3(y + 1, x0, wv, nb);
-#endif
-                    }
-                }
-            }
-        };
-        lds_barrier();  // (the previous item's phase B is done with the rings; the q tables are in)
-#if ICX_BACK_PP
-        int4 ca[8], cb[8];
-        BlkLoc la = blk_resolve(d, pend_at(lo - 2)), lb;
-        BlkPend pa, pb = pend_at(lo - 1);
-        load_block(ac, la.blk, h, ca);
-        for (int tr = lo - 2;;) {
-            step(tr, ca, la, cb, lb, pb, pa);
-            if (++tr >= r1) break;
-            step(tr, cb, lb, ca, la, pa, pb);
-            if (++tr >= r1) break;
-        }
-#else  // one register set (the next step's block overwrites this one's once it is transformed)
-        int4 ca[8];
-        BlkLoc la = blk_resolve(d, pend_at(lo - 2));
-        BlkPend pa = pend_at(lo - 1);
-        load_block(ac, la.blk, h, ca);
-        for (int tr = lo - 2; tr < r1; ++tr) step(tr, ca, la, ca, la, pa, pa);
-#endif
-#ifdef ICX_EXP_BACK_NOSTORE
-        if (sink == 0x12345678u) o[lane] = 1;
-#endif
     }
 }
 
@@ -2303,13 +1586,12 @@ void launch_decode_back(const GroupWs& ws, int n, uint8_t* d_out, uint64_t out_s
     //   5 (default) k_idct420s transforms the chroma planes, k_fused420s the luma blocks inside
     //     the conversion (no luma plane in HBM); k_convert_edge takes the border lanes
     //   4 k_idct420s (one lane per block) for all three planes, then the stream conversion
-    //   3 k_back420, the whole back half without planes
-    //   2 the lane-pair IDCT k_idct420y / k_idct420c, then the stream conversion
-    //   1 k_idct420c + k_fused420 (round 2's luma IDCT inside the conversion, lane pairs)
-    //   0 the generic k_idct
+    //   0 the generic k_idct, then the stream conversion
+    // (modes 1-3, the lane-pair IDCT and whole-back-half kernels of rounds 2-4, lost their A/B
+    // runs and are gone; the surviving numbers are kept so profiles and DESIGN.md still read right)
     const int fuse = [] {  // (read per launch: tests switch modes within one process)
         const int v = std::getenv("ICX_FUSE420") ? std::atoi(std::getenv("ICX_FUSE420")) : 5;
-        return (v >= 0 && v <= 5) ? v : 5;
+        return (v == 0 || v == 4) ? v : 5;
     }();
     if (other || fuse == 0) {
         hipLaunchKernelGGL(k_idct, dim3(gx, n), dim3(256), 0, st, ws.desc, ws.ac, ws.dc, ws.map, ws.planes, ws.plane_cap,
@@ -2317,7 +1599,7 @@ void launch_decode_back(const GroupWs& ws, int n, uint8_t* d_out, uint64_t out_s
         hipLaunchKernelGGL(k_idct_any, dim3(gx, n), dim3(256), 0, st, ws.desc, ws.ac, ws.dc, ws.map, ws.planes,
                            ws.plane_cap);
     }
-    if (fuse == 4 || fuse == 5) {  // 4:2:0: 64 blocks of a block row per wave unit, luma (mode 4) then chroma units
+    if (fuse != 0) {  // 4:2:0: 64 blocks of a block row per wave unit, luma (mode 4) then chroma units
         // (units per wave: ICX_IDCT1_UPW, at least; small images' waves otherwise take one unit
         // each and its dependent map -> block -> store latency alone)
         static const int upw = std::getenv("ICX_IDCT1_UPW") ? std::max(1, std::atoi(std::getenv("ICX_IDCT1_UPW"))) : 1;
@@ -2326,35 +1608,11 @@ void launch_decode_back(const GroupWs& ws, int n, uint8_t* d_out, uint64_t out_s
         hipLaunchKernelGGL(k_idct420s, dim3(std::max(sgx, 8), n), dim3(256), 0, st, ws.desc, ws.ac, ws.dc, ws.map,
                            ws.planes, ws.plane_cap, fuse == 4 ? 1 : 0);
     }
-    if (fuse == 1 || fuse == 2) {  // 4:2:0: chroma planes (and, mode 2, luma planes) by the lane-pair IDCT
-        const int cgx = (int)std::max<int64_t>(1, std::min<int64_t>((maxblk / 6 / 16 + 31) / 32, 16384 / n)) & ~7;
-        hipLaunchKernelGGL(k_idct420c, dim3(std::max(cgx, 8), n), dim3(256), 0, st, ws.desc, ws.ac, ws.dc, ws.map,
-                           ws.planes, ws.plane_cap);
-        if (fuse == 2) {
-            const int ygx = (int)std::max<int64_t>(1, std::min<int64_t>((maxblk / 6 / 8 + 31) / 32, 16384 / n)) & ~7;
-            hipLaunchKernelGGL(k_idct420y, dim3(std::max(ygx, 8), n), dim3(256), 0, st, ws.desc, ws.ac, ws.dc, ws.map,
-                               ws.planes, ws.plane_cap);
-        }
-    }
     E(kStIdct);
-    // The kernels that read the coefficients inside the conversion (4:2:0 plane modes 1, 3, 5) run
+    // The kernel that reads the coefficients inside the conversion (4:2:0 plane mode 5) runs
     // before the generic upsample: its ping-pong planes (ws.tmp) live in the coefficient pool
     // (icx_api.cpp ws_alloc_all), which is dead from here on.
     B(kStConvert);
-    const int fgx = (int)std::max<int64_t>(1, std::min<int64_t>((((int64_t)(ws.max_w + 255) / 256) *
-                                                                  ((ws.max_h + 16 * kFB - 1) / (16 * kFB)) + 3) / 4,
-                                                                 16384 / n));
-    if (fuse == 3) {  // 4:2:0: the whole back half in k_back420, no planes
-        const int seg = std::getenv("ICX_BSEG")  // (read per launch: tests vary it)
-             ? std::max(1, std::atoi(std::getenv("ICX_BSEG"))) : 32;
-        const int64_t items = (int64_t)((ws.max_w + 16 * kBW - 1) / (16 * kBW)) * (((ws.max_h + 15) / 16 + seg - 1) / seg);
-        const int bgx = (int)std::max<int64_t>(1, std::min<int64_t>(items, 16384 / n));
-        hipLaunchKernelGGL(k_back420, dim3(bgx, n), dim3(256), 0, st, ws.desc, ws.ac, ws.dc, ws.map, d_out, out_stride,
-                           seg);
-    }
-    if (fuse == 1)
-        hipLaunchKernelGGL(k_fused420, dim3(fgx, n), dim3(256), 0, st, ws.desc, ws.ac, ws.dc, ws.map, ws.planes,
-                           ws.plane_cap, d_out, out_stride);
     if (fuse == 5) {
         const int64_t fs = ((int64_t)(ws.max_w + 255) / 256) * ((ws.max_h + 16 * kFB5 - 1) / (16 * kFB5));
         static const int spw = std::getenv("ICX_F5_SPW") ? std::max(1, std::atoi(std::getenv("ICX_F5_SPW"))) : 1;
@@ -2392,10 +1650,10 @@ void launch_decode_back(const GroupWs& ws, int n, uint8_t* d_out, uint64_t out_s
     const int egx = (int)std::max<int64_t>(1, std::min<int64_t>(egw, 16384 / n));
     const int ego = (int)std::max<int64_t>(1, std::min<int64_t>(egw, gwg / n));
     hipLaunchKernelGGL(k_convert_edge<3>, dim3(egx, n), dim3(256), 0, st, ws.desc, ws.planes, ws.plane_cap, d_out,
-                       out_stride, fuse);
+                       out_stride);
     if (other) {
         hipLaunchKernelGGL(k_convert_edge<1>, dim3(ego, n), dim3(256), 0, st, ws.desc, ws.planes, ws.plane_cap, d_out,
-                           out_stride, fuse);
+                           out_stride);
         hipLaunchKernelGGL(k_convert_fused, dim3(cx, n), dim3(256), 0, st, ws.desc, ws.planes, ws.plane_cap, d_out,
                            out_stride);
         hipLaunchKernelGGL(k_convert, dim3(cx, n), dim3(256), 0, st, ws.desc, ws.planes, ws.tmp, ws.plane_cap,

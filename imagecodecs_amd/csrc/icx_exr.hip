@@ -371,9 +371,6 @@ __global__ __launch_bounds__(kUnpackThreads) void k_exr_unpack(const uint8_t* __
     __syncthreads();
     m = produced;
     if (m == 0) return;
-#ifdef ICX_EXP_NOPRED  // timing experiment only: the inflate alone (output left predicted)
-    return;
-#endif
     // t'[i] = t[0] + sum_{k=1..i} (t[k] - 128) mod 256: each thread one contiguous segment of whole
     // dwords (t is 16-byte aligned), read and written a dword at a time
     const int64_t seg = ((m + kUnpackThreads - 1) / kUnpackThreads + 3) & ~(int64_t)3;

@@ -196,11 +196,7 @@ __device__ __forceinline__ BlkPend blk_pend(const Desc& d, const uint2* map, int
     return BlkPend{map[d.acbase + n], d.acbase + n};
 }
 __device__ __forceinline__ BlkLoc blk_resolve(const Desc& d, const BlkPend& q) {
-#ifdef ICX_EXP_BACK_NOMAP
-    return BlkLoc{q.n, 0};
-#else
     return d.mapped ? BlkLoc{(int64_t)q.e.x, (int32_t)q.e.y} : BlkLoc{q.n, 0};
-#endif
 }
 
 

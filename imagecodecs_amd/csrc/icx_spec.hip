@@ -544,248 +544,6 @@ __global__ __launch_bounds__(256) void k_ustf_write(int n, const uint8_t* __rest
     }
 }
 
-// ---- one-pass unstuff (k_ustf_one: count, scan and write in one launch) ----
-// A wave takes tiles in ticket order (an atomic counter), so every tile with a smaller ticket is
-// held by a wave that is running or done, and takes its next ticket once its tile's aggregate is
-// out. It compacts its tile's kept bytes into LDS, publishes
-// the tile's aggregate (kept bytes, restart markers, whether the data ends in it), then looks back
-// over the image's earlier tiles -- 64 at a time, one per lane, nearest first -- until it meets an
-// inclusive prefix (or the image's first tile), publishes its own inclusive prefix and writes its
-// bytes at that offset. The tile that ends the data (or the image's last tile) sets the image's
-// length, markers, error position and lane count and writes the reader padding (k_ustf_scan's
-// work). A state word is 2 flag bits (1 aggregate, 2 inclusive), an end bit, 21 bits of restart
-// markers and 40 bits of kept bytes (scan_len < 2^40); the array is zeroed before each launch.
-constexpr uint64_t kTsAgg = 1, kTsInc = 2;
-constexpr int kTsRstBits = 21;
-__device__ __forceinline__ uint64_t ts_pack(uint64_t flag, bool end, int64_t nrst, int64_t kept) {
-    return flag << 62 | (uint64_t)end << 61 | (uint64_t)nrst << 40 | (uint64_t)kept;
-}
-__device__ __forceinline__ int64_t ts_kept(uint64_t v) { return (int64_t)(v & (((uint64_t)1 << 40) - 1)); }
-__device__ __forceinline__ int64_t ts_rst(uint64_t v) { return (int64_t)((v >> 40) & ((1u << kTsRstBits) - 1)); }
-__device__ __forceinline__ bool ts_end(uint64_t v) { return (v >> 61) & 1; }
-__device__ __forceinline__ long long wave_sum_ll(long long v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-// The image owning flat tile t: the largest i with pre[i] <= t (pre non-decreasing, pre[0] <= t),
-// two rounds of one load per lane for n <= 4096 images.
-__device__ __forceinline__ int find_image_wave(const int32_t* pre, int n, int t, int lane) {
-    if (n > 4096) return find_image(pre, n, t);
-    const int step = (n + 63) >> 6;
-    const int k = lane * step;
-    const uint64_t m = __ballot(k < n && pre[min(k, n - 1)] <= t);
-    const int base = (63 - __clzll((long long)m)) * step;
-    const int k2 = base + lane;
-    const uint64_t m2 = __ballot(lane < step && k2 < n && pre[min(k2, n - 1)] <= t);
-    return base + 63 - __clzll((long long)m2);
-}
-constexpr int kTsSpinMax = 1 << 22;  // a predecessor that never publishes: the image gives up
-
-__global__ __launch_bounds__(256) void k_ustf_one(int n, const uint8_t* __restrict__ data, const uint64_t* __restrict__ off,
-                                                  const Desc* __restrict__ desc, SpecImg* __restrict__ spec,
-                                                  const int32_t* __restrict__ tilepre, const int32_t* __restrict__ totals,
-                                                  uint64_t* __restrict__ tstate, uint8_t* __restrict__ U,
-                                                  int64_t* __restrict__ rst, int64_t rst_cap) {
-    constexpr int kBufW = kTileBytes / 4 + 8;
-    __shared__ uint32_t sbuf_all[4][kBufW];
-    const int lane = threadIdx.x & 63;
-    uint32_t* sbuf = sbuf_all[threadIdx.x >> 6];
-    const uint8_t* sb = reinterpret_cast<const uint8_t*>(sbuf);
-    const int total = totals[0];
-    unsigned int* ticket = reinterpret_cast<unsigned int*>(tstate + total);  // (one word past the tiles)
-    auto take = [&]() {
-        int v = 0;
-        if (lane == 0) v = (int)atomicAdd(ticket, 1u);
-        return __builtin_amdgcn_readfirstlane(__shfl(v, 0));
-    };
-    // Relaxed (monotonic) agent-scope accesses: a state word carries everything a reader uses, so
-    // no ordering with other data is needed -- and an acquire / release at agent scope invalidates /
-    // writes back the whole L2 of the XCD on gfx950 (40x slower at C3: every spin iteration
-    // emptied the cache under the other waves' tiles).
-    auto ts_load = [&](int q) { return __hip_atomic_load(tstate + q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); };
-    auto ts_store = [&](int q, uint64_t v) {
-        if (lane == 0) __hip_atomic_store(tstate + q, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    };
-    TileImg im, imn;
-    TileChunks tc, tn;
-    int t = take();
-    if (t < total) {
-        im.set(find_image_wave(tilepre, n, t, lane), data, off, desc, spec, tilepre);
-        tc.load(im.R, im.L, im.t0(t), lane);
-    }
-    while (t < total) {  // wave-uniform
-        const int i = im.i;
-        SpecImg& s = spec[i];
-        const bool on = s.mode == 1 || s.mode == 3;
-        const uint8_t* R = im.R;
-        const int64_t L = im.L;
-        const int64_t t0 = im.t0(t);
-        for (int k = lane; k < kBufW / 4; k += 64) reinterpret_cast<uint4*>(sbuf)[k] = make_uint4(0u, 0u, 0u, 0u);
-        __builtin_amdgcn_wave_barrier();
-        int32_t giveup = 0;
-        int kept = 0, nrst = 0, end_err = 0;
-        bool own_end = false;
-        for (int r = 0; on && r < kTileBytes / 1024 && t0 + r * 1024 < L; ++r) {
-            const int64_t a = t0 + r * 1024 + lane * 16;
-            RstSink rs0{0, 0, nullptr, 0, 0};
-            const ChunkIn c = tc.next(a, lane);
-            const Ustf16 u = ustf16<true>(R, L, a, c.D, c.nx, c.prun, &giveup, &rs0);
-            const long long e = __any(u.end_at >= 0) ? wave_min_ll(u.end_at >= 0 ? (long long)u.end_at : LLONG_MAX)
-                                                     : LLONG_MAX;
-            const bool before = u.end_at >= 0 ? u.end_at <= e : a < e;
-            const int k = before ? u.kept : 0;
-            const int incl = wave_incl_scan(k);
-            nrst += before ? rs0.n : 0;
-            if (k) {  // (as k_ustf_write)
-                const int ob = kept + incl - k, q = ob >> 2, sft = ob & 3;
-                const uint32_t* d = u.out;
-                if (k == 16 && (ob & 15) == 0) {
-                    reinterpret_cast<uint4*>(sbuf)[q >> 2] = make_uint4(d[0], d[1], d[2], d[3]);
-                } else if (sft == 0) {
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) atomicOr(&sbuf[q + j], d[j]);
-                } else {
-                    atomicOr(&sbuf[q], d[0] << (8 * sft));
-#pragma unroll
-                    for (int j = 1; j < 4; ++j) atomicOr(&sbuf[q + j], __builtin_amdgcn_alignbyte(d[j], d[j - 1], 4 - sft));
-                    atomicOr(&sbuf[q + 4], d[3] >> (32 - 8 * sft));
-                }
-            }
-            kept += __shfl(incl, 63);
-            if (e != LLONG_MAX) {  // wave-uniform: the data ends in this round
-                const uint64_t owner = __ballot(u.end_at >= 0 && u.end_at == e);
-                end_err = __shfl(u.end_err, __ffsll((long long)owner) - 1);
-                own_end = true;
-                break;
-            }
-        }
-        nrst = __any(nrst) ? wave_sum(nrst) : 0;
-        if (__any(giveup) && lane == 0) atomicOr(&s.err, kSpecGiveUp);
-        ts_store(t, ts_pack(kTsAgg, own_end, min(nrst, (1 << kTsRstBits) - 1), kept));
-        // The next ticket only now: a wave holding a ticket it has not scanned would make every
-        // look-back that reaches that tile wait for this wave's whole current tile (and so on
-        // down the tickets: a serial chain). Its image and chunks load during the look-back.
-        const int tnx = take();
-        if (tnx < total) {
-            imn.set(find_image_wave(tilepre, n, tnx, lane), data, off, desc, spec, tilepre);
-            tn.load(imn.R, imn.L, imn.t0(tnx), lane);
-        }
-        // look back: the prefix before this tile (pk bytes, pr markers) and whether the data ended
-        // before it (pe)
-        int64_t pk = 0, pr = 0, ak = 0, ar = 0;
-        bool pe = false, ae = false, stuck = false;
-        for (int p = t - 1;; p -= 64) {  // wave-uniform
-            const int q = p - lane;
-            uint64_t v = ts_pack(kTsInc, false, 0, 0);  // before the image's first tile: prefix 0
-            if (q >= im.t_first) {
-                int spins = 0;
-                for (v = ts_load(q); (v >> 62) == 0 && spins < kTsSpinMax; ++spins) {
-                    __builtin_amdgcn_s_sleep(1);
-                    v = ts_load(q);
-                }
-                if ((v >> 62) == 0) {
-                    stuck = true;
-                    v = ts_pack(kTsInc, false, 0, 0);
-                }
-            }
-            const uint64_t mi = __ballot((v >> 62) == kTsInc);
-            const int m = mi ? __ffsll((long long)mi) - 1 : 64;  // nearest inclusive prefix
-            const uint64_t vm = __shfl(v, m & 63);
-            if (m < 64 && ts_end(vm)) {  // the data ended at or before it: its prefix is final
-                pk = ts_kept(vm);
-                pr = ts_rst(vm);
-                pe = true;
-                break;
-            }
-            // the farthest (earliest) tile below m whose data ends: the tiles nearer than it
-            // follow the end and count for nothing, nor does what nearer windows summed
-            const uint64_t me = __ballot(lane < m && ts_end(v));
-            const int e = me ? 63 - __clzll((long long)me) : -1;
-            const bool in = lane < m && lane >= (e < 0 ? 0 : e);
-            const int64_t wk = wave_sum_ll(in ? ts_kept(v) : 0), wr = wave_sum_ll(in ? ts_rst(v) : 0);
-            if (e >= 0) { ak = wk; ar = wr; ae = true; }
-            else { ak += wk; ar += wr; }
-            if (m < 64) {
-                pk = ts_kept(vm) + ak;
-                pr = ts_rst(vm) + ar;
-                pe = ae;
-                break;
-            }
-        }
-        if (__any(stuck) && lane == 0) atomicOr(&s.err, kSpecGiveUp);
-        const int64_t ik = pe ? pk : pk + kept, ir = pe ? pr : pr + nrst;
-        if (ir >= (1 << kTsRstBits) && lane == 0) atomicOr(&s.err, kSpecGiveUp);
-        ts_store(t, ts_pack(kTsInc, pe || own_end, min<int64_t>(ir, (1 << kTsRstBits) - 1), ik));
-        __builtin_amdgcn_wave_barrier();
-        if (on && !pe) {
-            const int64_t obase = pk;
-            if (nrst) {  // restart markers to the image's list in stream order (DRI images): a second
-                         // walk of the tile (now in L2), placing them at the known prefix
-                TileChunks t2;
-                t2.load(R, L, t0, lane);
-                int kk = 0, nr_done = 0;
-                int32_t gdummy = 0;
-                for (int r = 0; r < kTileBytes / 1024 && t0 + r * 1024 < L; ++r) {
-                    const int64_t a = t0 + r * 1024 + lane * 16;
-                    RstSink rs0{0, 0, nullptr, 0, 0};
-                    const ChunkIn c = t2.next(a, lane);
-                    const Ustf16 u = ustf16<false>(R, L, a, c.D, c.nx, c.prun, &gdummy, &rs0);
-                    const long long e = __any(u.end_at >= 0) ? wave_min_ll(u.end_at >= 0 ? (long long)u.end_at : LLONG_MAX)
-                                                             : LLONG_MAX;
-                    const bool before = u.end_at >= 0 ? u.end_at <= e : a < e;
-                    const int k = before ? u.kept : 0;
-                    const int incl = wave_incl_scan(k);
-                    const int nr = before ? rs0.n : 0;
-                    if (__any(nr)) {
-                        const int rincl = wave_incl_scan(nr);
-                        if (nr) {
-                            RstSink rs{0, obase + kk + (incl - k), rst + (int64_t)i * rst_cap, (int32_t)(pr + nr_done + rincl - nr),
-                                       (int32_t)min<int64_t>(rst_cap, INT32_MAX)};
-                            (void)ustf16<false>(R, L, a, c.D, c.nx, c.prun, &gdummy, &rs);
-                        }
-                        nr_done += __shfl(rincl, 63);
-                    }
-                    kk += __shfl(incl, 63);
-                    if (e != LLONG_MAX) break;
-                }
-            }
-            // copy out (as k_ustf_write)
-            const int64_t nout = kept;
-            uint8_t* dst = U + s.uoff + obase;
-            const int head = (int)min<int64_t>(nout, (16 - (obase & 15)) & 15);
-            const int nunit = (int)((nout - head) >> 4);
-            const int tail0 = head + nunit * 16;
-            if (lane < head) dst[lane] = sb[lane];
-            if (lane < nout - tail0) dst[tail0 + lane] = sb[tail0 + lane];
-            for (int u = lane; u < nunit; u += 64) {
-                const int b0 = head + 16 * u, shb = (b0 & 3) * 8;
-                const uint32_t* q = sbuf + (b0 >> 2);
-                uint32_t v[4];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) v[j] = (uint32_t)((((uint64_t)q[j + 1] << 32) | q[j]) >> shb);
-                *reinterpret_cast<uint4*>(dst + b0) = make_uint4(v[0], v[1], v[2], v[3]);
-            }
-            if (own_end || t == im.t_end - 1) {  // the data's end: the image's stream is complete
-                const int64_t ulen = obase + kept;
-                uint8_t* u = U + s.uoff;
-                for (int64_t p = ulen + lane; p < u_pad_end(ulen); p += 64) u[p] = 0xFF;
-                if (lane == 0) {
-                    s.ulen = ulen;
-                    s.nrst = (int32_t)ir;
-                    s.errpos = own_end && end_err ? ulen : INT64_MAX;
-                    const int64_t nsub = ulen > 0 ? (ulen + s.sub_bytes - 1) / s.sub_bytes : 1;
-                    s.nsub = s.mode == 3 ? s.nint : (s.kint > 0 ? s.nint * s.kint : (int32_t)nsub);
-                }
-            }
-        }
-        __builtin_amdgcn_wave_barrier();
-        t = tnx;
-        tc = tn;
-        im = imn;
-    }
-}
-
 // -------------------------------------------------------------------- entropy lanes
 // Step tables (icx_step.h), one set per image, built once per group from the parsed Huffman
 // tables; each workgroup below stages the format it decodes with into LDS.
@@ -802,16 +560,10 @@ __global__ __launch_bounds__(256) void k_step_tabs(int n, const Desc* __restrict
     StepSet& S = steps[i];
     for (int k = threadIdx.x; k < ScanTab::entries(); k += blockDim.x) S.scan.fill(h, k);
     for (int k = threadIdx.x; k < WriteTab::entries(); k += blockDim.x) S.write.fill(h, k);
-#ifdef ICX_EXP_GW8
-    for (int k = threadIdx.x; k < ScanTab11::entries(); k += blockDim.x) S.scan11.fill(h, k);
-#endif
     if (threadIdx.x == 0) {
         const Sel sel = make_sel(desc[i]);
         set_block_sel(S.scan, h, sel);
         set_block_sel(S.write, h, sel);
-#ifdef ICX_EXP_GW8
-        set_block_sel(S.scan11, h, sel);
-#endif
     }
 }
 
@@ -1030,10 +782,9 @@ __global__ __launch_bounds__(NL) void k_spec_write(int want, int n, const Desc* 
 #pragma unroll
     for (int q = 0; q < 8; ++q) slot[q] = make_int4(0, 0, 0, 0);
     for (int wg = blockIdx.x; wg < total; wg += gridDim.x) {
-        {  // uniform per workgroup; `want` (1 or 3) limits a launch to one mode. Tested before the
+        {  // uniform per workgroup; `want` (1 or 3) is the mode the launch takes. Tested before the
            // tables are staged: the guess-write path's DRI launch spans every image's workgroups.
-            const int m = spec[find_image(wpre, n, wg)].mode;
-            if ((m != 1 && m != 3) || (want && m != want)) continue;
+            if (spec[find_image(wpre, n, wg)].mode != want) continue;
         }
         const int i = wg_image_setup(wpre, n, wg, cur, T, steps);
         SpecImg& s = spec[i];
@@ -1108,10 +859,6 @@ __global__ __launch_bounds__(NL) void k_spec_write(int want, int n, const Desc* 
         // coefficient store and prefetch in flight -- on every DC code.
         asm volatile("" : "+v"(dc0), "+v"(dc1), "+v"(dc2));
         r.phase();  // the prelude above ran a lane-dependent number of lookups
-#ifdef ICX_EXP_CYC  // timing experiment only: per-wave loop cycles and iterations (printf)
-        const uint64_t cyc0 = clock64();
-        int it_w = 0;
-#endif
         // Wave-uniform loop: one lookup (one symbol or a pair) per active lane per iteration,
         // then the wave flushes the blocks its lanes completed together -- eight 128-byte blocks
         // per round, each lane moving one 16-byte chunk LDS -> HBM and zeroing it (coalesced
@@ -1120,9 +867,6 @@ __global__ __launch_bounds__(NL) void k_spec_write(int want, int n, const Desc* 
         // carry are scalar ANDs of single-compare ballots.
         uint64_t am = wave_ballot(act);
         while (am) {
-#ifdef ICX_EXP_CYC
-            ++it_w;
-#endif
             // The reader advances on every lane, active or not (an idle lane decodes harmless
             // garbage; its loads are clamped to U): keeping Reader updates out of divergent
             // branches stops the compiler from routing the in-flight chunk through loop-header
@@ -1187,25 +931,18 @@ __global__ __launch_bounds__(NL) void k_spec_write(int want, int n, const Desc* 
                         const int sl = (wave << 6) | src;
                         int4* sp = &slots[sl][0];
                         const int sq = q ^ (sl & 7);
-#ifndef ICX_EXP_NOSTORE  // timing experiment only: drop the coefficient stores
                         {  // streaming (evict-first) stores: the lanes' U lines stay in L2 (fetch 6.3x -> 2.2x U)
                             typedef int32_t i32x4 __attribute__((ext_vector_type(4)));
                             const int4 v = sp[sq];
                             const i32x4 vv = {v.x, v.y, v.z, v.w};
                             __builtin_nontemporal_store(vv, reinterpret_cast<i32x4*>(A) + (int64_t)bsrc * 8 + q);
                         }
-#endif
                         sp[sq] = make_int4(0, 0, 0, 0);
                     }
                 }
                 __builtin_amdgcn_wave_barrier();
             }
         }
-#ifdef ICX_EXP_CYC
-        if (lane == 0 && blockIdx.x % 64 == 0 && wg == (int)blockIdx.x && wave < 2)
-            printf("CYC wg %d wave %d iters %d per_iter %llu\n", wg, wave, it_w,
-                   (unsigned long long)((clock64() - cyc0) / max(1, it_w)));
-#endif
         if (bad) atomicOr(&s.err, kSpecSyntax);
         // stopped lanes scribbled in their slots: zero them for the next workgroup item
 #pragma unroll
@@ -1266,32 +1003,18 @@ __global__ __launch_bounds__(NL, ICX_GW_MINW) void k_gw_lane(int n, const Desc* 
                                                 RecState* __restrict__ rec, int lead, const int64_t* __restrict__ rst,
                                                 int64_t rst_cap) {
     __shared__ WriteTab T;
-#ifdef ICX_EXP_GW8  // timing experiment only: 64-byte int8 slots (values truncated), 11-bit lead tables
-    constexpr int kSQ = 4;  // 16-byte quarters per slot
-    using LeadTab = ScanTab11;
-    typedef int8_t Cell;
-#else
-    constexpr int kSQ = 8;
-    using LeadTab = ScanTab;
-    typedef int16_t Cell;
-#endif
     union SlotsOrScan {  // the lead loop's scan tables, then the write loop's slots
-        LeadTab st;
-        int4 slots[NL][kSQ];
+        ScanTab st;
+        int4 slots[NL][8];
     };
-    static_assert(sizeof(LeadTab) <= sizeof(int4) * NL * kSQ, "scan tables fit the slots' LDS");
+    static_assert(sizeof(ScanTab) <= sizeof(int4) * NL * 8, "scan tables fit the slots' LDS");
     __shared__ SlotsOrScan L;
     __shared__ uint8_t done_lane[NL / 64][64];  // per wave: lanes that completed a block, by rank
     int cur = -1;
     const int total = totals[2];
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     int4* slot = &L.slots[threadIdx.x][0];
-    Cell* sv = reinterpret_cast<Cell*>(slot);
-#ifdef ICX_EXP_GW8
-    auto slot_cell = [](int t, int n) { return n ^ ((t & 3) << 4); };
-#else
-    auto slot_cell = [](int t, int n) { return slot_elem(t, n); };
-#endif
+    int16_t* sv = reinterpret_cast<int16_t*>(slot);
     int4* A = reinterpret_cast<int4*>(ac);
     const int32_t scratch = (int32_t)pool_cap;  // (a lane the pool could not hold writes here)
     for (int wg = blockIdx.x; wg < total; wg += gridDim.x) {
@@ -1302,11 +1025,7 @@ __global__ __launch_bounds__(NL, ICX_GW_MINW) void k_gw_lane(int n, const Desc* 
         const int i = wg_image_setup(wpre, n, wg, cur, T, steps);
         SpecImg& s = spec[i];
         __syncthreads();  // (the previous item's slots are done with)
-#ifdef ICX_EXP_GW8
-        stage_tab(L.st, steps[i].scan11);
-#else
         stage_tab(L.st, steps[i].scan);
-#endif
         __syncthreads();
         const int64_t j = (int64_t)(wg - wpre[i]) * NL + threadIdx.x;
         const Sel S = make_sel(desc[i]);
@@ -1334,7 +1053,7 @@ __global__ __launch_bounds__(NL, ICX_GW_MINW) void k_gw_lane(int n, const Desc* 
         const uint64_t g0 = pack_state(s0 + r.used, b, 0);
         __syncthreads();  // every wave is done with the scan tables: the slots take their LDS
 #pragma unroll
-        for (int q = 0; q < kSQ; ++q) slot[q] = make_int4(0, 0, 0, 0);
+        for (int q = 0; q < 8; ++q) slot[q] = make_int4(0, 0, 0, 0);
         __builtin_amdgcn_wave_barrier();
         r.phase();  // the lead ran a lane-dependent number of lookups
         ErrBounds eb;
@@ -1431,8 +1150,8 @@ __global__ __launch_bounds__(NL, ICX_GW_MINW) void k_gw_lane(int n, const Desc* 
             if (owndc && !dc_in) dcv[addr] = pc;  // lane-local DC outside int16 (rare)
             // (v1 is 0 for EOB and invalid codes; an invalid DC code is a decode error, so that
             // block is a discarded speculative one or the image fails)
-            sv[slot_cell(threadIdx.x, o.n2)] = (Cell)(o.w2 ? o.v2 : 0);
-            sv[slot_cell(threadIdx.x, o.n1)] = (Cell)(bs ? cell : o.v1);
+            sv[slot_elem(threadIdx.x, o.n2)] = (int16_t)(o.w2 ? o.v2 : 0);
+            sv[slot_elem(threadIdx.x, o.n1)] = (int16_t)(bs ? cell : o.v1);
             const uint64_t m = wave_ballot(z == 0) & lm;
             const bool done = lane_in(m);
             k = add_lane_bit(k, m);  // k += done
@@ -1450,21 +1169,18 @@ __global__ __launch_bounds__(NL, ICX_GW_MINW) void k_gw_lane(int n, const Desc* 
                 }
                 __builtin_amdgcn_wave_barrier();
                 const int cnt = __popcll(m);
-                constexpr int kPer = 64 / kSQ;  // blocks per flush round
-                for (int k0 = 0; k0 < cnt; k0 += kPer) {
-                    const int e = k0 + lane / kSQ, q = lane % kSQ;
+                for (int k0 = 0; k0 < cnt; k0 += 8) {
+                    const int e = k0 + (lane >> 3), q = lane & 7;
                     const int src = done_lane[wave][min(e, cnt - 1)];
                     const int bsrc = __shfl(addr, src);
                     if (e < cnt) {
                         const int sl = (wave << 6) | src;
                         int4* sp = &L.slots[sl][0];
-                        const int sq = q ^ (sl & (kSQ - 1));
-#ifndef ICX_EXP_NOSTORE  // timing experiment only: drop the coefficient stores
+                        const int sq = q ^ (sl & 7);
                         typedef int32_t i32x4 __attribute__((ext_vector_type(4)));
                         const int4 v = sp[sq];
                         const i32x4 vv = {v.x, v.y, v.z, v.w};
-                        __builtin_nontemporal_store(vv, reinterpret_cast<i32x4*>(A) + (int64_t)bsrc * kSQ + q);
-#endif
+                        __builtin_nontemporal_store(vv, reinterpret_cast<i32x4*>(A) + (int64_t)bsrc * 8 + q);
                         sp[sq] = make_int4(0, 0, 0, 0);
                     }
                 }
@@ -1988,7 +1704,6 @@ void launch_spec_round(const GroupWs& ws, int n, const uint8_t* d_data, const ui
     // ICX_GW=0 / 1 forces one (read per launch: tests run both paths in one process).
     const char* gw_env = std::getenv("ICX_GW");
     const int gw = gw_env ? (std::atoi(gw_env) != 0) : ((int64_t)ws.max_w * ws.max_h > kGwMinPixels ? 1 : 0);
-    const bool big = !gw && (std::getenv("ICX_BIG_WG") ? std::atoi(std::getenv("ICX_BIG_WG")) != 0 : true);
     // restart intervals on the guess-write path (ICX_DRI_GW: 0 never, 1 from kSubBytesSmall bytes per
     // interval; read per launch: tests run both paths)
     const char* dri_env = std::getenv("ICX_DRI_GW");
@@ -2001,22 +1716,12 @@ void launch_spec_round(const GroupWs& ws, int n, const uint8_t* d_data, const ui
         (void)hipEventRecord(ws.ev_defer, st);
         if (round == 0)  // (an image's tables serve every round)
             hipLaunchKernelGGL(k_step_tabs, dim3(n), dim3(256), 0, st, n, ws.desc, ws.steps);
-        // ICX_USTF1=1: the one-pass unstuff (k_ustf_one, its tile states in the tile records' memory:
-        // 8 bytes per tile plus the ticket, of 24 per tile); otherwise count, scan, write
-        const char* one_env = std::getenv("ICX_USTF1");
-        if (one_env && std::atoi(one_env) != 0) {
-            uint64_t* ts = reinterpret_cast<uint64_t*>(ws.tiles);
-            (void)hipMemsetAsync(ts, 0, sizeof(uint64_t) * (size_t)(ws.tiles_cap + 2), st);
-            hipLaunchKernelGGL(k_ustf_one, dim3(g), dim3(256), 0, st, n, d_data, d_off, ws.desc, ws.spec, ws.tilepre, ws.totals,
-                               ts, ws.U, ws.rst, ws.rst_cap);
-        } else {
-            hipLaunchKernelGGL(k_ustf_count, dim3(g), dim3(256), 0, st, n, d_data, d_off, ws.desc, ws.spec, ws.tilepre,
-                               ws.totals, ws.tiles);
-            hipLaunchKernelGGL(k_ustf_scan, dim3(n), dim3(256), 0, st, n, ws.spec, ws.tiles, ws.tile_obase, ws.tile_rbase,
-                               ws.U);
-            hipLaunchKernelGGL(k_ustf_write, dim3(g), dim3(256), 0, st, n, d_data, d_off, ws.desc, ws.spec, ws.tilepre,
-                               ws.totals, ws.tiles, ws.tile_obase, ws.tile_rbase, ws.U, ws.rst, ws.rst_cap);
-        }
+        hipLaunchKernelGGL(k_ustf_count, dim3(g), dim3(256), 0, st, n, d_data, d_off, ws.desc, ws.spec, ws.tilepre,
+                           ws.totals, ws.tiles);
+        hipLaunchKernelGGL(k_ustf_scan, dim3(n), dim3(256), 0, st, n, ws.spec, ws.tiles, ws.tile_obase, ws.tile_rbase,
+                           ws.U);
+        hipLaunchKernelGGL(k_ustf_write, dim3(g), dim3(256), 0, st, n, d_data, d_off, ws.desc, ws.spec, ws.tilepre,
+                           ws.totals, ws.tiles, ws.tile_obase, ws.tile_rbase, ws.U, ws.rst, ws.rst_cap);
         E(kStUnstuff);
         // Guess-write path (default; ICX_GW=0: guess, count, write)
         if (gw) {
@@ -2050,40 +1755,28 @@ void launch_spec_round(const GroupWs& ws, int n, const uint8_t* d_data, const ui
         } else {
         B(kStEntropy);
         // guess / count / write: 512-lane workgroups (tables amortised over more lanes), which each
-        // image's lanes fill (k_spec_plan); ICX_BIG_WG=0 selects 256-lane ones (experiments)
-        if (big) {
-            hipLaunchKernelGGL(k_spec_guess<kWriteLanesBig>, dim3(g), dim3(kWriteLanesBig), 0, st, n, ws.desc, ws.spec, ws.wg2pre,
-                               ws.totals, 2, ws.steps, ws.U, ws.X, ws.rec, ws.nrec, ws.guess_cnt, lead);
-            hipLaunchKernelGGL(k_spec_count<kWriteLanesBig>, dim3(g), dim3(kWriteLanesBig), 0, st, n, ws.desc, ws.spec, ws.wg2pre,
-                               ws.totals, 2, ws.steps, ws.U, ws.X, ws.Y, ws.rec, ws.nrec, ws.guess_cnt, ws.sub, ws.repair);
-        } else {
-            hipLaunchKernelGGL(k_spec_guess<kLanes>, dim3(g), dim3(kLanes), 0, st, n, ws.desc, ws.spec, ws.wgpre,
-                               ws.totals, 1, ws.steps, ws.U, ws.X, ws.rec, ws.nrec, ws.guess_cnt, lead);
-            hipLaunchKernelGGL(k_spec_count<kLanes>, dim3(g), dim3(kLanes), 0, st, n, ws.desc, ws.spec, ws.wgpre,
-                               ws.totals, 1, ws.steps, ws.U, ws.X, ws.Y, ws.rec, ws.nrec, ws.guess_cnt, ws.sub, ws.repair);
-        }
+        // image's lanes fill (k_spec_plan)
+        hipLaunchKernelGGL(k_spec_guess<kWriteLanesBig>, dim3(g), dim3(kWriteLanesBig), 0, st, n, ws.desc, ws.spec, ws.wg2pre,
+                           ws.totals, 2, ws.steps, ws.U, ws.X, ws.rec, ws.nrec, ws.guess_cnt, lead);
+        hipLaunchKernelGGL(k_spec_count<kWriteLanesBig>, dim3(g), dim3(kWriteLanesBig), 0, st, n, ws.desc, ws.spec, ws.wg2pre,
+                           ws.totals, 2, ws.steps, ws.U, ws.X, ws.Y, ws.rec, ws.nrec, ws.guess_cnt, ws.sub, ws.repair);
         hipLaunchKernelGGL(k_spec_repair, dim3(n), dim3(64), 0, st, n, ws.desc, ws.spec, ws.steps, ws.U, ws.X, ws.Y,
                            ws.rec, ws.nrec, ws.guess_cnt, ws.sub, ws.repair);
         hipLaunchKernelGGL(k_spec_scan, dim3(n), dim3(256), 0, st, n, ws.spec, ws.sub, ws.ent);
         E(kStEntropy);
         B(kStWrite);
-        if (big) {
-            // subsequences: 512-lane workgroups; restart intervals (DRI, typically one per MCU row, so
-            // a few hundred long lanes per image): 256-lane workgroups, which a 512-lane numbering
-            // would leave half idle
-            hipLaunchKernelGGL(k_spec_write<kWriteLanesBig>, dim3(g), dim3(kWriteLanesBig), 0, st, 1, n, ws.desc, ws.spec,
-                               ws.wg2pre, ws.totals, ws.steps, ws.U, ws.X, ws.ent, ws.ac, ws.dc, ws.rst, ws.rst_cap);
-        } else {
-            hipLaunchKernelGGL(k_spec_write<kLanes>, dim3(g), dim3(kLanes), 0, st, 0, n, ws.desc, ws.spec, ws.wgpre,
-                               ws.totals, ws.steps, ws.U, ws.X, ws.ent, ws.ac, ws.dc, ws.rst, ws.rst_cap);
-        }
+        // subsequences: 512-lane workgroups; restart intervals (DRI, typically one per MCU row, so
+        // a few hundred long lanes per image): 256-lane workgroups in the round's tail, which a
+        // 512-lane numbering would leave half idle
+        hipLaunchKernelGGL(k_spec_write<kWriteLanesBig>, dim3(g), dim3(kWriteLanesBig), 0, st, 1, n, ws.desc, ws.spec,
+                           ws.wg2pre, ws.totals, ws.steps, ws.U, ws.X, ws.ent, ws.ac, ws.dc, ws.rst, ws.rst_cap);
         E(kStWrite);
         }
     }
     if (piece == kRoundHead) return;
     // the round's tail: restart intervals (DRI) -- one write lane per interval, 256-lane workgroups
-    // (the non-big three-pass launch above took them) -- and the round's end
-    if ((gw || big) && piece != kRoundTailNoDri) {
+    // -- and the round's end
+    if (piece != kRoundTailNoDri) {
         B(kStWrite);  // (the write stage's second bracket: restart-interval lanes)
         // (kRoundTailGw: only fallbacks of guess-write DRI images, rare; 2048 empty workgroups of
         // 48 KB of LDS would cost as much as the CHK instance's did)

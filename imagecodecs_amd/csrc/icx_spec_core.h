@@ -308,9 +308,6 @@ ICX_HD bool lane_in(uint64_t m) {
 #endif
 }
 
-#ifndef ICX_RD_SUBB
-#define ICX_RD_SUBB 1
-#endif
 // MSB-first reader over U (padded as above).
 // Latency hiding at the WAVE level: a wave's vmcnt counts every lane's loads in issue order, so a
 // lane cannot wait for "its own" older load while a neighbour's newer one is in flight. Loads
@@ -357,7 +354,7 @@ struct Reader {
         const uint64_t w = (a0 >> 32) << ((32 - nb) & 63);
         buf |= need ? w : 0ull;
         nb += need ? 32 : 0;
-#if defined(__HIP_DEVICE_COMPILE__) && ICX_RD_SUBB
+#if defined(__HIP_DEVICE_COMPILE__)
         {  // na -= need: the compare's lane mask as the borrow (one VALU, not a select and a subtract)
             int32_t r;
             uint64_t c;

@@ -3,7 +3,7 @@
 # imagecodecs_amd/), one rocprofv3 --kernel-trace --stats pass of a short bench on ONE pipeline
 # (ICX_PIPES=1, so each kernel runs alone) and a per-kernel summary. Optional PROBE=1 first runs
 # tools/probe/valu_issue (the VALU issue-rate calibration) plainly and under one --pmc pass.
-#   LABEL=r06a LIBS="lib/libicx.so xlib/libicx_nostore.so" BENCH_ARGS="--images 256" tools/gpu_kstats.sh
+#   LABEL=r06a LIBS="lib/libicx.so xlib/libicx_gw2.so" BENCH_ARGS="--images 256" tools/gpu_kstats.sh
 # Output: gpurun_out/<LABEL>_<lib>/ (trace), gpurun_out/<LABEL>_kstats.txt (summaries).
 set -o pipefail
 R="$GRAFT_REPO_ROOT"; [ -n "$R" ] || R=$(pwd)
