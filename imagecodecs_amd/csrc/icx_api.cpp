@@ -17,6 +17,7 @@
 
 #include "../../include/icx.h"
 #include "icx_internal.h"
+#include "icx_mem.h"
 #include "icx_step.h"
 
 using namespace icx;
@@ -29,9 +30,6 @@ struct icx_ctx {
     std::vector<uint8_t> nj_image;
     int nj_w = 0, nj_h = 0, nj_color = 0, nj_size = 0;
     icx_batch* single = nullptr;  // cached workspace for one-image calls
-    // staging for one-image calls
-    uint8_t* d_in = nullptr;
-    size_t d_in_cap = 0;
     ExrWs* exr = nullptr;  // grow-only EXR read buffers (icx_exr.hip)
 };
 
@@ -49,13 +47,13 @@ struct icx_batch {
     int max_images = 0;
     int pipes = 1;
     GroupWs ws[kMaxPipes];
+    Blocks mem[kMaxPipes];            // the device and pinned memory ws[p] points into
     hipStream_t pst[kMaxPipes] = {};  // pst[0] unused: pipe 0 runs on the caller's stream
     hipEvent_t fork = nullptr, join[kMaxPipes] = {};
     std::vector<hipEvent_t> front_done;  // per group of a call: its front half has run
     int min_groups = 1;                  // a call is cut into at least this many groups
     bool stagger = false;                // group g's front waits for group g-1's front (ICX_STAGGER=1; measured slower)
-    uint8_t* d_hin = nullptr;  // staging for icx_jpeg_batch_decode_host
-    size_t d_hin_cap = 0;
+    Buf<uint8_t> d_hin;  // staging for icx_jpeg_batch_decode_host
     hipEvent_t done = nullptr;      // recorded after the last decode call's work (path_stats waits on it)
     bool decoded = false;
     std::unique_ptr<EventHook> hook;
@@ -74,6 +72,15 @@ static thread_local char g_msg[512];
             if (ctx) (ctx)->err = g_msg;                                                    \
             return ret;                                                                     \
         }                                                                                   \
+    } while (0)
+// The same for an allocation through icx_mem.h (`ok` false: HIP's error is still pending).
+#define ICX_ALLOC(ctx, ok, ret)                                                                              \
+    do {                                                                                                     \
+        if (!(ok)) {                                                                                         \
+            std::snprintf(g_msg, sizeof g_msg, "%s failed: %s", #ok, hipGetErrorString(hipGetLastError())); \
+            if (ctx) (ctx)->err = g_msg;                                                                     \
+            return ret;                                                                                      \
+        }                                                                                                    \
     } while (0)
 
 // Brackets every pipeline stage with HIP events on the launch stream, and with a roctx range on
@@ -110,6 +117,16 @@ struct EventHook : StageHook {
         (void)roctxRangePop();
         for (auto it = recs.rbegin(); it != recs.rend(); ++it)
             if (it->s == s) { (void)hipEventRecord(it->b, st); return; }
+    }
+    // ms per stage over the records (waits for each; a failed wait or read is dropped, and its
+    // error not left for the caller's next check)
+    void sum(float acc[kStCount]) const {
+        std::fill(acc, acc + kStCount, 0.f);
+        for (auto& r : recs) {
+            float t = 0;
+            if (hipEventSynchronize(r.b) == hipSuccess && hipEventElapsedTime(&t, r.a, r.b) == hipSuccess) acc[r.s] += t;
+            else (void)hipGetLastError();
+        }
     }
     ~EventHook() override {
         for (auto e : pool) (void)hipEventDestroy(e);
@@ -152,7 +169,6 @@ void icx_destroy(icx_ctx* c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
     if (c->single) icx_batch_destroy(c->single);
-    if (c->d_in) (void)hipFree(c->d_in);
     if (c->exr) exr_ws_destroy(c->exr);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
@@ -194,38 +210,28 @@ static int64_t ws_per_slot(GroupWs& ws, int max_w, int max_h) {
     const int64_t tiles_per_slot = ws.ucap / kTileBytes + 2;
     const int64_t lanes_per_slot = ((ws.ucap + kSubBytesSmall - 1) / kSubBytesSmall + kLanes - 1) / kLanes * kLanes + kLanes;
     // coefficient pool: kPoolPerSlot x coef_cap blocks per slot (int16 block + int32 DC escape + map entry)
-    // (the generic upsample's ping-pong planes, 6 x tmp_cap, live in the coefficient pool: ws_alloc_all)
+    // (the generic upsample's ping-pong planes, 6 x tmp_cap, live in the coefficient pool: ws_alloc)
+    // per tile: tiles, tile_obase. (tile_rbase, another int32_t per tile, has never been counted:
+    // left so, because the automatic group size follows from this value.)
+    constexpr int64_t per_tile = sizeof(TileRec) + sizeof(int32_t);
+    static_assert(per_tile == 28, "ws_per_slot must not drift");
+    // per lane: X, Y, sub, ent, nrec, guess_cnt, rec, gw, crec, clist
+    constexpr int64_t per_lane = 2 * sizeof(uint64_t) + sizeof(SubRec) + sizeof(LaneEntry) + sizeof(int32_t) +
+                                 4 * sizeof(int32_t) + sizeof(RecState) * kRec + sizeof(GwOut) + sizeof(GcRec) + sizeof(int2);
+    static_assert(per_lane == 8 + 8 + 20 + 24 + 4 + 16 + 24 * kRec + 40 + 32 + 8, "ws_per_slot must not drift");
     return ws.coef_cap * kPoolPerSlotX4 / 4 * (64 * 2 + 4 + 8) + ws.plane_cap + (int64_t)sizeof(Desc) + ws.ucap +
-           (int64_t)sizeof(StepSet) +
-           tiles_per_slot * 28 + ws.rst_cap * 8 +
-           lanes_per_slot * (8 + 8 + 20 + 24 + 4 + 16 + (int64_t)sizeof(RecState) * kRec + (int64_t)sizeof(GwOut) +
-                             (int64_t)sizeof(GcRec) + 8) + kMaxRepair * 4;
+           (int64_t)sizeof(StepSet) + tiles_per_slot * per_tile + ws.rst_cap * 8 + lanes_per_slot * per_lane +
+           kMaxRepair * 4;
 }
 
-static void ws_free(GroupWs& ws) {
-    if (ws.tmp_own && ws.tmp) (void)hipFree(ws.tmp);
-    for (void* p : {(void*)ws.desc, (void*)ws.ac, (void*)ws.dc, (void*)ws.planes, (void*)ws.spec,
-                    (void*)ws.tilepre, (void*)ws.wgpre, (void*)ws.wg2pre, (void*)ws.totals, (void*)ws.tiles,
-                    (void*)ws.tile_obase, (void*)ws.U, (void*)ws.X, (void*)ws.sub, (void*)ws.rst, (void*)ws.tile_rbase,
-                    (void*)ws.ent, (void*)ws.stats, (void*)ws.Y, (void*)ws.rec, (void*)ws.nrec, (void*)ws.guess_cnt,
-                    (void*)ws.repair, (void*)ws.steps, (void*)ws.map, (void*)ws.chunk_next, (void*)ws.pool_next,
-                    (void*)ws.gw, (void*)ws.crec, (void*)ws.clist})
-        if (p) (void)hipFree(p);
-    if (ws.h_defer) (void)hipHostFree(ws.h_defer);
-    if (ws.h_layout) (void)hipHostFree(ws.h_layout);
+static void ws_free(GroupWs& ws, Blocks& mem) {
+    mem.release();
     if (ws.ev_defer) (void)hipEventDestroy(ws.ev_defer);
     ws = GroupWs{};
 }
 
-static bool ws_alloc_all(icx_ctx* ctx, GroupWs& ws, int group, int max_w, int max_h);
-// All or nothing: a failure part-way frees this workspace's buffers before returning.
-static bool ws_alloc(icx_ctx* ctx, GroupWs& ws, int group, int max_w, int max_h) {
-    if (ws_alloc_all(ctx, ws, group, max_w, max_h)) return true;
-    ws_free(ws);
-    return false;
-}
-
-static bool ws_alloc_all(icx_ctx* ctx, GroupWs& ws, int group, int max_w, int max_h) {
+// A failure part-way leaves what was allocated to `mem` (icx_batch_destroy frees it).
+static bool ws_alloc(icx_ctx* ctx, GroupWs& ws, Blocks& mem, int group, int max_w, int max_h) {
     (void)ws_per_slot(ws, max_w, max_h);
     const int64_t tiles_per_slot = ws.ucap / kTileBytes + 2;
     const int64_t lanes_per_slot = ((ws.ucap + kSubBytesSmall - 1) / kSubBytesSmall + kLanes - 1) / kLanes * kLanes + kLanes;
@@ -234,7 +240,7 @@ static bool ws_alloc_all(icx_ctx* ctx, GroupWs& ws, int group, int max_w, int ma
     // even a one-image group takes a 3 B/px scan (k_spec_plan sends images past the pool to
     // the sequential kernel)
     ws.upool = (int64_t)(group + 2) * ws.ucap;
-    ICX_HIP(ctx, hipMalloc(&ws.desc, sizeof(Desc) * group), false);
+    ICX_ALLOC(ctx, mem.alloc(ws.desc, sizeof(Desc) * group), false);
     // the coefficient pool (k_spec_plan places each image in it; the guess-write lanes' overflow
     // chunks and count blocks take its tail), + kGwChunk scratch blocks past pool_cap. The static
     // regions take 1.1 x each image's blocks; the tail, 2.5 (G + 2) - 1.1 G > 1.4 G image-blocks,
@@ -242,12 +248,12 @@ static bool ws_alloc_all(icx_ctx* ctx, GroupWs& ws, int group, int max_w, int ma
     // worth of bytes stores nearly all its blocks there) plus the count lanes' copies and the
     // chunks' rounding, so a conforming group never runs out of it.
     ws.pool_cap = (int64_t)(group + 2) * ws.coef_cap * kPoolPerSlotX4 / 4;
-    ICX_HIP(ctx, hipMalloc(&ws.ac, (size_t)(ws.pool_cap + kGwChunk) * 64 * 2), false);
-    ICX_HIP(ctx, hipMalloc(&ws.dc, (size_t)(ws.pool_cap + kGwChunk) * 4), false);
-    ICX_HIP(ctx, hipMalloc(&ws.map, (size_t)ws.pool_cap * sizeof(uint2)), false);
-    ICX_HIP(ctx, hipMalloc(&ws.chunk_next, (size_t)(ws.pool_cap / kGwChunk + 2) * 4), false);
-    ICX_HIP(ctx, hipMalloc(&ws.pool_next, sizeof(unsigned long long)), false);
-    ICX_HIP(ctx, hipMalloc(&ws.planes, (size_t)ws.plane_cap * group), false);
+    ICX_ALLOC(ctx, mem.alloc(ws.ac, (size_t)(ws.pool_cap + kGwChunk) * 64 * 2), false);
+    ICX_ALLOC(ctx, mem.alloc(ws.dc, (size_t)(ws.pool_cap + kGwChunk) * 4), false);
+    ICX_ALLOC(ctx, mem.alloc(ws.map, (size_t)ws.pool_cap * sizeof(uint2)), false);
+    ICX_ALLOC(ctx, mem.alloc(ws.chunk_next, (size_t)(ws.pool_cap / kGwChunk + 2) * 4), false);
+    ICX_ALLOC(ctx, mem.alloc(ws.pool_next, sizeof(unsigned long long)), false);
+    ICX_ALLOC(ctx, mem.alloc(ws.planes, (size_t)ws.plane_cap * group), false);
     // The generic upsample's ping-pong planes (exotic samplings only: k_upsample, k_convert) share
     // the coefficient pool's memory: launch_decode_back runs them after every kernel that reads the
     // group's coefficients (the pool holds >= 15 x the slot's MCU-padded pixels in bytes, the planes
@@ -256,38 +262,37 @@ static bool ws_alloc_all(icx_ctx* ctx, GroupWs& ws, int group, int max_w, int ma
     if ((int64_t)(ws.pool_cap + kGwChunk) * 64 * 2 >= ws.tmp_cap * 6 * group) {
         ws.tmp = reinterpret_cast<uint8_t*>(ws.ac);
     } else {
-        ICX_HIP(ctx, hipMalloc(&ws.tmp, (size_t)ws.tmp_cap * 6 * group), false);
-        ws.tmp_own = true;
+        ICX_ALLOC(ctx, mem.alloc(ws.tmp, (size_t)ws.tmp_cap * 6 * group), false);
     }
     ws.tiles_cap = tiles_per_slot * (group + 2);
     ws.lanes_cap = lanes_per_slot * (group + 2);
-    ICX_HIP(ctx, hipMalloc(&ws.spec, sizeof(SpecImg) * group), false);
-    ICX_HIP(ctx, hipMalloc(&ws.tilepre, sizeof(int32_t) * (group + 1)), false);
-    ICX_HIP(ctx, hipMalloc(&ws.wgpre, sizeof(int32_t) * (group + 1)), false);
-    ICX_HIP(ctx, hipMalloc(&ws.wg2pre, sizeof(int32_t) * (group + 1)), false);
-    ICX_HIP(ctx, hipMalloc(&ws.totals, sizeof(int32_t) * 4), false);
-    ICX_HIP(ctx, hipMalloc(&ws.tiles, sizeof(TileRec) * ws.tiles_cap), false);
-    ICX_HIP(ctx, hipMalloc(&ws.tile_obase, sizeof(int32_t) * ws.tiles_cap), false);
+    ICX_ALLOC(ctx, mem.alloc(ws.spec, sizeof(SpecImg) * group), false);
+    ICX_ALLOC(ctx, mem.alloc(ws.tilepre, sizeof(int32_t) * (group + 1)), false);
+    ICX_ALLOC(ctx, mem.alloc(ws.wgpre, sizeof(int32_t) * (group + 1)), false);
+    ICX_ALLOC(ctx, mem.alloc(ws.wg2pre, sizeof(int32_t) * (group + 1)), false);
+    ICX_ALLOC(ctx, mem.alloc(ws.totals, sizeof(int32_t) * 4), false);
+    ICX_ALLOC(ctx, mem.alloc(ws.tiles, sizeof(TileRec) * ws.tiles_cap), false);
+    ICX_ALLOC(ctx, mem.alloc(ws.tile_obase, sizeof(int32_t) * ws.tiles_cap), false);
     // + slack: the entropy readers load whole 16-byte chunks (icx_spec_core.h Reader)
-    ICX_HIP(ctx, hipMalloc(&ws.U, (size_t)ws.upool + 256), false);
-    ICX_HIP(ctx, hipMalloc(&ws.X, sizeof(uint64_t) * ws.lanes_cap), false);
-    ICX_HIP(ctx, hipMalloc(&ws.sub, sizeof(SubRec) * ws.lanes_cap), false);
-    ICX_HIP(ctx, hipMalloc(&ws.rst, sizeof(int64_t) * ws.rst_cap * group), false);
-    ICX_HIP(ctx, hipMalloc(&ws.tile_rbase, sizeof(int32_t) * ws.tiles_cap), false);
-    ICX_HIP(ctx, hipMalloc(&ws.ent, sizeof(LaneEntry) * ws.lanes_cap), false);
-    ICX_HIP(ctx, hipMalloc(&ws.stats, sizeof(int32_t) * 4), false);
-    ICX_HIP(ctx, hipMalloc(&ws.Y, sizeof(uint64_t) * ws.lanes_cap), false);
-    ICX_HIP(ctx, hipMalloc(&ws.rec, sizeof(RecState) * kRec * ws.lanes_cap), false);
-    ICX_HIP(ctx, hipMalloc(&ws.nrec, sizeof(int32_t) * ws.lanes_cap), false);
-    ICX_HIP(ctx, hipMalloc(&ws.guess_cnt, sizeof(int32_t) * 4 * ws.lanes_cap), false);
-    ICX_HIP(ctx, hipMalloc(&ws.repair, sizeof(int32_t) * kMaxRepair * group), false);
-    ICX_HIP(ctx, hipMalloc(&ws.steps, sizeof(StepSet) * group), false);
-    ICX_HIP(ctx, hipMalloc(&ws.gw, sizeof(GwOut) * ws.lanes_cap), false);
-    ICX_HIP(ctx, hipMalloc(&ws.crec, sizeof(GcRec) * ws.lanes_cap), false);
-    ICX_HIP(ctx, hipMalloc(&ws.clist, sizeof(int2) * ws.lanes_cap), false);
-    ICX_HIP(ctx, hipHostMalloc(&ws.h_defer, 3 * sizeof(int32_t), hipHostMallocDefault), false);
+    ICX_ALLOC(ctx, mem.alloc(ws.U, (size_t)ws.upool + 256), false);
+    ICX_ALLOC(ctx, mem.alloc(ws.X, sizeof(uint64_t) * ws.lanes_cap), false);
+    ICX_ALLOC(ctx, mem.alloc(ws.sub, sizeof(SubRec) * ws.lanes_cap), false);
+    ICX_ALLOC(ctx, mem.alloc(ws.rst, sizeof(int64_t) * ws.rst_cap * group), false);
+    ICX_ALLOC(ctx, mem.alloc(ws.tile_rbase, sizeof(int32_t) * ws.tiles_cap), false);
+    ICX_ALLOC(ctx, mem.alloc(ws.ent, sizeof(LaneEntry) * ws.lanes_cap), false);
+    ICX_ALLOC(ctx, mem.alloc(ws.stats, sizeof(int32_t) * 4), false);
+    ICX_ALLOC(ctx, mem.alloc(ws.Y, sizeof(uint64_t) * ws.lanes_cap), false);
+    ICX_ALLOC(ctx, mem.alloc(ws.rec, sizeof(RecState) * kRec * ws.lanes_cap), false);
+    ICX_ALLOC(ctx, mem.alloc(ws.nrec, sizeof(int32_t) * ws.lanes_cap), false);
+    ICX_ALLOC(ctx, mem.alloc(ws.guess_cnt, sizeof(int32_t) * 4 * ws.lanes_cap), false);
+    ICX_ALLOC(ctx, mem.alloc(ws.repair, sizeof(int32_t) * kMaxRepair * group), false);
+    ICX_ALLOC(ctx, mem.alloc(ws.steps, sizeof(StepSet) * group), false);
+    ICX_ALLOC(ctx, mem.alloc(ws.gw, sizeof(GwOut) * ws.lanes_cap), false);
+    ICX_ALLOC(ctx, mem.alloc(ws.crec, sizeof(GcRec) * ws.lanes_cap), false);
+    ICX_ALLOC(ctx, mem.alloc(ws.clist, sizeof(int2) * ws.lanes_cap), false);
+    ICX_ALLOC(ctx, mem.alloc(ws.h_defer, 3 * sizeof(int32_t), true), false);
     ws.h_defer[0] = ws.h_defer[1] = ws.h_defer[2] = 0;
-    ICX_HIP(ctx, hipHostMalloc(&ws.h_layout, sizeof(int32_t), hipHostMallocDefault), false);
+    ICX_ALLOC(ctx, mem.alloc(ws.h_layout, sizeof(int32_t), true), false);
     *ws.h_layout = 1;
     ICX_HIP(ctx, hipEventCreateWithFlags(&ws.ev_defer, hipEventDisableTiming), false);
     return true;
@@ -327,7 +332,7 @@ icx_batch* icx_batch_create(icx_ctx* ctx, int max_images, int max_w, int max_h, 
     for (int p = 0; p < pipes; ++p) {
         // `group` images in flight over all pipes: each workspace holds its share
         const int slots = (group + pipes - 1) / pipes;
-        if (!ws_alloc(ctx, b->ws[p], slots, max_w, max_h)) return nullptr;
+        if (!ws_alloc(ctx, b->ws[p], b->mem[p], slots, max_w, max_h)) return nullptr;
         if (p > 0) ICX_HIP(ctx, hipStreamCreateWithFlags(&b->pst[p], hipStreamNonBlocking), nullptr);
         ICX_HIP(ctx, hipEventCreateWithFlags(&b->join[p], hipEventDisableTiming), nullptr);
     }
@@ -341,14 +346,13 @@ void icx_batch_destroy(icx_batch* b) {
     if (!b) return;
     (void)hipSetDevice(b->ctx->device);
     for (int p = 0; p < kMaxPipes; ++p) {
-        ws_free(b->ws[p]);
+        ws_free(b->ws[p], b->mem[p]);
         if (b->pst[p]) (void)hipStreamDestroy(b->pst[p]);
         if (b->join[p]) (void)hipEventDestroy(b->join[p]);
     }
     if (b->fork) (void)hipEventDestroy(b->fork);
     if (b->done) (void)hipEventDestroy(b->done);
     for (auto e : b->front_done) (void)hipEventDestroy(e);
-    if (b->d_hin) (void)hipFree(b->d_hin);
     delete b;
 }
 
@@ -488,12 +492,8 @@ int icx_batch_group(const icx_batch* b) { return b ? b->ws[0].slots : 0; }
 
 int icx_batch_stage_times(const icx_batch* b, const char** names, float* ms, int cap) {
     if (!b) return 0;
-    float acc[kStCount] = {0};
-    for (auto& r : b->hook->recs) {
-        float t = 0;
-        if (hipEventSynchronize(r.b) == hipSuccess && hipEventElapsedTime(&t, r.a, r.b) == hipSuccess) acc[r.s] += t;
-        else (void)hipGetLastError();  // (not left for the caller's next check)
-    }
+    float acc[kStCount];
+    b->hook->sum(acc);
     int k = 0;
     for (int s = 0; s < kStCount && k < cap; ++s, ++k) {
         if (names) names[k] = kStageNames[s];
@@ -513,14 +513,8 @@ int icx_jpeg_batch_decode_host(icx_batch* b, int n, const uint8_t* const* jpegs,
     for (int i = 0; i < n; ++i) { off[i] = total; sz[i] = sizes[i]; total += (sizes[i] + 15) & ~uint64_t(15); }
     const size_t meta = (size_t)n * (8 + 8 + 4 + 12);
     const size_t need = total + meta + (size_t)n * out_stride + 256;
-    if (need > b->d_hin_cap) {
-        if (b->d_hin) (void)hipFree(b->d_hin);
-        b->d_hin = nullptr;
-        b->d_hin_cap = 0;
-        ICX_HIP(ctx, hipMalloc(&b->d_hin, need), ICX_OUT_OF_MEM);
-        b->d_hin_cap = need;
-    }
-    uint8_t* base = b->d_hin;
+    ICX_ALLOC(ctx, b->d_hin.reserve(need), ICX_OUT_OF_MEM);
+    uint8_t* base = b->d_hin.p;
     uint8_t* d_data = base;
     uint64_t* d_off = reinterpret_cast<uint64_t*>(base + ((total + 15) & ~uint64_t(15)));
     uint64_t* d_sz = d_off + n;
@@ -894,6 +888,7 @@ int icx_png_encoder_stage_times(icx_png_encoder* enc, const char** names, float*
 struct icx_hdr_batch {
     icx_ctx* ctx = nullptr;
     HdrWs ws;
+    Blocks mem;  // the device memory ws points into
     std::unique_ptr<EventHook> hook;
 };
 
@@ -914,10 +909,9 @@ icx_hdr_batch* icx_hdr_batch_create(icx_ctx* ctx, int max_images, int max_w, int
     auto* b = new icx_hdr_batch();
     b->ctx = ctx;
     b->hook = std::make_unique<EventHook>();
-    if (!hdr_ws_alloc(b->ws, max_images, max_w, max_h)) {
-        hdr_ws_free(b->ws);
+    if (!hdr_ws_alloc(b->ws, b->mem, max_images, max_w, max_h)) {
+        ctx->err = std::string("icx_hdr_batch_create: out of device memory: ") + hipGetErrorString(hipGetLastError());
         delete b;
-        ctx->err = "icx_hdr_batch_create: out of device memory";
         return nullptr;
     }
     return b;
@@ -926,7 +920,6 @@ icx_hdr_batch* icx_hdr_batch_create(icx_ctx* ctx, int max_images, int max_w, int
 void icx_hdr_batch_destroy(icx_hdr_batch* b) {
     if (!b) return;
     (void)hipSetDevice(b->ctx->device);
-    hdr_ws_free(b->ws);
     delete b;
 }
 
@@ -951,11 +944,8 @@ int icx_hdr_batch_stage_times(const icx_hdr_batch* b, const char** names, float*
     if (!b) return 0;
     static const Stage order[4] = {kStParse, kStUnstuff, kStEntropy, kStConvert};
     static const char* const label[4] = {"parse", "locate", "unpack", "convert"};
-    float acc[kStCount] = {0};
-    for (auto& r : b->hook->recs) {
-        float t = 0;
-        if (hipEventSynchronize(r.b) == hipSuccess && hipEventElapsedTime(&t, r.a, r.b) == hipSuccess) acc[r.s] += t;
-    }
+    float acc[kStCount];
+    b->hook->sum(acc);
     for (int k = 0; k < 4 && k < cap; ++k) {
         if (names) names[k] = label[k];
         if (ms) ms[k] = acc[order[k]];
@@ -973,26 +963,26 @@ int icx_hdr_decode(icx_ctx* ctx, const uint8_t* data, size_t size, float** out, 
     const int prc = icx_hdr_probe(data, size, &ww, &hh);
     if (prc != ICX_HDR_OK) return prc;  // header errors need no device work
     ICX_HIP(ctx, hipSetDevice(ctx->device), ICX_HDR_INTERNAL_ERR);
-    icx_hdr_batch* b = icx_hdr_batch_create(ctx, 1, ww, hh);
+    // (declared before the buffers: they are freed first, then the batch)
+    std::unique_ptr<icx_hdr_batch, void (*)(icx_hdr_batch*)> b(icx_hdr_batch_create(ctx, 1, ww, hh), icx_hdr_batch_destroy);
     if (!b) return ICX_HDR_INTERNAL_ERR;
     const uint64_t nout = 4ull * ww * hh;
-    uint8_t* d_in = nullptr;
-    float* d_out = nullptr;
-    uint64_t* d_meta = nullptr;
-    int32_t* d_res = nullptr;
+    Buf<uint8_t> d_in;
+    Buf<float> d_out;
+    Buf<uint64_t> d_meta;
+    Buf<int32_t> d_res;
     int rc = ICX_HDR_INTERNAL_ERR;
     const uint64_t meta[2] = {0, (uint64_t)size};
     int32_t res[4] = {0, 0, 0, 0};
     hipStream_t st = ctx->stream;
-    if (hipMalloc(&d_in, size + 16) == hipSuccess && hipMalloc(&d_out, nout * 4) == hipSuccess &&
-        hipMalloc(&d_meta, 16) == hipSuccess && hipMalloc(&d_res, 16) == hipSuccess &&
-        hipMemcpyAsync(d_in, data, size, hipMemcpyHostToDevice, st) == hipSuccess &&
-        hipMemcpyAsync(d_meta, meta, 16, hipMemcpyHostToDevice, st) == hipSuccess &&
-        icx_hdr_batch_decode(b, 1, d_in, d_meta, d_meta + 1, d_out, nout, d_res, d_res + 1, st) == ICX_HDR_OK &&
-        hipMemcpyAsync(res, d_res, 16, hipMemcpyDeviceToHost, st) == hipSuccess && hipStreamSynchronize(st) == hipSuccess) {
+    if (d_in.reserve(size + 16) && d_out.reserve(nout * 4) && d_meta.reserve(16) && d_res.reserve(16) &&
+        hipMemcpyAsync(d_in.p, data, size, hipMemcpyHostToDevice, st) == hipSuccess &&
+        hipMemcpyAsync(d_meta.p, meta, 16, hipMemcpyHostToDevice, st) == hipSuccess &&
+        icx_hdr_batch_decode(b.get(), 1, d_in.p, d_meta.p, d_meta.p + 1, d_out.p, nout, d_res.p, d_res.p + 1, st) == ICX_HDR_OK &&
+        hipMemcpyAsync(res, d_res.p, 16, hipMemcpyDeviceToHost, st) == hipSuccess && hipStreamSynchronize(st) == hipSuccess) {
         rc = res[0];
         float* hostp = (float*)std::malloc(nout * 4);
-        if (hostp && hipMemcpy(hostp, d_out, nout * 4, hipMemcpyDeviceToHost) == hipSuccess) {
+        if (hostp && hipMemcpy(hostp, d_out.p, nout * 4, hipMemcpyDeviceToHost) == hipSuccess) {
             *out = hostp;
             if (w) *w = res[1];
             if (h) *h = res[2];
@@ -1005,11 +995,6 @@ int icx_hdr_decode(icx_ctx* ctx, const uint8_t* data, size_t size, float** out, 
     } else if (ctx->err.empty()) {
         ctx->err = "icx_hdr_decode: HIP failure";
     }
-    (void)hipFree(d_in);
-    (void)hipFree(d_out);
-    (void)hipFree(d_meta);
-    (void)hipFree(d_res);
-    icx_hdr_batch_destroy(b);
     return rc;
 }
 

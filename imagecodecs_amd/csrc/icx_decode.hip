@@ -1611,7 +1611,7 @@ void launch_decode_back(const GroupWs& ws, int n, uint8_t* d_out, uint64_t out_s
     E(kStIdct);
     // The kernel that reads the coefficients inside the conversion (4:2:0 plane mode 5) runs
     // before the generic upsample: its ping-pong planes (ws.tmp) live in the coefficient pool
-    // (icx_api.cpp ws_alloc_all), which is dead from here on.
+    // (icx_api.cpp ws_alloc), which is dead from here on.
     B(kStConvert);
     if (fuse == 5) {
         const int64_t fs = ((int64_t)(ws.max_w + 255) / 256) * ((ws.max_h + 16 * kFB5 - 1) / (16 * kFB5));

@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "icx_internal.h"
+#include "icx_mem.h"
 
 namespace icx {
 
@@ -848,22 +849,15 @@ static void ijg_table(const uint8_t* base, int q, uint8_t* out) {  // IJG jpeg_q
 // An image whose stream outgrew its words buffer (sized from the images before) is encoded again
 // with a buffer of its measured size.
 struct EncWs {
-    EncTables* T = nullptr;
-    RunRec* recs = nullptr;
-    size_t recs_cap = 0;
-    unsigned* ticket = nullptr;
-    uint32_t* words = nullptr;
-    size_t words_cap = 0;        // bytes
-    uint32_t *wsum = nullptr, *wbase = nullptr;
-    size_t wsum_cap = 0, wbase_cap = 0;
-    uint64_t* info = nullptr;    // device: 4 per image (stream bytes, stuffed bytes)
-    uint64_t* hinfo = nullptr;   // pinned host copy
-    size_t info_cap = 0;         // images
-    const uint8_t** srcs = nullptr;  // device array of source pointers
-    size_t srcs_cap = 0;
+    Buf<EncTables> T;
+    Buf<RunRec> recs;
+    Buf<unsigned> ticket;
+    Buf<uint32_t> words, wsum, wbase;
+    Buf<uint64_t> info;          // device: 4 per image (stream bytes, stuffed bytes)
+    Buf<uint64_t> hinfo{true};   // pinned host copy (+ the look-back flag)
+    Buf<const uint8_t*> srcs;    // device array of source pointers
     uint64_t est_bytes = 0;      // words-buffer estimate per image from the images so far
-    void* tmp = nullptr;
-    size_t tmp_cap = 0;
+    Buf<void> tmp;
     // per-stage HIP events of the last batch (icx_encoder_stage_times): encode, stuff; ms[]
     // accumulates over calls until read
     hipEvent_t ev[4] = {};
@@ -871,10 +865,6 @@ struct EncWs {
     ~EncWs() {
         for (hipEvent_t e : ev)
             if (e) (void)hipEventDestroy(e);
-        for (void* p : {(void*)T, (void*)recs, (void*)ticket, (void*)words, (void*)wsum, (void*)wbase, (void*)info,
-                        (void*)srcs, tmp})
-            if (p) (void)hipFree(p);
-        if (hinfo) (void)hipHostFree(hinfo);
     }
 };
 EncWs* enc_ws_create() {
@@ -885,13 +875,7 @@ EncWs* enc_ws_create() {
 }
 const char* const kEncStageNames[2] = {"encode", "stuff"};
 int enc_ws_stage_times(EncWs* ws, const char** names, float* ms, int cap) {
-    const int k = cap < 2 ? cap : 2;
-    for (int i = 0; i < k; ++i) {
-        if (names) names[i] = kEncStageNames[i];
-        if (ms) ms[i] = ws->ms[i];
-    }
-    for (float& m : ws->ms) m = 0.f;
-    return k;
+    return stage_times_out(kEncStageNames, ws->ms, 2, names, ms, cap);
 }
 void enc_ws_destroy(EncWs* ws) { delete ws; }
 
@@ -899,17 +883,6 @@ void enc_ws_destroy(EncWs* ws) { delete ws; }
     do {                                               \
         if ((call) != hipSuccess) return false;        \
     } while (0)
-
-template <class Ptr>
-static bool grow(Ptr*& p, size_t need, size_t& cap_bytes) {
-    if (need <= cap_bytes && p) return true;
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap_bytes = 0;
-    if (hipMalloc(&p, need) != hipSuccess) return false;
-    cap_bytes = need;
-    return true;
-}
 
 // Images per launch: the words buffers of one launch stay within this many bytes.
 constexpr uint64_t kEncWordsBudget = 4ull << 30;
@@ -925,59 +898,49 @@ static bool enc_launch(hipStream_t st, EncWs& ws, const EncLayout& L, const EncT
     const int64_t runs = (int64_t)runs_per_row * mbh;
     const uint64_t wwords = wbytes / 4;
     const int nwg = (int)((wbytes + kStuffWg - 1) / kStuffWg);
-    if (!ws.T) ENC_HIP(hipMalloc(&ws.T, sizeof(EncTables)));
-    if (!ws.ticket) ENC_HIP(hipMalloc(&ws.ticket, 2 * sizeof(unsigned)));
-    if (!grow(ws.recs, sizeof(RunRec) * runs * n, ws.recs_cap) || !grow(ws.words, wbytes * n, ws.words_cap) ||
-        !grow(ws.wsum, sizeof(uint32_t) * ((size_t)nwg * n + 1), ws.wsum_cap) ||
-        !grow(ws.wbase, sizeof(uint32_t) * ((size_t)nwg * n + 1), ws.wbase_cap))
+    if (!ws.T.reserve(sizeof(EncTables)) || !ws.ticket.reserve(2 * sizeof(unsigned)) ||
+        !ws.recs.reserve(sizeof(RunRec) * runs * n) || !ws.words.reserve(wbytes * n) ||
+        !ws.wsum.reserve(sizeof(uint32_t) * ((size_t)nwg * n + 1)) ||
+        !ws.wbase.reserve(sizeof(uint32_t) * ((size_t)nwg * n + 1)) || !ws.srcs.reserve(sizeof(uint8_t*) * n) ||
+        !ws.info.reserve(sizeof(uint64_t) * 4 * n) || !ws.hinfo.reserve(sizeof(uint64_t) * (4 * n + 1)))
         return false;
-    if (!grow(ws.srcs, sizeof(uint8_t*) * n, ws.srcs_cap)) return false;
-    if ((size_t)n > ws.info_cap) {
-        if (ws.info) (void)hipFree(ws.info);
-        if (ws.hinfo) (void)hipHostFree(ws.hinfo);
-        ws.info = nullptr;
-        ws.hinfo = nullptr;
-        ws.info_cap = 0;
-        ENC_HIP(hipMalloc(&ws.info, sizeof(uint64_t) * 4 * n));
-        ENC_HIP(hipHostMalloc(&ws.hinfo, sizeof(uint64_t) * (4 * n + 1)));
-        ws.info_cap = n;
-    }
-    ENC_HIP(hipMemcpyAsync(ws.T, &T, sizeof T, hipMemcpyHostToDevice, st));
-    ENC_HIP(hipMemcpyAsync(ws.srcs, srcs, sizeof(uint8_t*) * n, hipMemcpyHostToDevice, st));
+    ENC_HIP(hipMemcpyAsync(ws.T.p, &T, sizeof T, hipMemcpyHostToDevice, st));
+    ENC_HIP(hipMemcpyAsync(ws.srcs.p, srcs, sizeof(uint8_t*) * n, hipMemcpyHostToDevice, st));
     const bool ev = ws.ev[3] != nullptr;
     if (ev) ENC_HIP(hipEventRecord(ws.ev[0], st));
-    ENC_HIP(hipMemsetAsync(ws.words, 0, wbytes * n, st));
-    ENC_HIP(hipMemsetAsync(ws.recs, 0, sizeof(RunRec) * runs * n, st));
-    ENC_HIP(hipMemsetAsync(ws.ticket, 0, 2 * sizeof(unsigned), st));
+    ENC_HIP(hipMemsetAsync(ws.words.p, 0, wbytes * n, st));
+    ENC_HIP(hipMemsetAsync(ws.recs.p, 0, sizeof(RunRec) * runs * n, st));
+    ENC_HIP(hipMemsetAsync(ws.ticket.p, 0, 2 * sizeof(unsigned), st));
     EncBatch B;
-    B.srcs = ws.srcs;
+    B.srcs = ws.srcs.p;
     B.w = w;
     B.h = h;
     B.comps = comps;
     B.runs_per_row = runs_per_row;
     B.runs = (int)runs;
     B.wwords = wwords;
-    hipLaunchKernelGGL(k_enc_run, dim3((unsigned)(runs * n)), dim3(256), 0, st, B, L, ws.T, ws.recs, ws.ticket, ws.words,
-                       ws.info);
+    hipLaunchKernelGGL(k_enc_run, dim3((unsigned)(runs * n)), dim3(256), 0, st, B, L, ws.T.p, ws.recs.p, ws.ticket.p,
+                       ws.words.p, ws.info.p);
     if (ev) ENC_HIP(hipEventRecord(ws.ev[1], st));
     if (ev) ENC_HIP(hipEventRecord(ws.ev[2], st));
-    hipLaunchKernelGGL(k_stuff_count_b, dim3(nwg, n), dim3(256), 0, st, ws.words, wwords, ws.info, nwg, ws.wsum);
+    hipLaunchKernelGGL(k_stuff_count_b, dim3(nwg, n), dim3(256), 0, st, ws.words.p, wwords, ws.info.p, nwg, ws.wsum.p);
     size_t tmp_b = 0;
     const int ns = nwg * n + 1;
-    ENC_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_b, ws.wsum, ws.wbase, ns, st));
-    if (!grow(ws.tmp, tmp_b, ws.tmp_cap)) return false;
-    ENC_HIP(hipcub::DeviceScan::ExclusiveSum(ws.tmp, tmp_b, ws.wsum, ws.wbase, ns, st));
-    hipLaunchKernelGGL(k_stuff_write_b, dim3(nwg, n), dim3(256), 0, st, ws.words, wwords, ws.info, nwg, ws.wbase, hdr, out,
-                       stride, cap, eoi ? 1 : 0);
+    ENC_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_b, ws.wsum.p, ws.wbase.p, ns, st));
+    if (!ws.tmp.reserve(tmp_b)) return false;
+    ENC_HIP(hipcub::DeviceScan::ExclusiveSum(ws.tmp.p, tmp_b, ws.wsum.p, ws.wbase.p, ns, st));
+    hipLaunchKernelGGL(k_stuff_write_b, dim3(nwg, n), dim3(256), 0, st, ws.words.p, wwords, ws.info.p, nwg, ws.wbase.p, hdr,
+                       out, stride, cap, eoi ? 1 : 0);
     if (ev) ENC_HIP(hipEventRecord(ws.ev[3], st));
     ENC_HIP(hipGetLastError());
-    ENC_HIP(hipMemcpyAsync(ws.hinfo, ws.info, sizeof(uint64_t) * 4 * n, hipMemcpyDeviceToHost, st));
-    ENC_HIP(hipMemcpyAsync(ws.hinfo + 4 * n, ws.ticket + 1, sizeof(unsigned), hipMemcpyDeviceToHost, st));
+    uint64_t* const hinfo = ws.hinfo.p;
+    ENC_HIP(hipMemcpyAsync(hinfo, ws.info.p, sizeof(uint64_t) * 4 * n, hipMemcpyDeviceToHost, st));
+    ENC_HIP(hipMemcpyAsync(hinfo + 4 * n, ws.ticket.p + 1, sizeof(unsigned), hipMemcpyDeviceToHost, st));
     ENC_HIP(hipStreamSynchronize(st));
-    if (*reinterpret_cast<const unsigned*>(ws.hinfo + 4 * n)) return false;  // a look-back wait expired
+    if (*reinterpret_cast<const unsigned*>(hinfo + 4 * n)) return false;  // a look-back wait expired
     for (int i = 0; i < n; ++i) {
-        nbytes[i] = ws.hinfo[4 * i];
-        total[i] = ws.hinfo[4 * i + 1];
+        nbytes[i] = hinfo[4 * i];
+        total[i] = hinfo[4 * i + 1];
     }
     if (ev) {
         for (int i = 0; i < 2; ++i) {
@@ -1041,29 +1004,25 @@ static bool encode_host_image(hipStream_t st, const EncLayout& L, const EncTable
         return true;
     }
     EncWs ws;
-    uint8_t *d_src = nullptr, *d_out = nullptr;
+    Buf<uint8_t> d_src, d_out;
     HdrArg none;
     none.n = 0;
-    bool ok = hipMalloc(&d_src, srcb) == hipSuccess && hipMemcpyAsync(d_src, src, srcb, hipMemcpyHostToDevice, st) == hipSuccess;
+    bool ok = d_src.reserve(srcb) && hipMemcpyAsync(d_src.p, src, srcb, hipMemcpyHostToDevice, st) == hipSuccess;
     // first pass sizes the output, the second (only when it did not fit) writes it
     uint64_t cap = srcb + 65536, size = 0;
     bool fit = false;
-    const uint8_t* srcs[1] = {d_src};
-    ok = ok && hipMalloc(&d_out, cap) == hipSuccess && enc_batch(st, ws, L, T, 1, srcs, w, h, comps, d_out, cap, cap, false, none, &size, &fit);
+    const uint8_t* srcs[1] = {d_src.p};
+    ok = ok && d_out.reserve(cap) && enc_batch(st, ws, L, T, 1, srcs, w, h, comps, d_out.p, cap, cap, false, none, &size, &fit);
     if (ok && !fit) {
-        (void)hipFree(d_out);
-        d_out = nullptr;
         cap = size;
-        ok = hipMalloc(&d_out, cap) == hipSuccess && enc_batch(st, ws, L, T, 1, srcs, w, h, comps, d_out, cap, cap, false, none, &size, &fit) && fit;
+        ok = d_out.reserve(cap) && enc_batch(st, ws, L, T, 1, srcs, w, h, comps, d_out.p, cap, cap, false, none, &size, &fit) && fit;
     }
     if (ok && size) {
         const size_t h0 = out.size();
         out.resize(h0 + size);
-        ok = hipMemcpyAsync(out.data() + h0, d_out, size, hipMemcpyDeviceToHost, st) == hipSuccess &&
+        ok = hipMemcpyAsync(out.data() + h0, d_out.p, size, hipMemcpyDeviceToHost, st) == hipSuccess &&
              hipStreamSynchronize(st) == hipSuccess;
     }
-    if (d_src) (void)hipFree(d_src);
-    if (d_out) (void)hipFree(d_out);
     out.push_back(0xFF);
     out.push_back(0xD9);
     return ok;

@@ -29,6 +29,7 @@
 
 #include "icx_exr_plan.h"
 #include "icx_internal.h"
+#include "icx_mem.h"
 
 namespace icx {
 
@@ -496,14 +497,8 @@ __global__ __launch_bounds__(256) void k_exr_convert(const uint8_t* __restrict__
 // into the file copy (host-input reads), scratch, chunk table, maps, work lists, failure flags and
 // output, plus pinned failure flags.
 struct ExrWs {
-    uint8_t* arena = nullptr;
-    size_t cap = 0;
-    int32_t* h_fail = nullptr;
-    size_t h_cap = 0;
-    ~ExrWs() {
-        if (arena) (void)hipFree(arena);
-        if (h_fail) (void)hipHostFree(h_fail);
-    }
+    Buf<uint8_t> arena;
+    Buf<int32_t> h_fail{true};
 };
 ExrWs* exr_ws_create() { return new ExrWs(); }
 void exr_ws_destroy(ExrWs* w) { delete w; }
@@ -575,28 +570,15 @@ static int exr_batch(hipStream_t st, ExrWs& ws, int n, const uint8_t* const* dat
     const size_t o_list = take(sizeof(int32_t) * std::max<size_t>(1, list.size()));
     const size_t o_fail = take(sizeof(int32_t) * (size_t)std::max(1, n));
     auto ok = [&](hipError_t e) { return e == hipSuccess; };
-    if (at > ws.cap) {
-        if (ws.arena) (void)hipFree(ws.arena);
-        ws.arena = nullptr;
-        ws.cap = 0;
-        if (!ok(hipMalloc(&ws.arena, at))) {
-            err = "icx_exr_decode: device allocation failed";
-            return -100;
-        }
-        ws.cap = at;
+    if (!ws.arena.reserve(at)) {
+        err = "icx_exr_decode: device allocation failed";
+        return -100;
     }
-    if ((size_t)std::max(1, n) > ws.h_cap) {
-        if (ws.h_fail) (void)hipHostFree(ws.h_fail);
-        ws.h_fail = nullptr;
-        ws.h_cap = 0;
-        if (!ok(hipHostMalloc(&ws.h_fail, sizeof(int32_t) * (size_t)std::max(1, n), hipHostMallocDefault))) {
-            ws.h_fail = nullptr;
-            err = "icx_exr_decode: pinned allocation failed";
-            return -100;
-        }
-        ws.h_cap = (size_t)std::max(1, n);
+    if (!ws.h_fail.reserve(sizeof(int32_t) * (size_t)std::max(1, n))) {
+        err = "icx_exr_decode: pinned allocation failed";
+        return -100;
     }
-    uint8_t* A = ws.arena;
+    uint8_t* A = ws.arena.p;
     std::vector<const uint8_t*> dfile((size_t)n);
     for (int i = 0; i < n; ++i) dfile[i] = d_data_in ? d_data_in[i] : A + o_file[i];
     // chunk file bases relative to the first file's device address (k_exr_unpack)
@@ -651,14 +633,14 @@ static int exr_batch(hipStream_t st, ExrWs& ws, int n, const uint8_t* const* dat
                            out);
     }
     if (!ok(hipGetLastError()) ||
-        !ok(hipMemcpyAsync(ws.h_fail, d_fail, sizeof(int32_t) * (size_t)std::max(1, n), hipMemcpyDeviceToHost, st)) ||
+        !ok(hipMemcpyAsync(ws.h_fail.p, d_fail, sizeof(int32_t) * (size_t)std::max(1, n), hipMemcpyDeviceToHost, st)) ||
         !ok(hipStreamSynchronize(st))) {
         err = "icx_exr_decode: HIP failure";
         return -100;
     }
     for (int i = 0; i < n; ++i) {
         if (codes[i] != kExrOk) continue;
-        if (ws.h_fail[i]) {
+        if (ws.h_fail.p[i]) {
             codes[i] = kExrInvalidData;  // "Invalid/Corrupted data found when decoding pixels" (:5512-5524)
         } else {
             widths[i] = P[i].w;

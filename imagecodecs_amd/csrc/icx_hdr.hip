@@ -22,6 +22,7 @@
 #include <algorithm>
 
 #include "icx_internal.h"
+#include "icx_mem.h"
 
 namespace icx {
 
@@ -541,25 +542,14 @@ int64_t hdr_ws_bytes(int max_images, int max_w, int max_h) {
                                   4LL * max_w * max_h);
 }
 
-bool hdr_ws_alloc(HdrWs& ws, int max_images, int max_w, int max_h) {
+bool hdr_ws_alloc(HdrWs& ws, Blocks& mem, int max_images, int max_w, int max_h) {
     ws.max_images = max_images;
     ws.max_w = max_w;
     ws.max_h = max_h;
     const size_t n = (size_t)max_images;
-    return hipMalloc(&ws.desc, n * sizeof(HdrDesc)) == hipSuccess &&
-           hipMalloc(&ws.cq, n * kHdrCandCap * 4) == hipSuccess && hipMalloc(&ws.ce, n * kHdrCandCap * 4) == hipSuccess &&
-           hipMalloc(&ws.start, n * max_h * 8) == hipSuccess && hipMalloc(&ws.kind, n * max_h) == hipSuccess &&
-           hipMalloc(&ws.planes, n * (size_t)max_h * 4 * max_w) == hipSuccess;
-}
-
-void hdr_ws_free(HdrWs& ws) {
-    (void)hipFree(ws.desc);
-    (void)hipFree(ws.cq);
-    (void)hipFree(ws.ce);
-    (void)hipFree(ws.start);
-    (void)hipFree(ws.kind);
-    (void)hipFree(ws.planes);
-    ws = HdrWs{};
+    return mem.alloc(ws.desc, n * sizeof(HdrDesc)) && mem.alloc(ws.cq, n * kHdrCandCap * 4) &&
+           mem.alloc(ws.ce, n * kHdrCandCap * 4) && mem.alloc(ws.start, n * max_h * 8) && mem.alloc(ws.kind, n * max_h) &&
+           mem.alloc(ws.planes, n * (size_t)max_h * 4 * max_w);
 }
 
 void launch_hdr_decode(const HdrWs& ws, int n, const uint8_t* d_data, const uint64_t* d_off, const uint64_t* d_size,

@@ -118,8 +118,7 @@ struct GroupWs {
     int16_t* ac = nullptr;   // [pool_cap + kGwChunk][64] coefficient pool: quantized blocks, zig-zag order
     int32_t* dc = nullptr;   // [pool_cap + kGwChunk] int32 DC of pool blocks whose cell holds kDcEscape
     uint8_t* planes = nullptr;  // [slots][plane_cap]
-    uint8_t* tmp = nullptr;     // [slots][3 comps][2 buffers][tmp_cap]; aliases `ac` (tmp_own == false)
-    bool tmp_own = false;       // tmp is an allocation of its own (ac too small to hold it)
+    uint8_t* tmp = nullptr;     // [slots][3 comps][2 buffers][tmp_cap]; aliases `ac` unless that is too small
     // parallel entropy decode
     int64_t ucap = 0;           // unstuffed bytes per slot on average: U is one pool of (slots + 2) * ucap
                                 // bytes, each image's stream at SpecImg::uoff (k_spec_plan), so one
@@ -212,6 +211,17 @@ struct StageHook {
     virtual void end(Stage s, hipStream_t st) = 0;
     virtual ~StageHook() = default;
 };
+// The encoders' stage-time read-out: k = min(cap, n) names and accumulated ms copied out, every
+// accumulator zeroed; returns k.
+inline int stage_times_out(const char* const* stage, float* acc, int n, const char** names, float* ms, int cap) {
+    const int k = cap < n ? cap : n;
+    for (int i = 0; i < k; ++i) {
+        if (names) names[i] = stage[i];
+        if (ms) ms[i] = acc[i];
+    }
+    for (int i = 0; i < n; ++i) acc[i] = 0.f;
+    return k;
+}
 
 // Enqueue the whole decode of `n` (<= ws.slots) images on `st`.
 void launch_decode_group(const GroupWs& ws, int n, const uint8_t* d_data, const uint64_t* d_off,
@@ -305,8 +315,8 @@ struct HdrWs {
 };
 int hdr_probe(const uint8_t* data, int64_t size, int* w, int* h);
 int64_t hdr_ws_bytes(int max_images, int max_w, int max_h);
-bool hdr_ws_alloc(HdrWs& ws, int max_images, int max_w, int max_h);
-void hdr_ws_free(HdrWs& ws);
+struct Blocks;  // icx_mem.h: owns the workspace's device memory
+bool hdr_ws_alloc(HdrWs& ws, Blocks& mem, int max_images, int max_w, int max_h);
 void launch_hdr_decode(const HdrWs& ws, int n, const uint8_t* d_data, const uint64_t* d_off, const uint64_t* d_size,
                        float* d_out, uint64_t out_stride, int32_t* d_status, int32_t* d_dims, hipStream_t st,
                        StageHook* hook);

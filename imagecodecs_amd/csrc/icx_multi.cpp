@@ -24,6 +24,7 @@
 
 #include "../../include/icx.h"
 #include "icx_internal.h"
+#include "icx_mem.h"
 
 using namespace icx;
 
@@ -34,8 +35,7 @@ struct Dev {
     icx_batch* batch = nullptr;
     int cap_images = 0;
     // device staging, grown on demand
-    uint8_t* d_buf = nullptr;
-    size_t d_cap = 0;
+    Buf<uint8_t> d_buf;
     Record* d_rec = nullptr;  // the last shard's records on the device (RCCL gather)
     Record* d_all = nullptr;  // the gather's receive buffer
     std::string err;
@@ -91,7 +91,7 @@ icx_multi* icx_multi_create(const int* devices, int ndev, int max_width, int max
             delete m;
             return nullptr;
         }
-        m->devs.push_back(d);
+        m->devs.push_back(std::move(d));
     }
     // RCCL communicators over distinct devices (ICX_MULTI_RCCL=0: always the host gather)
     std::vector<int> dl(devices, devices + ndev), sorted = dl;
@@ -122,7 +122,7 @@ void icx_multi_destroy(icx_multi* m) {
         if (c) (void)m->rccl.destroy(c);
     for (auto& d : m->devs) {
         (void)hipSetDevice(d.device);
-        if (d.d_buf) (void)hipFree(d.d_buf);
+        d.d_buf.release();
         if (d.batch) icx_batch_destroy(d.batch);
         icx_destroy(d.ctx);
     }
@@ -171,14 +171,8 @@ static int run_shard(icx_multi* m, Dev& d, const std::vector<int>& idx, const ui
     const int nr = std::max(n, pad);  // record slots: the shard, padded for the gather
     const size_t meta = (size_t)n * (8 + 8 + 4 + 12) + (size_t)nr * sizeof(icx_record) * (1 + m->devs.size()) + 1024;
     const size_t need = total + meta + (size_t)n * stride_al + 256;
-    if (need > d.d_cap) {
-        if (d.d_buf) (void)hipFree(d.d_buf);
-        d.d_buf = nullptr;
-        d.d_cap = 0;
-        if (hipMalloc(&d.d_buf, need) != hipSuccess) { d.err = "hipMalloc of the shard staging failed"; return ICX_OUT_OF_MEM; }
-        d.d_cap = need;
-    }
-    uint8_t* base = d.d_buf;
+    if (!d.d_buf.reserve(need)) { d.err = "hipMalloc of the shard staging failed"; return ICX_OUT_OF_MEM; }
+    uint8_t* base = d.d_buf.p;
     auto align = [](uintptr_t p, uintptr_t a) { return (p + a - 1) & ~(a - 1); };
     uint8_t* d_data = base;
     uint64_t* d_off = reinterpret_cast<uint64_t*>(align((uintptr_t)(base + total), 16));

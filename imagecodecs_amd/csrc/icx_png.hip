@@ -32,6 +32,7 @@
 #include <vector>
 
 #include "icx_internal.h"
+#include "icx_mem.h"
 
 namespace icx {
 
@@ -1505,28 +1506,24 @@ __global__ void k_png_tail(uint8_t* __restrict__ out, unsigned long long data_at
 using namespace png;
 
 struct PngWs {
-    Stats* st = nullptr;
-    unsigned long long *set_key = nullptr, *set_idx = nullptr;
-    Mode* mode = nullptr;
-    uint8_t *conv = nullptr, *filt = nullptr;
-    size_t conv_cap = 0, filt_cap = 0;
-    uint16_t* tok = nullptr;  // token slots: literal byte, or a match's length slot + distance slot
-    uint32_t *ntok = nullptr, *hist = nullptr, *adl = nullptr, *crc = nullptr, *small = nullptr;
-    size_t tok_cap = 0, seg_cap = 0, blk_cap = 0, hist_cap = 0, crc_cap = 0;
-    BlockCodes* bc = nullptr;
-    unsigned long long *bits = nullptr, *off = nullptr;
-    uint16_t* seghist = nullptr;  // per segment: literal/length and distance symbol counts
-    uint32_t* segx = nullptr;     // per segment: extra bits of its matches
-    uint32_t* seam = nullptr;     // per segment: overhang, head skip, head slots, cut (k_png_seam)
-    uint16_t* head = nullptr;     // per segment: kHead re-parsed head slots
-    uint32_t* plan = nullptr;     // per base block: first / last base block of its deflate block
-    uint32_t* blksym = nullptr;   // per base block: symbols k_png_lz77 counted (+ EOB)
-    size_t seghist_cap = 0, segx_cap = 0, seam_cap = 0, head_cap = 0, plan_cap = 0, blksym_cap = 0;
-    void* tmp = nullptr;
-    size_t tmp_cap = 0;
-    struct PngHost* host = nullptr;  // pinned read-back buffer (PngJob)
-    png::PngTail* tl = nullptr;      // device: the file layout (k_png_size)
-    uint8_t* predev = nullptr;       // device copy of the header bytes (k_png_head)
+    Buf<Stats> st;
+    Buf<unsigned long long> set_key, set_idx;
+    Buf<Mode> mode;
+    Buf<uint8_t> conv, filt;
+    Buf<uint16_t> tok;  // token slots: literal byte, or a match's length slot + distance slot
+    Buf<uint32_t> ntok, hist, adl, crc, small;
+    Buf<BlockCodes> bc;
+    Buf<unsigned long long> bits, off;
+    Buf<uint16_t> seghist;  // per segment: literal/length and distance symbol counts
+    Buf<uint32_t> segx;     // per segment: extra bits of its matches
+    Buf<uint32_t> seam;     // per segment: overhang, head skip, head slots, cut (k_png_seam)
+    Buf<uint16_t> head;     // per segment: kHead re-parsed head slots
+    Buf<uint32_t> plan;     // per base block: first / last base block of its deflate block
+    Buf<uint32_t> blksym;   // per base block: symbols k_png_lz77 counted (+ EOB)
+    Buf<void> tmp;
+    Buf<struct PngHost> host{true};  // pinned read-back buffer (PngJob)
+    Buf<png::PngTail> tl;            // device: the file layout (k_png_size)
+    Buf<uint8_t> predev;             // device copy of the header bytes (k_png_head)
     hipEvent_t done = nullptr;       // a job's statistics event
     // per-stage HIP events (icx_png_encoder_stage_times): stage i spans ev[s][2i] .. ev[s][2i+1],
     // two sets used by alternate images, so one image's times are read once the next image's
@@ -1547,11 +1544,6 @@ struct PngWs {
             for (hipEvent_t e : set)
                 if (e) (void)hipEventDestroy(e);
         if (done) (void)hipEventDestroy(done);
-        if (host) (void)hipHostFree(host);
-        for (void* p : {(void*)tl, (void*)predev, (void*)st, (void*)set_key, (void*)set_idx, (void*)mode, (void*)conv, (void*)filt, (void*)tok,
-                        (void*)ntok, (void*)hist, (void*)adl, (void*)crc, (void*)small, (void*)bc, (void*)bits,
-                        (void*)off, (void*)seghist, (void*)segx, (void*)seam, (void*)head, (void*)plan, (void*)blksym, tmp})
-            if (p) (void)hipFree(p);
     }
 };
 PngWs* png_ws_create() {
@@ -1567,13 +1559,7 @@ int png_ws_stage_times(PngWs* ws, const char** names, float* ms, int cap) {
         ws->read_times(ws->evset ^ 1);  // (the last image encoded)
         ws->ev_pending = false;
     }
-    const int k = cap < PngWs::kStages ? cap : PngWs::kStages;
-    for (int i = 0; i < k; ++i) {
-        if (names) names[i] = kPngStageNames[i];
-        if (ms) ms[i] = ws->ms[i];
-    }
-    for (float& m : ws->ms) m = 0.f;
-    return k;
+    return stage_times_out(kPngStageNames, ws->ms, PngWs::kStages, names, ms, cap);
 }
 void png_ws_destroy(PngWs* ws) { delete ws; }
 
@@ -1586,16 +1572,6 @@ void png_ws_destroy(PngWs* ws) { delete ws; }
 static int seam_join() {
     const char* e = std::getenv("ICX_PNG_SEAM");
     return !(e && e[0] == '0');
-}
-template <class T>
-static bool pgrow(T*& p, size_t bytes, size_t& cap) {
-    if (p && bytes <= cap) return true;
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-    if (hipMalloc(&p, std::max<size_t>(bytes, 64)) != hipSuccess) return false;
-    cap = bytes;
-    return true;
 }
 
 static void be32(uint8_t* p, uint32_t v) {
@@ -1666,23 +1642,22 @@ int PngJob::issue_a() {
     const int64_t np = (int64_t)w * h;
     set = ws->evset;
     timed = ws->ev[set][2 * PngWs::kStages - 1] != nullptr;
-    size_t c1 = ws->st ? sizeof(Stats) : 0, c2 = ws->set_key ? kSetSlots * 8 : 0, c3 = c2, c4 = ws->mode ? sizeof(Mode) : 0;
-    if (!pgrow(ws->st, sizeof(Stats), c1) || !pgrow(ws->set_key, kSetSlots * 8, c2) ||
-        !pgrow(ws->set_idx, kSetSlots * 8, c3) || !pgrow(ws->mode, sizeof(Mode), c4))
+    if (!ws->st.reserve(sizeof(Stats)) || !ws->set_key.reserve(kSetSlots * 8) || !ws->set_idx.reserve(kSetSlots * 8) ||
+        !ws->mode.reserve(sizeof(Mode)))
         return -1;
     // ---- P1: colour statistics (lodepng_compute_color_stats) and auto_choose_color
     Stats zero{};
     zero.bits = 1;
     zero.first_a0 = ~0ull;
     hb->S = zero;
-    PNG_HIP(hipMemcpyAsync(ws->st, &hb->S, sizeof zero, hipMemcpyHostToDevice, st));
-    PNG_HIP(hipMemsetAsync(ws->set_key, 0, kSetSlots * 8, st));
-    PNG_HIP(hipMemsetAsync(ws->set_idx, 0xFF, kSetSlots * 8, st));
+    PNG_HIP(hipMemcpyAsync(ws->st.p, &hb->S, sizeof zero, hipMemcpyHostToDevice, st));
+    PNG_HIP(hipMemsetAsync(ws->set_key.p, 0, kSetSlots * 8, st));
+    PNG_HIP(hipMemsetAsync(ws->set_idx.p, 0xFF, kSetSlots * 8, st));
     mark(0);
     const int gs = (int)std::max<int64_t>(1, std::min<int64_t>((np + 255) / 256, 4096));
-    if (np) hipLaunchKernelGGL(k_png_stats, dim3(gs), dim3(256), 0, st, d_src, np, d, ws->st, ws->set_key, ws->set_idx);
+    if (np) hipLaunchKernelGGL(k_png_stats, dim3(gs), dim3(256), 0, st, d_src, np, d, ws->st.p, ws->set_key.p, ws->set_idx.p);
     mark(1);
-    PNG_HIP(hipMemcpyAsync(&hb->S, ws->st, sizeof(Stats), hipMemcpyDeviceToHost, st));
+    PNG_HIP(hipMemcpyAsync(&hb->S, ws->st.p, sizeof(Stats), hipMemcpyDeviceToHost, st));
     PNG_HIP(hipEventRecord(ev, st));
     return 0;
 }
@@ -1704,8 +1679,8 @@ int PngJob::issue_b() {
         kr = kp[0];
         kg = kp[1];
         kb = kp[2];
-        hipLaunchKernelGGL(k_png_keycheck, dim3(gs), dim3(256), 0, st, d_src, np, kr | kg << 8 | kb << 16, ws->st);
-        PNG_HIP(hipMemcpyAsync(&hb->S, ws->st, sizeof S, hipMemcpyDeviceToHost, st));
+        hipLaunchKernelGGL(k_png_keycheck, dim3(gs), dim3(256), 0, st, d_src, np, kr | kg << 8 | kb << 16, ws->st.p);
+        PNG_HIP(hipMemcpyAsync(&hb->S, ws->st.p, sizeof S, hipMemcpyDeviceToHost, st));
         PNG_HIP(hipStreamSynchronize(st));
         S = hb->S;
         alpha = S.a2 || S.a3;
@@ -1734,8 +1709,8 @@ int PngJob::issue_b() {
         M.colortype = kPalette;
         M.bitdepth = (int)palettebits;
         std::vector<unsigned long long> keys(kSetSlots), idx(kSetSlots);
-        PNG_HIP(hipMemcpyAsync(keys.data(), ws->set_key, kSetSlots * 8, hipMemcpyDeviceToHost, st));
-        PNG_HIP(hipMemcpyAsync(idx.data(), ws->set_idx, kSetSlots * 8, hipMemcpyDeviceToHost, st));
+        PNG_HIP(hipMemcpyAsync(keys.data(), ws->set_key.p, kSetSlots * 8, hipMemcpyDeviceToHost, st));
+        PNG_HIP(hipMemcpyAsync(idx.data(), ws->set_idx.p, kSetSlots * 8, hipMemcpyDeviceToHost, st));
         PNG_HIP(hipStreamSynchronize(st));
         std::vector<std::pair<unsigned long long, uint32_t>> cols;
         for (int i = 0; i < kSetSlots; ++i)
@@ -1756,7 +1731,7 @@ int PngJob::issue_b() {
     M.bpp = ch * M.bitdepth;
     M.bw = (M.bpp + 7) / 8;
     M.lb = ((int64_t)w * M.bpp + 7) / 8;
-    PNG_HIP(hipMemcpyAsync(ws->mode, &M, sizeof M, hipMemcpyHostToDevice, st));
+    PNG_HIP(hipMemcpyAsync(ws->mode.p, &M, sizeof M, hipMemcpyHostToDevice, st));
 
     // ---- header bytes (host; tiny)
     head.assign({137, 80, 78, 71, 13, 10, 26, 10});
@@ -1798,68 +1773,58 @@ int PngJob::issue_b() {
     const uint8_t* img = d_src;
     mark(2);
     if (!identity) {
-        if (!pgrow(ws->conv, (size_t)(M.lb * h), ws->conv_cap)) return -1;
+        if (!ws->conv.reserve((size_t)(M.lb * h))) return -1;
         const int gc = (int)std::max<int64_t>(1, std::min<int64_t>((M.lb * h + 255) / 256, 16384));
-        hipLaunchKernelGGL(k_png_convert, dim3(gc), dim3(256), 0, st, d_src, w, h, d, ws->mode, ws->conv);
-        img = ws->conv;
+        hipLaunchKernelGGL(k_png_convert, dim3(gc), dim3(256), 0, st, d_src, w, h, d, ws->mode.p, ws->conv.p);
+        img = ws->conv.p;
     }
-    if (!pgrow(ws->filt, (size_t)N, ws->filt_cap)) return -1;
-    hipLaunchKernelGGL(k_png_filter, dim3(std::max(1, std::min(h, 16384))), dim3(256), 0, st, img, h, ws->mode, ws->filt);
+    if (!ws->filt.reserve((size_t)N)) return -1;
+    hipLaunchKernelGGL(k_png_filter, dim3(std::max(1, std::min(h, 16384))), dim3(256), 0, st, img, h, ws->mode.p, ws->filt.p);
     mark(3);
 
     // ---- P3/P4: deflate
     nseg = (N + kSeg - 1) / kSeg;
     nblk = (nseg + kSegPerBlock - 1) / kSegPerBlock;
-    size_t c5 = ws->seg_cap, c6 = ws->seg_cap, c7 = ws->seg_cap, c8 = ws->seg_cap;
-    if (!pgrow(ws->tok, (size_t)nseg * kSlots * 2, ws->tok_cap)) return -1;
-    if ((size_t)nseg * 8 > ws->seg_cap || !ws->ntok) {
-        if (!pgrow(ws->ntok, (size_t)nseg * 8, c5) || !pgrow(ws->adl, (size_t)nseg * 8, c6) ||
-            !pgrow(ws->bits, (size_t)nseg * 8, c7) || !pgrow(ws->off, (size_t)nseg * 8, c8))
-            return -1;
-        ws->seg_cap = (size_t)nseg * 8;
-    }
-    if (!pgrow(ws->hist, (size_t)nblk * (kNLL + kND) * 4, ws->hist_cap) ||
-        !pgrow(ws->bc, (size_t)nblk * sizeof(BlockCodes), ws->blk_cap))
+    if (!ws->tok.reserve((size_t)nseg * kSlots * 2) || !ws->ntok.reserve((size_t)nseg * 8) ||
+        !ws->adl.reserve((size_t)nseg * 8) || !ws->bits.reserve((size_t)nseg * 8) || !ws->off.reserve((size_t)nseg * 8) ||
+        !ws->hist.reserve((size_t)nblk * (kNLL + kND) * 4) || !ws->bc.reserve((size_t)nblk * sizeof(BlockCodes)) ||
+        !ws->small.reserve(64))
         return -1;
-    size_t c11 = ws->small ? 64 : 0;
-    if (!pgrow(ws->small, 64, c11)) return -1;
     mark(4);
-    if (!pgrow(ws->seghist, (size_t)nseg * (kNLL + kND) * 2, ws->seghist_cap) ||
-        !pgrow(ws->segx, (size_t)nseg * 4, ws->segx_cap) || !pgrow(ws->seam, (size_t)nseg * 16, ws->seam_cap) ||
-        !pgrow(ws->head, (size_t)nseg * kHead * 2, ws->head_cap) || !pgrow(ws->plan, (size_t)nblk * 8, ws->plan_cap) ||
-        !pgrow(ws->blksym, (size_t)nblk * 4, ws->blksym_cap))
+    if (!ws->seghist.reserve((size_t)nseg * (kNLL + kND) * 2) || !ws->segx.reserve((size_t)nseg * 4) ||
+        !ws->seam.reserve((size_t)nseg * 16) || !ws->head.reserve((size_t)nseg * kHead * 2) ||
+        !ws->plan.reserve((size_t)nblk * 8) || !ws->blksym.reserve((size_t)nblk * 4))
         return -1;
-    hipLaunchKernelGGL(k_png_lz77, dim3((unsigned)nblk), dim3(256), 0, st, ws->filt, N, nseg, 1 + M.lb, M.bw, ws->tok,
-                       ws->ntok, ws->hist, ws->adl, ws->seghist, ws->segx, ws->seam, ws->blksym);
+    hipLaunchKernelGGL(k_png_lz77, dim3((unsigned)nblk), dim3(256), 0, st, ws->filt.p, N, nseg, 1 + M.lb, M.bw, ws->tok.p,
+                       ws->ntok.p, ws->hist.p, ws->adl.p, ws->seghist.p, ws->segx.p, ws->seam.p, ws->blksym.p);
     gwave = (unsigned)((nseg + 3) / 4);  // one wave per segment
-    hipLaunchKernelGGL(k_png_seam, dim3(gwave), dim3(256), 0, st, ws->filt, N, nseg, 1 + M.lb, M.bw, ws->tok, ws->ntok,
-                       ws->seam, ws->head, seam_join());
-    hipLaunchKernelGGL(k_png_seam_apply, dim3((unsigned)((nseg + 255) / 256)), dim3(256), 0, st, ws->filt, N, nseg,
-                       ws->tok, ws->ntok, ws->seam, ws->head, ws->seghist, ws->segx, ws->hist);
+    hipLaunchKernelGGL(k_png_seam, dim3(gwave), dim3(256), 0, st, ws->filt.p, N, nseg, 1 + M.lb, M.bw, ws->tok.p, ws->ntok.p,
+                       ws->seam.p, ws->head.p, seam_join());
+    hipLaunchKernelGGL(k_png_seam_apply, dim3((unsigned)((nseg + 255) / 256)), dim3(256), 0, st, ws->filt.p, N, nseg,
+                       ws->tok.p, ws->ntok.p, ws->seam.p, ws->head.p, ws->seghist.p, ws->segx.p, ws->hist.p);
     mark(5);
     mark(6);
     // (ICX_PNG_PLAN_LDS lowers the LDS limit so tests reach the global-memory walk)
     const char* pl = std::getenv("ICX_PNG_PLAN_LDS");
     const int64_t lds_max = pl ? std::max<int64_t>(0, std::min<int64_t>(kPlanLds, std::atoll(pl))) : kPlanLds;
     hipLaunchKernelGGL(k_png_blockplan, dim3(1), dim3(256), (size_t)std::max<int64_t>(1, std::min<int64_t>(nblk, lds_max)) * 4,
-                       st, ws->blksym, nblk, ws->plan, lds_max);
-    hipLaunchKernelGGL(k_png_huff, dim3((unsigned)nblk), dim3(64), 0, st, ws->hist, nblk, ws->plan, ws->bc);
-    hipLaunchKernelGGL(k_png_segbits, dim3(gwave), dim3(256), 0, st, nseg, ws->seghist, ws->segx, ws->bc, ws->plan,
-                       ws->bits);
+                       st, ws->blksym.p, nblk, ws->plan.p, lds_max);
+    hipLaunchKernelGGL(k_png_huff, dim3((unsigned)nblk), dim3(64), 0, st, ws->hist.p, nblk, ws->plan.p, ws->bc.p);
+    hipLaunchKernelGGL(k_png_segbits, dim3(gwave), dim3(256), 0, st, nseg, ws->seghist.p, ws->segx.p, ws->bc.p, ws->plan.p,
+                       ws->bits.p);
     size_t tb = 0;
-    PNG_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, ws->bits, ws->off, (int)nseg, st));
-    if (!pgrow(ws->tmp, tb, ws->tmp_cap)) return -1;
-    PNG_HIP(hipcub::DeviceScan::ExclusiveSum(ws->tmp, tb, ws->bits, ws->off, (int)nseg, st));
-    hipLaunchKernelGGL(k_png_adler, dim3(1), dim3(256), 0, st, ws->adl, nseg, ws->small);
+    PNG_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, ws->bits.p, ws->off.p, (int)nseg, st));
+    if (!ws->tmp.reserve(tb)) return -1;
+    PNG_HIP(hipcub::DeviceScan::ExclusiveSum(ws->tmp.p, tb, ws->bits.p, ws->off.p, (int)nseg, st));
+    hipLaunchKernelGGL(k_png_adler, dim3(1), dim3(256), 0, st, ws->adl.p, nseg, ws->small.p);
     mark(7);
     // ---- P5: the file (png_encoder.cpp:1888-1952, 2277), laid out on the device
-    size_t c13 = ws->tl ? sizeof(png::PngTail) : 0, c14 = ws->predev ? sizeof hb->pre : 0;
-    if (!pgrow(ws->tl, sizeof(png::PngTail), c13) || !pgrow(ws->predev, sizeof hb->pre, c14)) return -1;
+    if (!ws->tl.reserve(sizeof(png::PngTail)) || !ws->predev.reserve(sizeof hb->pre)) return -1;
     const uint64_t idat_at = head.size();  // IDAT chunk header position
     const uint64_t data_at = idat_at + 8;  // zlib stream position
     const uint64_t dstart = data_at + 2;   // deflate data
-    hipLaunchKernelGGL(k_png_size, dim3(1), dim3(1), 0, st, ws->off, ws->bits, nseg, (unsigned long long)data_at,
-                       (unsigned long long)cap, ws->tl);
+    hipLaunchKernelGGL(k_png_size, dim3(1), dim3(1), 0, st, ws->off.p, ws->bits.p, nseg, (unsigned long long)data_at,
+                       (unsigned long long)cap, ws->tl.p);
     // The deflate bits go to a 4-byte aligned word view of d_out starting at dstart rounded down
     // -- aligned as an address, since a batch slot may start anywhere (k_png_emit's atomics on the
     // words two segments share need it) -- and the few bytes before it (zlib header) are
@@ -1867,9 +1832,9 @@ int PngJob::issue_b() {
     const uint64_t mis = (reinterpret_cast<uintptr_t>(d_out) + dstart) & 3u;
     uint32_t* wv = reinterpret_cast<uint32_t*>(d_out + dstart - mis);
     mark(8);
-    hipLaunchKernelGGL(k_png_zero, dim3(1024), dim3(256), 0, st, wv, (unsigned long long)mis, ws->tl);
-    hipLaunchKernelGGL(k_png_emit, dim3(gwave), dim3(256), 0, st, nseg, ws->tok, ws->ntok, ws->seam, ws->head, ws->bc,
-                       ws->plan, ws->off, ws->bits, wv, (unsigned long long)(mis * 8), ws->tl);
+    hipLaunchKernelGGL(k_png_zero, dim3(1024), dim3(256), 0, st, wv, (unsigned long long)mis, ws->tl.p);
+    hipLaunchKernelGGL(k_png_emit, dim3(gwave), dim3(256), 0, st, nseg, ws->tok.p, ws->ntok.p, ws->seam.p, ws->head.p, ws->bc.p,
+                       ws->plan.p, ws->off.p, ws->bits.p, wv, (unsigned long long)(mis * 8), ws->tl.p);
     mark(9);
     // signature + IHDR/PLTE/tRNS + IDAT length (k_png_head) / type + zlib header (78 01, :1932-1941)
     std::vector<uint8_t> pre = head;
@@ -1879,9 +1844,9 @@ int PngJob::issue_b() {
     pre.push_back(0x01);
     if (pre.size() > sizeof hb->pre) return -1;
     std::memcpy(hb->pre, pre.data(), pre.size());
-    PNG_HIP(hipMemcpyAsync(ws->predev, hb->pre, pre.size(), hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(k_png_head, dim3(1), dim3(256), 0, st, d_out, ws->predev, (int)pre.size(),
-                       (unsigned long long)idat_at, (unsigned long long)dstart, ws->small, (long long)N, ws->tl);
+    PNG_HIP(hipMemcpyAsync(ws->predev.p, hb->pre, pre.size(), hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_png_head, dim3(1), dim3(256), 0, st, d_out, ws->predev.p, (int)pre.size(),
+                       (unsigned long long)idat_at, (unsigned long long)dstart, ws->small.p, (long long)N, ws->tl.p);
     // CRC-32 over "IDAT" + zlib stream: segment CRCs aligned to the stream's end (the device
     // knows its length; the grid covers the longest stream that fits), folded 256:1 per pass
     // (bounded by the longest stream this image can produce -- at most 16 bits per filtered byte
@@ -1892,17 +1857,12 @@ int PngJob::issue_b() {
     const uint64_t zcap = cap > data_at + 16 ? cap - data_at - 16 : 0;
     const uint64_t zmax = std::min(zcap, zworst) + 4;  // ("IDAT" + stream)
     const int64_t ncs = std::max<int64_t>(1, (int64_t)((zmax + kCrcSeg - 1) / kCrcSeg));
-    size_t c12 = ws->crc_cap;
-    const size_t crc_need = (size_t)(ncs + (ncs + 255) / 256 + 64) * 4;
-    if (crc_need > ws->crc_cap || !ws->crc) {
-        if (!pgrow(ws->crc, crc_need, c12)) return -1;
-        ws->crc_cap = crc_need;
-    }
+    if (!ws->crc.reserve((size_t)(ncs + (ncs + 255) / 256 + 64) * 4)) return -1;
     mark(10);
     hipLaunchKernelGGL(k_png_crc_seg, dim3((unsigned)((ncs + 255) / 256)), dim3(256), 0, st, d_out + idat_at + 4,
-                       ws->tl, ncs, ws->crc);
+                       ws->tl.p, ncs, ws->crc.p);
     uint32_t X = x8n(kCrcSeg);
-    uint32_t* cur = ws->crc;
+    uint32_t* cur = ws->crc.p;
     int64_t m = ncs;
     while (m > 1) {
         const int64_t nb = (m + 255) / 256;
@@ -1912,9 +1872,9 @@ int PngJob::issue_b() {
         cur = nxt;
         m = nb;
     }
-    hipLaunchKernelGGL(k_png_tail, dim3(1), dim3(1), 0, st, d_out, (unsigned long long)data_at, cur, ws->tl);
+    hipLaunchKernelGGL(k_png_tail, dim3(1), dim3(1), 0, st, d_out, (unsigned long long)data_at, cur, ws->tl.p);
     mark(11);
-    PNG_HIP(hipMemcpyAsync(out_tl, ws->tl, sizeof(png::PngTail), hipMemcpyDeviceToHost, st));
+    PNG_HIP(hipMemcpyAsync(out_tl, ws->tl.p, sizeof(png::PngTail), hipMemcpyDeviceToHost, st));
     PNG_HIP(hipGetLastError());
     if (timed) {
         ws->ev_pending = true;
@@ -1925,10 +1885,10 @@ int PngJob::issue_b() {
 
 static bool png_job_init(PngJob& j, PngWs* ws, hipStream_t st, int w, int h, int d, const uint8_t* d_src, uint8_t* d_out,
                          uint64_t cap, png::PngTail* out_tl) {
-    if (!ws->host && hipHostMalloc(reinterpret_cast<void**>(&ws->host), sizeof(PngHost)) != hipSuccess) return false;
+    if (!ws->host.reserve(sizeof(PngHost))) return false;
     if (!ws->done && hipEventCreateWithFlags(&ws->done, hipEventDisableTiming) != hipSuccess) return false;
     j.ws = ws;
-    j.hb = ws->host;
+    j.hb = ws->host.p;
     j.st = st;
     j.ev = ws->done;
     j.w = w;
@@ -1949,7 +1909,7 @@ int png_encode_device(hipStream_t st, PngWs* ws, int w, int h, int d, const uint
     // hipHostFree would synchronise the device)
     PngJob j;
     int rc = png_job_init(j, ws, st, w, h, d, d_src, d_out, cap, nullptr) ? 0 : -1;
-    png::PngTail* tl = rc == 0 ? &ws->host->tl : nullptr;
+    png::PngTail* tl = rc == 0 ? &ws->host.p->tl : nullptr;
     if (rc == 0) {
         *tl = png::PngTail{};
         j.out_tl = tl;
@@ -2016,29 +1976,24 @@ int png_encode_device_batch(int k, hipStream_t* sts, PngWs** wss, int n, int w, 
 bool png_encode_gpu(hipStream_t st, int w, int h, int d, const uint8_t* src, std::vector<uint8_t>& out) {
     PngWs ws;
     const size_t srcb = (size_t)w * h * d;
-    uint8_t *d_src = nullptr, *d_out = nullptr;
-    bool ok = hipMalloc(&d_src, std::max<size_t>(srcb, 1)) == hipSuccess &&
-              hipMemcpyAsync(d_src, src, srcb, hipMemcpyHostToDevice, st) == hipSuccess;
+    Buf<uint8_t> d_src, d_out;
+    bool ok = d_src.reserve(srcb) && hipMemcpyAsync(d_src.p, src, srcb, hipMemcpyHostToDevice, st) == hipSuccess;
     uint64_t cap = srcb + srcb / 64 + (1 << 20), n = 0;
     int rc = -1;
     if (ok) {
-        ok = hipMalloc(&d_out, cap) == hipSuccess;
-        if (ok) rc = png_encode_device(st, &ws, w, h, d, d_src, d_out, cap, &n);
+        ok = d_out.reserve(cap);
+        if (ok) rc = png_encode_device(st, &ws, w, h, d, d_src.p, d_out.p, cap, &n);
         if (rc == 1) {
-            (void)hipFree(d_out);
-            d_out = nullptr;
             cap = n;
-            ok = hipMalloc(&d_out, cap) == hipSuccess;
-            if (ok) rc = png_encode_device(st, &ws, w, h, d, d_src, d_out, cap, &n);
+            ok = d_out.reserve(cap);
+            if (ok) rc = png_encode_device(st, &ws, w, h, d, d_src.p, d_out.p, cap, &n);
         }
         ok = ok && rc == 0;
         if (ok) {
             out.resize(n);
-            ok = hipMemcpy(out.data(), d_out, n, hipMemcpyDeviceToHost) == hipSuccess;
+            ok = hipMemcpy(out.data(), d_out.p, n, hipMemcpyDeviceToHost) == hipSuccess;
         }
     }
-    if (d_src) (void)hipFree(d_src);
-    if (d_out) (void)hipFree(d_out);
     return ok;
 }
 

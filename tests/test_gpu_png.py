@@ -162,6 +162,46 @@ def test_png_device_batch(ctx, monkeypatch, inflight):
     enc.close()
 
 
+@pytest.fixture(scope="module")
+def regrow_seq(ctx):
+    """Images that make a persistent workspace grow, shrink its use and grow again, with the
+    one-shot entry's file (a fresh workspace per call) for each: small, more than one 256 KiB
+    deflate block (360 300 filtered bytes: segment, block and CRC buffers grow), small again, a
+    palette image (first use of the convert buffer, on a grown workspace), an odd-sized RGB one."""
+    rng = np.random.default_rng(2024)
+    noise = lambda w, h, d: rng.integers(0, 256, (h, w, d), dtype=np.uint8)
+    pxs = [noise(16, 16, 4), noise(300, 300, 4), noise(16, 16, 4), _palette_img(rng, 40, 300, 300), noise(301, 299, 3)]
+    return [(np.ascontiguousarray(p), ctx.png_encode(p.shape[1], p.shape[0], p.shape[2], p.tobytes())) for p in pxs]
+
+
+@pytest.mark.parametrize("entry", ["device", "batch"])
+def test_png_workspace_regrowth(ctx, regrow_seq, monkeypatch, entry):
+    """One PngEncoder across sizes: every file equals the one-shot entry's byte for byte. The
+    batch entry takes two copies of each image per call with ICX_PNG_INFLIGHT=2, so its second
+    workspace goes through the same sequence."""
+    import torch
+    monkeypatch.setenv("ICX_PNG_INFLIGHT", "2")
+    enc = icx.PngEncoder(ctx)
+    for i, (px, want) in enumerate(regrow_seq):
+        assert want is not None
+        h, w, d = px.shape
+        d_src = torch.from_numpy(px).cuda()
+        stride = len(want) + 4096
+        d_out = torch.zeros(2 * stride, dtype=torch.uint8, device="cuda")
+        if entry == "device":
+            rc, n = enc.encode_device(w, h, d, d_src.data_ptr(), d_out.data_ptr(), stride)
+            assert rc == icx.OK, (i, rc)
+            sizes = [n]
+        else:
+            st, sizes = enc.encode_device_batch(w, h, d, [d_src.data_ptr()] * 2, d_out.data_ptr(), stride)
+            assert (st == icx.OK).all(), (i, st)
+        out = d_out.cpu().numpy()
+        for k, n in enumerate(sizes):
+            assert int(n) == len(want), (i, k)
+            assert out[k * stride: k * stride + int(n)].tobytes() == want, (i, k)
+    enc.close()
+
+
 def test_png_rejects(ctx):
     assert ctx.png_encode(4, 4, 2, bytes(32)) is None
     assert ctx.png_encode(0, 4, 4, b"") is None
