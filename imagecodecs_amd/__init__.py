@@ -11,6 +11,8 @@ callers (tests, bench): it binds the C ABI with ctypes and offers
   * ``Batch``                     -- device-resident batched decode (the throughput path)
   * ``Context.hdr_decode``        -- Image::readHdr's Radiance RGBE -> float decode (codecs.cpp:706-777)
   * ``HdrBatch``                  -- device-resident batched .hdr decode
+  * ``Context.png_decode``        -- Image::readPng's PNG -> RGBA8 decode (codecs.cpp:903-1020)
+  * ``PngBatch``                  -- device-resident batched PNG decode
   * ``Context.exr_decode``        -- Image::readExr's OpenEXR -> RGBA float (tinyexr LoadEXRFromMemory)
   * ``Image``                     -- ImageCodecs::Image (codecs.h:16-103) for .jpg/.jpeg/.png/.hdr
 
@@ -28,7 +30,9 @@ import numpy as np
 __all__ = ["ICXError", "Context", "Batch", "HdrBatch", "Image", "lib", "build", "LIB_PATH",
            "OK", "NO_JPEG", "UNSUPPORTED", "OUT_OF_MEM", "INTERNAL_ERR", "SYNTAX_ERROR",
            "HDR_OK", "HDR_NOT_RADIANCE", "HDR_BAD_HEADER", "HDR_MALFORMED", "HDR_TRUNCATED",
-           "HDR_TOO_LARGE", "HDR_INTERNAL_ERR", "hdr_probe", "exr_probe", "EXR_SUCCESS", "EXR_INVALID_DATA", "Multi", "RECORD_DTYPE", "records_device",
+           "HDR_TOO_LARGE", "HDR_INTERNAL_ERR", "hdr_probe", "exr_probe",
+           "PngBatch", "png_probe", "PNGR_OK", "PNGR_NOT_PNG", "PNGR_BAD_HEADER", "PNGR_UNSUPPORTED", "PNGR_MALFORMED",
+           "PNGR_BAD_DATA", "PNGR_TOO_LARGE", "PNGR_INTERNAL_ERR", "EXR_SUCCESS", "EXR_INVALID_DATA", "Multi", "RECORD_DTYPE", "records_device",
            "checksum64", "multi_shard"]
 
 OK, NO_JPEG, UNSUPPORTED, OUT_OF_MEM, INTERNAL_ERR, SYNTAX_ERROR = range(6)  # nj_result_t
@@ -99,6 +103,12 @@ _SIGS = {
     "icx_hdr_batch_destroy": (None, [_vp]),
     "icx_hdr_batch_decode": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _vp]),
     "icx_hdr_batch_stage_times": (_i32, [_vp, _vp, _vp, _i32]),
+    "icx_png_probe": (_i32, [_vp, _sz, C.POINTER(_i32), C.POINTER(_i32)]),
+    "icx_png_decode": (_i32, [_vp, _vp, _sz, C.POINTER(_vp), C.POINTER(_i32), C.POINTER(_i32)]),
+    "icx_png_batch_create": (_vp, [_vp, _i32, _i32, _i32]),
+    "icx_png_batch_destroy": (None, [_vp]),
+    "icx_png_batch_decode": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _vp]),
+    "icx_png_batch_stage_times": (_i32, [_vp, _vp, _vp, _i32]),
     "icx_jpeg_records": (_i32, [_vp, _i32, _vp, _u64, _vp, _vp, _i32, _i32, _vp, _vp]),
     "icx_checksum64": (_u64, [_vp, _sz]),
     "icx_ctx_device": (_i32, [_vp]),
@@ -122,6 +132,10 @@ RECORD_DTYPE = np.dtype([("status", "<i4"), ("width", "<i4"), ("height", "<i4"),
 # icx_hdr_result (include/icx.h): Image::readHdr outcomes
 HDR_OK, HDR_NOT_RADIANCE, HDR_BAD_HEADER, HDR_MALFORMED, HDR_TRUNCATED, HDR_TOO_LARGE = range(6)
 HDR_INTERNAL_ERR = -1
+
+# icx_png_read_result (include/icx.h): Image::readPng outcomes
+PNGR_OK, PNGR_NOT_PNG, PNGR_BAD_HEADER, PNGR_UNSUPPORTED, PNGR_MALFORMED, PNGR_BAD_DATA, PNGR_TOO_LARGE = range(7)
+PNGR_INTERNAL_ERR = -1
 
 # icx_exr_result (include/icx.h): tinyexr's LoadEXRFromMemory codes
 EXR_SUCCESS, EXR_INVALID_MAGIC_NUMBER, EXR_INVALID_EXR_VERSION, EXR_INVALID_ARGUMENT, EXR_INVALID_DATA = 0, -1, -2, -3, -4
@@ -269,6 +283,22 @@ class Context:
             arr = np.frombuffer(C.string_at(out.value, n * 4), np.float32).reshape(h.value, w.value, 4).copy()
             lib().icx_free(out)
         return code, w.value, h.value, rows.value, arr
+
+    def png_decode(self, data: bytes):
+        """Image::readPng (codecs.cpp:903-1020) on the GPU -> (code, w, h, uint8 (h, w, 4) RGBA or
+        None); code is an icx_png_read_result."""
+        buf = C.create_string_buffer(bytes(data), max(1, len(data)))
+        out = C.c_void_p()
+        w, h = C.c_int(), C.c_int()
+        code = lib().icx_png_decode(self._p, buf, len(data), C.byref(out), C.byref(w), C.byref(h))
+        if code == PNGR_INTERNAL_ERR:
+            raise ICXError("icx_png_decode: " + _err(self._p))
+        arr = None
+        if out.value:
+            n = w.value * h.value * 4
+            arr = np.frombuffer(C.string_at(out.value, n), np.uint8).reshape(h.value, w.value, 4).copy()
+            lib().icx_free(out)
+        return code, w.value, h.value, arr
 
     def exr_decode(self, data: bytes):
         """Image::readExr's LoadEXRFromMemory (tinyexr.h:6645) on the GPU -> (code, w, h, float32
@@ -607,6 +637,47 @@ def exr_probe(data: bytes):
     return code, w.value, h.value
 
 
+def png_probe(data: bytes):
+    """Host chunk walk of the PNG read (signature, IHDR, PLTE / tRNS, IDAT present) -> (code, width, height)."""
+    w, h = C.c_int(), C.c_int()
+    buf = C.create_string_buffer(bytes(data), max(1, len(data)))
+    code = lib().icx_png_probe(buf, len(data), C.byref(w), C.byref(h))
+    return code, w.value, h.value
+
+
+class PngBatch:
+    """Device-resident batched PNG decode (icx_png_batch_*): image i is
+    d_data[d_offsets[i] .. + d_sizes[i]); RGBA8 at d_out + i*out_stride bytes, status in
+    d_status[i], {width, height, 4} in d_dims[3i..]."""
+
+    def __init__(self, ctx: Context, max_images: int, max_width: int, max_height: int):
+        self.ctx = ctx
+        self._p = lib().icx_png_batch_create(ctx.ptr, max_images, max_width, max_height)
+        if not self._p:
+            raise ICXError("icx_png_batch_create failed: " + _err(ctx.ptr))
+        self.max_images, self.max_width, self.max_height = max_images, max_width, max_height
+
+    def close(self):
+        if getattr(self, "_p", None):
+            lib().icx_png_batch_destroy(self._p)
+            self._p = None
+
+    def __del__(self):
+        self.close()
+
+    def decode_device(self, n, d_data, d_offsets, d_sizes, d_out, out_stride, d_status, d_dims, stream=0):
+        rc = lib().icx_png_batch_decode(self._p, n, d_data, d_offsets, d_sizes, d_out, out_stride,
+                                        d_status, d_dims, stream or None)
+        if rc != PNGR_OK:
+            raise ICXError(f"icx_png_batch_decode -> {rc}: {_err(self.ctx.ptr)}")
+
+    def stage_times(self) -> dict:
+        names = (C.c_char_p * 8)()
+        ms = (C.c_float * 8)()
+        k = lib().icx_png_batch_stage_times(self._p, names, ms, 8)
+        return {names[i].decode(): float(ms[i]) for i in range(k)}
+
+
 class HdrBatch:
     """Device-resident batched Radiance .hdr decode (icx_hdr_batch_*): image i is
     d_data[d_offsets[i] .. + d_sizes[i]); 4 floats per pixel at d_out + i*out_stride floats."""
@@ -643,8 +714,8 @@ class Image:
     """ImageCodecs::Image (codecs.h:16-103) for the JPEG hot path.
 
     read()/write() dispatch on the lower-cased extension like Image::read/write
-    (codecs.cpp:53-122): read .jpg/.jpeg (readJpg) and .hdr (readHdr: d = 4, type FLOAT, the
-    floats' bytes in pixels_), write .jpg/.jpeg and .png. Other extensions raise ValueError (the
+    (codecs.cpp:53-122): read .jpg/.jpeg (readJpg), .png (readPng: d = 4, type UBYTE) and .hdr
+    (readHdr: d = 4, type FLOAT, the floats' bytes in pixels_), write .jpg/.jpeg and .png. Other extensions raise ValueError (the
     reference's std::invalid_argument for unknown types)."""
 
     UBYTE, USHORT, FLOAT = range(3)  # ImageCodecs::Type (codecs.h:14)
@@ -669,6 +740,9 @@ class Image:
         if ext == ".exr":
             self._read_exr(filepath)
             return
+        if ext == ".png":
+            self._read_png(filepath)
+            return
         if ext not in (".jpg", ".jpeg"):
             raise ValueError("Cannot parse filetype")
         data = open(filepath, "rb").read()
@@ -690,6 +764,18 @@ class Image:
         self.w_, self.h_, self.d_ = w, h, 4
         self.pixels_ = px.reshape(-1).view(np.uint8).copy()
         self.type_ = Image.FLOAT
+
+    def _read_png(self, filepath: str):
+        """readPng (codecs.cpp:903-1020): d = 4, type UBYTE, 8-bit RGBA rows top-down. Every
+        failure is Image::read's RuntimeError("Could not read image data") (:85-88: readPng leaves
+        pixels_ null)."""
+        data = open(filepath, "rb").read()
+        code, w, h, px = self.context().png_decode(data)
+        if code != PNGR_OK:
+            raise RuntimeError("Could not read image data")
+        self.w_, self.h_, self.d_ = w, h, 4
+        self.pixels_ = px.reshape(-1).copy()
+        self.type_ = Image.UBYTE
 
     def _read_exr(self, filepath: str):
         """readExr (codecs.cpp:464-493): LoadEXRFromMemory -> d = 4, type FLOAT, the floats' bytes in

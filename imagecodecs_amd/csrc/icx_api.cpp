@@ -998,6 +998,121 @@ int icx_hdr_decode(icx_ctx* ctx, const uint8_t* data, size_t size, float** out, 
     return rc;
 }
 
+// --------------------------------------------------------- PNG read (Image::readPng)
+struct icx_png_batch {
+    icx_ctx* ctx = nullptr;
+    PngdWs ws;
+    Blocks mem;  // the device memory ws points into
+    std::unique_ptr<EventHook> hook;
+};
+
+int icx_png_probe(const uint8_t* data, size_t size, int* w, int* h) {
+    int ww = 0, hh = 0;
+    const int rc = data ? pngd_probe(data, (int64_t)size, &ww, &hh) : ICX_PNGR_NOT_PNG;
+    if (w) *w = rc == ICX_PNGR_OK ? ww : 0;
+    if (h) *h = rc == ICX_PNGR_OK ? hh : 0;
+    return rc;
+}
+
+icx_png_batch* icx_png_batch_create(icx_ctx* ctx, int max_images, int max_w, int max_h) {
+    // (images are one grid dimension; no image the walk accepts is larger than the pixel limit)
+    if (!ctx || max_images <= 0 || max_images > 65535 || max_w <= 0 || max_h <= 0 || max_w > 0x1000000 || max_h > 0x1000000) {
+        if (ctx) ctx->err = "icx_png_batch_create: bad arguments";
+        return nullptr;
+    }
+    ICX_HIP(ctx, hipSetDevice(ctx->device), nullptr);
+    auto* b = new icx_png_batch();
+    b->ctx = ctx;
+    b->hook = std::make_unique<EventHook>();
+    if (!pngd_ws_alloc(b->ws, b->mem, max_images, max_w, max_h)) {
+        ctx->err = std::string("icx_png_batch_create: out of device memory: ") + hipGetErrorString(hipGetLastError());
+        delete b;
+        return nullptr;
+    }
+    return b;
+}
+
+void icx_png_batch_destroy(icx_png_batch* b) {
+    if (!b) return;
+    (void)hipSetDevice(b->ctx->device);
+    delete b;
+}
+
+int icx_png_batch_decode(icx_png_batch* b, int n, const uint8_t* d_data, const uint64_t* d_off, const uint64_t* d_size,
+                         uint8_t* d_out, uint64_t out_stride, int32_t* d_status, int32_t* d_dims, void* stream) {
+    if (!b) return ICX_PNGR_INTERNAL_ERR;
+    icx_ctx* ctx = b->ctx;
+    if (n < 0 || n > b->ws.max_images) { ctx->err = "icx_png_batch_decode: n exceeds batch capacity"; return ICX_PNGR_INTERNAL_ERR; }
+    if (n == 0) return ICX_PNGR_OK;
+    if (!d_data || !d_off || !d_size || !d_out || !d_status || !d_dims) { ctx->err = "null pointer"; return ICX_PNGR_INTERNAL_ERR; }
+    if (out_stride < 4ull * b->ws.max_w * b->ws.max_h) { ctx->err = "icx_png_batch_decode: out_stride too small"; return ICX_PNGR_INTERNAL_ERR; }
+    if ((reinterpret_cast<uintptr_t>(d_out) & 3) || (out_stride & 3)) { ctx->err = "icx_png_batch_decode: d_out and out_stride must be multiples of 4"; return ICX_PNGR_INTERNAL_ERR; }
+    ICX_HIP(ctx, hipSetDevice(ctx->device), ICX_PNGR_INTERNAL_ERR);
+    hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
+    const RoctxRange range("icx_png_batch_decode");
+    b->hook->reset();
+    launch_pngd_decode(b->ws, n, d_data, d_off, d_size, d_out, out_stride, d_status, d_dims, st, b->hook.get());
+    ICX_HIP(ctx, hipGetLastError(), ICX_PNGR_INTERNAL_ERR);
+    return ICX_PNGR_OK;
+}
+
+int icx_png_batch_stage_times(const icx_png_batch* b, const char** names, float* ms, int cap) {
+    if (!b) return 0;
+    static const Stage order[5] = {kStParse, kStUnstuff, kStEntropy, kStIdct, kStConvert};
+    static const char* const label[5] = {"parse", "gather", "inflate", "unfilter", "expand"};
+    float acc[kStCount];
+    b->hook->sum(acc);
+    for (int k = 0; k < 5 && k < cap; ++k) {
+        if (names) names[k] = label[k];
+        if (ms) ms[k] = acc[order[k]];
+    }
+    return 5;
+}
+
+int icx_png_decode(icx_ctx* ctx, const uint8_t* data, size_t size, uint8_t** out, int* w, int* h) {
+    if (out) *out = nullptr;
+    if (w) *w = 0;
+    if (h) *h = 0;
+    if (!ctx || !out) return ICX_PNGR_INTERNAL_ERR;
+    int ww = 0, hh = 0;
+    const int prc = icx_png_probe(data, size, &ww, &hh);
+    if (prc != ICX_PNGR_OK) return prc;  // header and chunk errors need no device work
+    ICX_HIP(ctx, hipSetDevice(ctx->device), ICX_PNGR_INTERNAL_ERR);
+    // (declared before the buffers: they are freed first, then the batch)
+    std::unique_ptr<icx_png_batch, void (*)(icx_png_batch*)> b(icx_png_batch_create(ctx, 1, ww, hh), icx_png_batch_destroy);
+    if (!b) return ICX_PNGR_INTERNAL_ERR;
+    const uint64_t nout = 4ull * ww * hh;
+    Buf<uint8_t> d_in, d_out;
+    Buf<uint64_t> d_meta;
+    Buf<int32_t> d_res;
+    int rc = ICX_PNGR_INTERNAL_ERR;
+    const uint64_t meta[2] = {0, (uint64_t)size};
+    int32_t res[4] = {0, 0, 0, 0};
+    hipStream_t st = ctx->stream;
+    if (d_in.reserve(size) && d_out.reserve(nout) && d_meta.reserve(16) && d_res.reserve(16) &&
+        hipMemcpyAsync(d_in.p, data, size, hipMemcpyHostToDevice, st) == hipSuccess &&
+        hipMemcpyAsync(d_meta.p, meta, 16, hipMemcpyHostToDevice, st) == hipSuccess &&
+        icx_png_batch_decode(b.get(), 1, d_in.p, d_meta.p, d_meta.p + 1, d_out.p, nout, d_res.p, d_res.p + 1, st) == ICX_PNGR_OK &&
+        hipMemcpyAsync(res, d_res.p, 16, hipMemcpyDeviceToHost, st) == hipSuccess && hipStreamSynchronize(st) == hipSuccess) {
+        rc = res[0];
+        if (rc == ICX_PNGR_OK) {
+            uint8_t* hostp = (uint8_t*)std::malloc(nout);
+            if (hostp && hipMemcpy(hostp, d_out.p, nout, hipMemcpyDeviceToHost) == hipSuccess) {
+                *out = hostp;
+                if (w) *w = res[1];
+                if (h) *h = res[2];
+            } else {
+                std::free(hostp);
+                ctx->err = "icx_png_decode: host allocation or copy failed";
+                rc = ICX_PNGR_INTERNAL_ERR;
+            }
+        }
+    } else if (ctx->err.empty()) {
+        ctx->err = "icx_png_decode: HIP failure";
+    }
+    return rc;
+}
+
 // --------------------------------------------------------- OpenEXR (Image::readExr)
 int icx_exr_probe(const uint8_t* data, size_t size, int* w, int* h) {
     if (w) *w = 0;

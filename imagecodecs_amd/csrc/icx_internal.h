@@ -321,6 +321,22 @@ void launch_hdr_decode(const HdrWs& ws, int n, const uint8_t* d_data, const uint
                        float* d_out, uint64_t out_stride, int32_t* d_status, int32_t* d_dims, hipStream_t st,
                        StageHook* hook);
 
+// PNG read (icx_pngd.hip; Image::readPng, codecs.cpp:903-1020). Status codes: icx_pngd_core.h
+// kPngr* = include/icx.h ICX_PNGR_*.
+struct PngdDesc;
+struct PngdWs {
+    int max_images = 0, max_w = 0, max_h = 0;
+    int64_t scap = 0, zcap = 0;  // bytes per image of scr and z (multiples of 16)
+    PngdDesc* desc = nullptr;    // [max_images]
+    uint8_t* scr = nullptr;      // [max_images][scap] filtered bytes, un-filtered in place
+    uint8_t* z = nullptr;        // [max_images][zcap] the IDAT payloads as one zlib stream
+};
+int pngd_probe(const uint8_t* data, int64_t size, int* w, int* h);
+bool pngd_ws_alloc(PngdWs& ws, Blocks& mem, int max_images, int max_w, int max_h);
+void launch_pngd_decode(const PngdWs& ws, int n, const uint8_t* d_data, const uint64_t* d_off, const uint64_t* d_size,
+                        uint8_t* d_out, uint64_t out_stride, int32_t* d_status, int32_t* d_dims, hipStream_t st,
+                        StageHook* hook);
+
 // ---- OpenEXR read (icx_exr.hip) ----
 // tinyexr's LoadEXRFromMemory; returns its code (-100: HIP failure, err says which).
 struct ExrWs;

@@ -247,6 +247,48 @@ int icx_png_encode_device_batch(icx_png_encoder* enc, int n, int width, int heig
  * the number of stages. */
 int icx_png_encoder_stage_times(icx_png_encoder* enc, const char** names, float* ms, int cap);
 
+/* ---- PNG read (Image::readPng, codecs.cpp:903-1020) --------------------------------------------
+ * Output as readPng returns it (d = 4, Type::UBYTE): 8-bit RGBA, rows top-down. The reference
+ * decodes through libpng; here the sample conversions are the PNG specification's (unpinned
+ * parity): 16-bit samples keep their high byte, grey of 1 / 2 / 4 bits is scaled by
+ * 255 / (2^depth - 1), a palette index takes PLTE's colour and tRNS's alpha (255 without one;
+ * (0, 0, 0, 255) past the end of PLTE), grey is replicated to R, G, B, and alpha is the file's
+ * (colour types 4 and 6), 0 where a tRNS key equals the samples at file precision (colour types
+ * 0 and 2), else 255. Non-interlaced files of every colour type and bit depth. The CRCs of IHDR,
+ * PLTE and tRNS are verified; an IDAT CRC is not (the zlib stream's Adler-32 is). A zlib stream
+ * that inflates to anything but height * (1 + row bytes) is BAD_DATA (libpng only warns about
+ * excess data). */
+enum icx_png_read_result {
+    ICX_PNGR_OK = 0,
+    ICX_PNGR_NOT_PNG = 1,       /* no PNG signature                                              */
+    ICX_PNGR_BAD_HEADER = 2,    /* IHDR missing, damaged (CRC) or with illegal values            */
+    ICX_PNGR_UNSUPPORTED = 3,   /* interlaced, or an unknown critical chunk                      */
+    ICX_PNGR_MALFORMED = 4,     /* a chunk runs past the file; bad PLTE / tRNS; no PLTE; no IDAT */
+    ICX_PNGR_BAD_DATA = 5,      /* the zlib stream or a filter byte                              */
+    ICX_PNGR_TOO_LARGE = 6,     /* above the reference's 0x1000000 pixel limit, or the batch's   */
+    ICX_PNGR_INTERNAL_ERR = -1  /* HIP failure (see icx_last_error)                              */
+};
+/* Chunk walk only (host): width/height of a file the decoder would start on, else the code. */
+int icx_png_probe(const uint8_t* data, size_t size, int* width, int* height);
+/* One image, host in / host out: *out receives a malloc()'d width*height*4 byte buffer (free with
+ * icx_free). A code the probe gives is returned without touching the GPU. */
+int icx_png_decode(icx_ctx* ctx, const uint8_t* data, size_t size, uint8_t** out, int* width, int* height);
+/* Device-resident batch: image i = d_data[d_offsets[i] .. + d_sizes[i]), RGBA8 at d_out +
+ * i*out_stride bytes (d_out and out_stride multiples of 4; out_stride >= 4*max_width*max_height),
+ * per-image status in d_status[i] and {width, height, 4} in d_dims[3i..] (zeros unless OK). An
+ * image wider or taller than the batch's maxima is TOO_LARGE; a failed image does not disturb the
+ * others and its pixels are unspecified. Asynchronous on hip_stream (NULL = the context's
+ * stream), no host read-back. Returns ICX_PNGR_OK or ICX_PNGR_INTERNAL_ERR. */
+typedef struct icx_png_batch icx_png_batch;
+icx_png_batch* icx_png_batch_create(icx_ctx* ctx, int max_images, int max_width, int max_height);
+void icx_png_batch_destroy(icx_png_batch* b);
+int icx_png_batch_decode(icx_png_batch* b, int n, const uint8_t* d_data, const uint64_t* d_offsets,
+                         const uint64_t* d_sizes, uint8_t* d_out, uint64_t out_stride, int32_t* d_status,
+                         int32_t* d_dims, void* hip_stream);
+/* Milliseconds per stage of the last icx_png_batch_decode ("parse", "gather", "inflate",
+ * "unfilter", "expand"; synchronises). Returns the number of stages. */
+int icx_png_batch_stage_times(const icx_png_batch* b, const char** names, float* ms, int cap);
+
 /* ---- Radiance .hdr read (Image::readHdr, codecs.cpp:706-777) -----------------------------------
  * Output as readHdr returns it (d = 4, Type::FLOAT): 4 floats per pixel, rows in file order,
  * R, G, B = convertComponent(E - 128, v) = v * 2^(E - 136) (codecs.cpp:610-615; exact, so the

@@ -7,6 +7,9 @@
  *                  decode on the GPU (readJpg, codecs.cpp:821-849 -> icx_jpeg_decode).
  *               ".hdr" decodes Radiance RGBE to 4 floats per pixel on the GPU (readHdr,
  *               codecs.cpp:706-777 -> icx_hdr_decode; bit-identical floats).
+ *               ".png" decodes to 8-bit RGBA, rows top-down, on the GPU (readPng,
+ *               codecs.cpp:903-1020 -> icx_png_decode; the PNG specification's sample
+ *               conversions where the reference calls libpng).
  *               ".exr" decodes OpenEXR to RGBA floats on the GPU (readExr, codecs.cpp:464-493 ->
  *               icx_exr_decode = tinyexr's LoadEXRFromMemory; scope in include/icx.h).
  *   write(path) -- ".jpg"/".jpeg" encode with tiny_jpeg quality 3 semantics (writeJpg,
@@ -189,6 +192,38 @@ class Image {
         type_ = Type::FLOAT;
     }
 
+    // readPng (codecs.cpp:903-1020): d = 4, Type::UBYTE, 8-bit RGBA, rows top-down (the reference
+    // fills them bottom-up and flips). As in the reference a failure leaves pixels_ null, and
+    // read() throws "Could not read image data" (:85-88).
+    void readPng(const std::string& path) {
+        std::FILE* f = std::fopen(path.c_str(), "rb");
+        std::vector<uint8_t> buf;
+        if (f) {
+            uint8_t chunk[1 << 16];
+            size_t k;
+            while ((k = std::fread(chunk, 1, sizeof chunk, f)) > 0) buf.insert(buf.end(), chunk, chunk + k);
+            std::fclose(f);
+        }
+        auto& P = detail::icx_process();
+        std::lock_guard<std::mutex> lock(P.mu);
+        uint8_t* out = nullptr;
+        int w = 0, h = 0;
+        const int rc = icx_png_decode(P.get(), buf.data(), buf.size(), &out, &w, &h);
+        delete[] pixels_;
+        pixels_ = nullptr;
+        w_ = h_ = d_ = 0;
+        if (rc == ICX_PNGR_INTERNAL_ERR) throw std::runtime_error(std::string("icx_png_decode: ") + icx_last_error(P.get()));
+        if (rc != ICX_PNGR_OK) return;
+        const size_t n = (size_t)w * h * 4;
+        pixels_ = new unsigned char[n ? n : 1];
+        if (n) std::memcpy(pixels_, out, n);
+        icx_free(out);
+        w_ = w;
+        h_ = h;
+        d_ = 4;
+        type_ = Type::UBYTE;
+    }
+
     void writeJpg(const std::string& path) {
         auto& P = detail::icx_process();
         std::lock_guard<std::mutex> lock(P.mu);
@@ -262,6 +297,7 @@ public:
     void read(const std::string& filepath) {
         const std::string ext = detail::lower_ext(filepath);
         if (ext == ".jpg" || ext == ".jpeg") readJpg(filepath);
+        else if (ext == ".png") readPng(filepath);
         else if (ext == ".hdr") readHdr(filepath);
         else if (ext == ".exr") readExr(filepath);
         else throw std::invalid_argument("Cannot parse filetype");
