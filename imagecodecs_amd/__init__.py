@@ -14,6 +14,7 @@ callers (tests, bench): it binds the C ABI with ctypes and offers
   * ``Context.png_decode``        -- Image::readPng's PNG -> RGBA8 decode (codecs.cpp:903-1020)
   * ``PngBatch``                  -- device-resident batched PNG decode
   * ``Context.exr_decode``        -- Image::readExr's OpenEXR -> RGBA float (tinyexr LoadEXRFromMemory)
+  * ``Context.exr_encode``        -- Image::writeExr's float pixels -> OpenEXR (tinyexr SaveEXR)
   * ``Image``                     -- ImageCodecs::Image (codecs.h:16-103) for .jpg/.jpeg/.png/.hdr
 
 There is deliberately no CPU fallback: if libicx.so is missing or no GPU is visible every
@@ -123,6 +124,11 @@ _SIGS = {
     "icx_exr_decode": (_i32, [_vp, _vp, _sz, C.POINTER(_vp), C.POINTER(_i32), C.POINTER(_i32)]),
     "icx_exr_decode_device": (_i32, [_vp, _vp, _vp, _sz, _vp, _sz, C.POINTER(_i32), C.POINTER(_i32)]),
     "icx_exr_decode_device_batch": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "icx_exr_save_to_memory": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, C.POINTER(_vp), C.POINTER(_sz)]),
+    "icx_exr_save_to_file": (_i32, [_vp, C.c_char_p, _vp, _i32, _i32, _i32, _i32]),
+    "icx_exr_encode_bound": (_sz, [_i32, _i32, _i32, _i32]),
+    "icx_exr_encode_device": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _sz, C.POINTER(_sz)]),
+    "icx_exr_encode_device_batch": (_i32, [_vp, _i32, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp]),
 }
 
 # icx_record (include/icx.h): per-image result record gathered across devices / ranks
@@ -349,6 +355,53 @@ class Context:
         if rc != 0:
             raise ICXError(f"icx_exr_decode_device_batch: code {rc}")
         return codes, ws, hs
+
+    def exr_encode(self, arr, fp16: bool = False) -> bytes:
+        """Image::writeExr's SaveEXR (tinyexr.h:9333) on the GPU: float32 (h, w) or (h, w, c) with
+        c in 1, 3, 4 -> the file's bytes. Raises ICXError with the icx_exr_result otherwise."""
+        a = np.ascontiguousarray(arr, np.float32)
+        if a.ndim == 2:
+            a = a[:, :, None]
+        if a.ndim != 3:
+            raise ICXError(f"icx_exr_save_to_memory: code {EXR_INVALID_ARGUMENT}")
+        h, w, c = a.shape
+        out, size = C.c_void_p(), C.c_size_t()
+        code = lib().icx_exr_save_to_memory(self._p, a.ctypes.data, w, h, c, 1 if fp16 else 0, C.byref(out),
+                                            C.byref(size))
+        if code == EXR_INTERNAL_ERR:
+            raise ICXError("icx_exr_save_to_memory: " + _err(self._p))
+        if code != EXR_SUCCESS:
+            raise ICXError(f"icx_exr_save_to_memory: code {code}")
+        data = C.string_at(out.value, size.value)
+        lib().icx_free(out)
+        return data
+
+    def exr_encode_device(self, d_src: int, width: int, height: int, components: int, fp16: bool, d_out: int,
+                          cap: int):
+        """icx_exr_encode_device: ``width*height*components`` floats on the device at ``d_src``, the
+        file to device memory ``d_out`` (``cap`` bytes of room) -> (code, size)."""
+        size = C.c_size_t()
+        code = lib().icx_exr_encode_device(self._p, C.c_void_p(d_src), width, height, components, 1 if fp16 else 0,
+                                           C.c_void_p(d_out), cap, C.byref(size))
+        return code, size.value
+
+    def exr_encode_device_batch(self, d_srcs, widths, heights, components: int, fp16: bool, d_outs, caps):
+        """icx_exr_encode_device_batch over n images -> (codes int32, sizes uint64)."""
+        n = len(d_srcs)
+        sp = (C.c_void_p * n)(*d_srcs)
+        op = (C.c_void_p * n)(*d_outs)
+        cp = (C.c_size_t * n)(*caps)
+        ws = np.asarray(widths, np.int32)
+        hs = np.asarray(heights, np.int32)
+        codes = np.zeros(n, np.int32)
+        sizes = (C.c_size_t * n)()
+        rc = lib().icx_exr_encode_device_batch(self._p, n, sp, ws.ctypes.data, hs.ctypes.data, components,
+                                               1 if fp16 else 0, op, cp, codes.ctypes.data, sizes)
+        if rc == EXR_INTERNAL_ERR:
+            raise ICXError("icx_exr_encode_device_batch: " + _err(self._p))
+        if rc != 0:
+            raise ICXError(f"icx_exr_encode_device_batch: code {rc}")
+        return codes, np.array(list(sizes), np.uint64)
 
     def png_encode(self, width: int, height: int, d: int, src: bytes):
         """PNG bytes of an RGB8 (d=3) / RGBA8 (d=4) image (png_encoder::saveToFile), or None."""
@@ -715,7 +768,7 @@ class Image:
 
     read()/write() dispatch on the lower-cased extension like Image::read/write
     (codecs.cpp:53-122): read .jpg/.jpeg (readJpg), .png (readPng: d = 4, type UBYTE) and .hdr
-    (readHdr: d = 4, type FLOAT, the floats' bytes in pixels_), write .jpg/.jpeg and .png. Other extensions raise ValueError (the
+    (readHdr: d = 4, type FLOAT, the floats' bytes in pixels_) and .exr, write .jpg/.jpeg, .png and .exr. Other extensions raise ValueError (the
     reference's std::invalid_argument for unknown types)."""
 
     UBYTE, USHORT, FLOAT = range(3)  # ImageCodecs::Type (codecs.h:14)
@@ -796,6 +849,12 @@ class Image:
             out = self.context().png_encode(self.w_, self.h_, self.d_, self.pixels_.tobytes())
         elif ext in (".jpg", ".jpeg"):
             out = self.context().tje_encode(3, self.w_, self.h_, self.d_, self.pixels_.tobytes())  # codecs.cpp:853
+        elif ext == ".exr":  # writeExr -> SaveEXR(float*, w, h, d, fp16 = 0) (codecs.cpp:495-505)
+            try:  # (the reference only prints tinyexr's message: nothing is thrown, no file appears)
+                px = np.frombuffer(self.pixels_.tobytes(), np.float32, self.w_ * self.h_ * self.d_)
+                out = self.context().exr_encode(px.reshape(self.h_, self.w_, self.d_))
+            except (ICXError, ValueError):
+                return
         else:
             raise ValueError("Cannot parse filetype")
         with open(filepath, "wb") as f:

@@ -31,6 +31,7 @@ struct icx_ctx {
     int nj_w = 0, nj_h = 0, nj_color = 0, nj_size = 0;
     icx_batch* single = nullptr;  // cached workspace for one-image calls
     ExrWs* exr = nullptr;  // grow-only EXR read buffers (icx_exr.hip)
+    ExrwWs* exrw = nullptr;  // grow-only EXR write buffers (icx_exrw.hip)
 };
 
 struct EventHook;
@@ -170,6 +171,7 @@ void icx_destroy(icx_ctx* c) {
     (void)hipSetDevice(c->device);
     if (c->single) icx_batch_destroy(c->single);
     if (c->exr) exr_ws_destroy(c->exr);
+    if (c->exrw) exrw_ws_destroy(c->exrw);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
 }
@@ -1208,6 +1210,95 @@ int icx_exr_decode_device(icx_ctx* ctx, const uint8_t* data, const uint8_t* d_da
         if (h) *h = hh;
     }
     return rc;
+}
+
+// --------------------------------------------------------- OpenEXR (Image::writeExr)
+size_t icx_exr_encode_bound(int width, int height, int components, int save_as_fp16) {
+    try {
+        return exrw_encode_bound(width, height, components, save_as_fp16);
+    } catch (const std::exception&) {
+        return 0;
+    }
+}
+
+int icx_exr_encode_device_batch(icx_ctx* ctx, int n, const float* const* d_src, const int32_t* widths,
+                                const int32_t* heights, int components, int save_as_fp16, uint8_t* const* d_out,
+                                const size_t* caps, int32_t* codes, size_t* sizes) {
+    if (!ctx) return ICX_EXR_INTERNAL_ERR;
+    if (n < 0 || (n > 0 && (!d_src || !widths || !heights || !d_out || !caps || !codes || !sizes)))
+        return ICX_EXR_INVALID_ARGUMENT;
+    if (n == 0) return ICX_EXR_SUCCESS;
+    ICX_HIP(ctx, hipSetDevice(ctx->device), ICX_EXR_INTERNAL_ERR);
+    const RoctxRange range("icx_exr_encode_device_batch");
+    std::string err;
+    int rc;
+    try {  // (nothing may cross the C ABI: a host allocation failure is an internal error)
+        if (!ctx->exrw) ctx->exrw = exrw_ws_create();
+        rc = exrw_encode_batch(ctx->stream, *ctx->exrw, n, d_src, widths, heights, components, save_as_fp16, d_out, caps,
+                               codes, sizes, err);
+    } catch (const std::exception& e) {
+        err = std::string("icx_exr_encode_device_batch: ") + e.what();
+        rc = ICX_EXR_INTERNAL_ERR;
+    }
+    if (rc != 0) {
+        ctx->err = err.empty() ? "icx_exr_encode_device_batch: HIP failure" : err;
+        return ICX_EXR_INTERNAL_ERR;
+    }
+    for (int i = 0; i < n; ++i)
+        if (codes[i] == ICX_EXR_INTERNAL_ERR) ctx->err = "icx_exr_encode_device_batch: an output buffer is too small";
+    return ICX_EXR_SUCCESS;
+}
+
+int icx_exr_encode_device(icx_ctx* ctx, const float* d_src, int width, int height, int components, int save_as_fp16,
+                          uint8_t* d_out, size_t cap, size_t* size) {
+    if (size) *size = 0;
+    if (!ctx) return ICX_EXR_INTERNAL_ERR;
+    if (!d_src || !d_out || !size) return ICX_EXR_INVALID_ARGUMENT;
+    int32_t code = 0, w = width, h = height;
+    const int rc = icx_exr_encode_device_batch(ctx, 1, &d_src, &w, &h, components, save_as_fp16, &d_out, &cap, &code, size);
+    if (rc != ICX_EXR_SUCCESS) return rc;
+    if (code == ICX_EXR_INTERNAL_ERR) ctx->err = "icx_exr_encode_device: output buffer too small";
+    return code;
+}
+
+int icx_exr_save_to_memory(icx_ctx* ctx, const float* data, int width, int height, int components, int save_as_fp16,
+                           uint8_t** out, size_t* size) {
+    if (out) *out = nullptr;
+    if (size) *size = 0;
+    if (!ctx) return ICX_EXR_INTERNAL_ERR;
+    if (!data || !out || !size || !exrw_args_ok(width, height, components)) return ICX_EXR_INVALID_ARGUMENT;
+    ICX_HIP(ctx, hipSetDevice(ctx->device), ICX_EXR_INTERNAL_ERR);
+    const RoctxRange range("icx_exr_save_to_memory");
+    std::string err;
+    int rc;
+    try {
+        if (!ctx->exrw) ctx->exrw = exrw_ws_create();
+        rc = exrw_save_to_memory(ctx->stream, *ctx->exrw, data, width, height, components, save_as_fp16, out, size, err);
+    } catch (const std::exception& e) {
+        err = std::string("icx_exr_save_to_memory: ") + e.what();
+        rc = ICX_EXR_INTERNAL_ERR;
+    }
+    if (rc == ICX_EXR_INTERNAL_ERR) ctx->err = err.empty() ? "icx_exr_save_to_memory: HIP failure" : err;
+    return rc;
+}
+
+int icx_exr_save_to_file(icx_ctx* ctx, const char* path, const float* data, int width, int height, int components,
+                         int save_as_fp16) {
+    if (!ctx) return ICX_EXR_INTERNAL_ERR;
+    if (!path) return ICX_EXR_INVALID_ARGUMENT;
+    uint8_t* mem = nullptr;
+    size_t size = 0;
+    const int rc = icx_exr_save_to_memory(ctx, data, width, height, components, save_as_fp16, &mem, &size);
+    if (rc != ICX_EXR_SUCCESS) return rc;
+    std::FILE* f = std::fopen(path, "wb");
+    const bool ok = f && std::fwrite(mem, 1, size, f) == size;
+    const bool closed = f && std::fclose(f) == 0;
+    std::free(mem);
+    if (!ok || !closed) {
+        ctx->err = std::string("icx_exr_save_to_file: cannot write ") + path;
+        return ICX_EXR_INTERNAL_ERR;
+    }
+    return ICX_EXR_SUCCESS;
 }
 
 }  // extern "C"

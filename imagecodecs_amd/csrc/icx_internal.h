@@ -349,4 +349,17 @@ int exr_decode_batch(hipStream_t st, ExrWs& ws, int n, const uint8_t* const* dat
                      int32_t* heights, std::string& err);
 int exr_probe(const uint8_t* data, size_t size, int* width, int* height);
 
+// ---- OpenEXR write (icx_exrw.hip) ----
+// tinyexr's SaveEXR; codes are tinyexr's (-100: HIP failure, or a file that does not fit).
+struct ExrwWs;
+ExrwWs* exrw_ws_create();
+void exrw_ws_destroy(ExrwWs* w);
+bool exrw_args_ok(int width, int height, int components);
+size_t exrw_encode_bound(int width, int height, int components, int fp16);
+int exrw_encode_batch(hipStream_t st, ExrwWs& ws, int n, const float* const* d_src, const int32_t* widths,
+                      const int32_t* heights, int components, int fp16, uint8_t* const* d_out, const size_t* caps,
+                      int32_t* codes, size_t* sizes, std::string& err);
+int exrw_save_to_memory(hipStream_t st, ExrwWs& ws, const float* data, int width, int height, int components, int fp16,
+                        uint8_t** out, size_t* size, std::string& err);
+
 }  // namespace icx

@@ -374,6 +374,39 @@ int icx_exr_decode_device_batch(icx_ctx* ctx, int n, const uint8_t* const* data,
                                 const size_t* sizes, float* const* d_out, const size_t* out_floats, int32_t* codes,
                                 int32_t* widths, int32_t* heights);
 
+/* ---- OpenEXR write (Image::writeExr, codecs.cpp:495-505 -> tinyexr SaveEXR, tinyexr.h:9333) ----
+ * `data`: width*height*components interleaved floats, components 1, 3 or 4 (file channels A /
+ * B,G,R / A,B,G,R). save_as_fp16 > 0 stores HALF samples (float_to_half_full), otherwise FLOAT.
+ * Single-part scanline file; NONE when width < 16 && height < 16, else ZIP in chunks of 16 lines.
+ * Header, offset table, chunk headers, NONE payloads and ZIP chunks stored raw are tinyexr's bytes;
+ * a compressed ZIP chunk is a zlib stream of our own that inflates to exactly the bytes tinyexr
+ * compresses (and is stored raw exactly when that stream is not smaller than the samples).
+ * components not in {1, 3, 4}, width or height < 1, a null pointer, or a chunk of 2 GiB or more
+ * -> ICX_EXR_INVALID_ARGUMENT. */
+/* Host pixels in, *out receives the malloc()'d file (free with icx_free). Returns an icx_exr_result. */
+int icx_exr_save_to_memory(icx_ctx* ctx, const float* data, int width, int height, int components, int save_as_fp16,
+                           uint8_t** out, size_t* size);
+/* SaveEXR with a context: the same file written to `path` (ICX_EXR_INTERNAL_ERR when it cannot
+ * be written; see icx_last_error). */
+int icx_exr_save_to_file(icx_ctx* ctx, const char* path, const float* data, int width, int height, int components,
+                         int save_as_fp16);
+/* The largest file such a write can give (header + offset table + chunk headers + raw payloads);
+ * 0 for arguments the writes refuse. Host only. */
+size_t icx_exr_encode_bound(int width, int height, int components, int save_as_fp16);
+/* The write with pixels and file resident on the device: `d_src` floats in, the file to `d_out`
+ * (room for `cap` bytes, any alignment), its length to *size. A file longer than `cap` is
+ * ICX_EXR_INTERNAL_ERR: nothing of it is written, *size says what it needs. Synchronises with
+ * the context's stream. */
+int icx_exr_encode_device(icx_ctx* ctx, const float* d_src, int width, int height, int components, int save_as_fp16,
+                          uint8_t* d_out, size_t cap, size_t* size);
+/* n such writes in one call: the chunks of all n images go through every kernel in one launch
+ * (a 2048^2 image has 128 independent chunks). codes[i] gets image i's icx_exr_result, sizes[i]
+ * its file length. Returns ICX_EXR_SUCCESS when the call ran (per-image results in codes),
+ * ICX_EXR_INVALID_ARGUMENT for a null array, or ICX_EXR_INTERNAL_ERR (HIP failure). */
+int icx_exr_encode_device_batch(icx_ctx* ctx, int n, const float* const* d_src, const int32_t* widths,
+                                const int32_t* heights, int components, int save_as_fp16, uint8_t* const* d_out,
+                                const size_t* caps, int32_t* codes, size_t* sizes);
+
 #ifdef __cplusplus
 }
 #endif

@@ -17,6 +17,10 @@
  *               ".png" encodes with png_encoder::saveToFile semantics (writePng,
  *               codecs.cpp:1022-1025 -> icx_png_save_to_file: lodepng's colour type and
  *               filter bytes, GPU deflate).
+ *               ".exr" writes pixels_ as w*h*d floats with tinyexr's SaveEXR semantics (writeExr,
+ *               codecs.cpp:495-505 -> icx_exr_save_to_file: FLOAT samples, ZIP chunks of 16
+ *               lines with a GPU deflate, tinyexr's bytes everywhere else); as in the reference a
+ *               failure throws nothing (lastWriteOk() tells).
  *   pixels_ is new[]-owned and delete[]-d by ~Image (codecs.h:102); load() adopts a buffer.
  * Every other extension is outside this path: it throws std::invalid_argument exactly like the
  * reference's unknown-extension branch (codecs.cpp:80-83), so a build that needs those codecs
@@ -239,6 +243,25 @@ class Image {
         last_write_ok_ = icx_png_save_to_file(P.get(), path.c_str(), pixels_, w_, h_, d_) == ICX_OK;
     }
 
+    // writeExr (codecs.cpp:495-505): SaveEXR(float*, w, h, d, fp16 = false, path). As in the
+    // reference, type_ is not consulted (pixels_ is read as w*h*d floats) and nothing is thrown:
+    // a failure -- no usable GPU included -- only prints the message; the result stays queryable.
+    void writeExr(const std::string& path) {
+        auto& P = detail::icx_process();
+        std::lock_guard<std::mutex> lock(P.mu);
+        last_write_ok_ = false;
+        icx_ctx* c = nullptr;
+        try {
+            c = P.get();
+        } catch (const std::runtime_error& e) {
+            std::fprintf(stderr, "%s\n", e.what());
+            return;
+        }
+        const int rc = icx_exr_save_to_file(c, path.c_str(), reinterpret_cast<const float*>(pixels_), w_, h_, d_, 0);
+        last_write_ok_ = rc == ICX_EXR_SUCCESS;
+        if (!last_write_ok_) std::fprintf(stderr, "icx_exr_save_to_file -> %d %s\n", rc, icx_last_error(c));
+    }
+
 public:
     Image() = default;
     Image(const Image&) = delete;  // the reference's implicit copy double-frees pixels_
@@ -308,6 +331,7 @@ public:
         const std::string ext = detail::lower_ext(filepath);
         if (ext == ".jpg" || ext == ".jpeg") writeJpg(filepath);
         else if (ext == ".png") writePng(filepath);
+        else if (ext == ".exr") writeExr(filepath);
         else throw std::invalid_argument("Cannot parse filetype");
     }
 };
