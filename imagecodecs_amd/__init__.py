@@ -15,7 +15,9 @@ callers (tests, bench): it binds the C ABI with ctypes and offers
   * ``PngBatch``                  -- device-resident batched PNG decode
   * ``Context.exr_decode``        -- Image::readExr's OpenEXR -> RGBA float (tinyexr LoadEXRFromMemory)
   * ``Context.exr_encode``        -- Image::writeExr's float pixels -> OpenEXR (tinyexr SaveEXR)
-  * ``Image``                     -- ImageCodecs::Image (codecs.h:16-103) for .jpg/.jpeg/.png/.hdr
+  * ``Context.tga_decode`` / ``tga_encode`` -- Image::readTga / writeTga (codecs.cpp:1304-1437), RLE included
+  * ``TgaBatch``                  -- device-resident batched .tga decode
+  * ``Image``                     -- ImageCodecs::Image (codecs.h:16-103) for .jpg/.jpeg/.png/.hdr/.exr/.tga
 
 There is deliberately no CPU fallback: if libicx.so is missing or no GPU is visible every
 entry point raises ``ICXError``.
@@ -34,7 +36,9 @@ __all__ = ["ICXError", "Context", "Batch", "HdrBatch", "Image", "lib", "build", 
            "HDR_TOO_LARGE", "HDR_INTERNAL_ERR", "hdr_probe", "exr_probe",
            "PngBatch", "png_probe", "PNGR_OK", "PNGR_NOT_PNG", "PNGR_BAD_HEADER", "PNGR_UNSUPPORTED", "PNGR_MALFORMED",
            "PNGR_BAD_DATA", "PNGR_TOO_LARGE", "PNGR_INTERNAL_ERR", "EXR_SUCCESS", "EXR_INVALID_DATA", "Multi", "RECORD_DTYPE", "records_device",
-           "checksum64", "multi_shard"]
+           "checksum64", "multi_shard", "TgaBatch", "tga_probe", "tga_encode_bound", "TGA_OK", "TGA_BAD_HEADER",
+           "TGA_UNSUPPORTED", "TGA_NO_IMAGE", "TGA_MALFORMED", "TGA_TRUNCATED", "TGA_TOO_LARGE", "TGA_INVALID_ARGUMENT",
+           "TGA_INTERNAL_ERR"]
 
 OK, NO_JPEG, UNSUPPORTED, OUT_OF_MEM, INTERNAL_ERR, SYNTAX_ERROR = range(6)  # nj_result_t
 RESULT_NAMES = ["NJ_OK", "NJ_NO_JPEG", "NJ_UNSUPPORTED", "NJ_OUT_OF_MEM", "NJ_INTERNAL_ERR", "NJ_SYNTAX_ERROR"]
@@ -129,6 +133,16 @@ _SIGS = {
     "icx_exr_encode_bound": (_sz, [_i32, _i32, _i32, _i32]),
     "icx_exr_encode_device": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _sz, C.POINTER(_sz)]),
     "icx_exr_encode_device_batch": (_i32, [_vp, _i32, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "icx_tga_probe": (_i32, [_vp, _sz, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32)]),
+    "icx_tga_decode": (_i32, [_vp, _vp, _sz, C.POINTER(_vp), C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32)]),
+    "icx_tga_batch_create": (_vp, [_vp, _i32, _i32, _i32]),
+    "icx_tga_batch_destroy": (None, [_vp]),
+    "icx_tga_batch_decode": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _vp]),
+    "icx_tga_batch_stage_times": (_i32, [_vp, _vp, _vp, _i32]),
+    "icx_tga_encode_bound": (_sz, [_i32, _i32, _i32]),
+    "icx_tga_save_to_memory": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, C.POINTER(_vp), C.POINTER(_sz)]),
+    "icx_tga_save_to_file": (_i32, [_vp, C.c_char_p, _vp, _i32, _i32, _i32, _i32]),
+    "icx_tga_encode_device_batch": (_i32, [_vp, _i32, _vp, _vp, _vp, _i32, _i32, _vp, _u64, _vp, _vp, _vp]),
 }
 
 # icx_record (include/icx.h): per-image result record gathered across devices / ranks
@@ -146,6 +160,11 @@ PNGR_INTERNAL_ERR = -1
 # icx_exr_result (include/icx.h): tinyexr's LoadEXRFromMemory codes
 EXR_SUCCESS, EXR_INVALID_MAGIC_NUMBER, EXR_INVALID_EXR_VERSION, EXR_INVALID_ARGUMENT, EXR_INVALID_DATA = 0, -1, -2, -3, -4
 EXR_UNSUPPORTED_FORMAT, EXR_INVALID_HEADER, EXR_UNSUPPORTED_FEATURE, EXR_INTERNAL_ERR = -8, -9, -10, -100
+
+# icx_tga_result (include/icx.h): Image::readTga / writeTga outcomes
+(TGA_OK, TGA_BAD_HEADER, TGA_UNSUPPORTED, TGA_NO_IMAGE, TGA_MALFORMED, TGA_TRUNCATED, TGA_TOO_LARGE,
+ TGA_INVALID_ARGUMENT) = range(8)
+TGA_INTERNAL_ERR = -1
 
 WRITE_FUNC = C.CFUNCTYPE(None, C.c_void_p, C.c_void_p, C.c_int)
 
@@ -402,6 +421,56 @@ class Context:
         if rc != 0:
             raise ICXError(f"icx_exr_encode_device_batch: code {rc}")
         return codes, np.array(list(sizes), np.uint64)
+
+    def tga_decode(self, data: bytes):
+        """Image::readTga (codecs.cpp:1304-1407; contract in include/icx.h) on the GPU -> (code, w, h,
+        channels, uint8 (h, w, channels) or None); code is an icx_tga_result."""
+        buf = C.create_string_buffer(bytes(data), max(1, len(data)))
+        out = C.c_void_p()
+        w, h, d = C.c_int(), C.c_int(), C.c_int()
+        code = lib().icx_tga_decode(self._p, buf, len(data), C.byref(out), C.byref(w), C.byref(h), C.byref(d))
+        if code == TGA_INTERNAL_ERR:
+            raise ICXError("icx_tga_decode: " + _err(self._p))
+        arr = None
+        if out.value:
+            n = w.value * h.value * d.value
+            arr = np.frombuffer(C.string_at(out.value, n), np.uint8).reshape(h.value, w.value, d.value).copy()
+            lib().icx_free(out)
+        return code, w.value, h.value, d.value, arr
+
+    def tga_encode(self, px, rle: bool = False):
+        """Image::writeTga (codecs.cpp:1410-1437) on the GPU: uint8 (h, w) or (h, w, d), d in 1, 3, 4,
+        rows top-down -> (code, the file's bytes or None). rle: the run-length coded extension."""
+        a = np.ascontiguousarray(px, np.uint8)
+        if a.ndim == 2:
+            a = a[:, :, None]
+        if a.ndim != 3:
+            return TGA_INVALID_ARGUMENT, None
+        h, w, d = a.shape
+        out, size = C.c_void_p(), C.c_size_t()
+        code = lib().icx_tga_save_to_memory(self._p, a.ctypes.data if a.size else None, w, h, d, 1 if rle else 0,
+                                            C.byref(out), C.byref(size))
+        if code == TGA_INTERNAL_ERR:
+            raise ICXError("icx_tga_save_to_memory: " + _err(self._p))
+        if code != TGA_OK:
+            return code, None
+        data = C.string_at(out.value, size.value)
+        lib().icx_free(out)
+        return code, data
+
+    def tga_encode_device_batch(self, d_srcs, widths, heights, d: int, rle: bool, d_out: int, out_stride: int,
+                                d_sizes: int, d_status: int, stream=0) -> int:
+        """icx_tga_encode_device_batch: image i's pixels at device address d_srcs[i], its file to
+        d_out + i*out_stride, size (uint64) and status (int32) to the device arrays -> the call's code."""
+        n = len(d_srcs)
+        sp = (C.c_void_p * max(1, n))(*d_srcs)
+        ws = np.ascontiguousarray(widths, np.int32)
+        hs = np.ascontiguousarray(heights, np.int32)
+        rc = lib().icx_tga_encode_device_batch(self._p, n, sp, ws.ctypes.data, hs.ctypes.data, d, 1 if rle else 0, d_out,
+                                               out_stride, d_sizes, d_status, stream or None)
+        if rc == TGA_INTERNAL_ERR:
+            raise ICXError("icx_tga_encode_device_batch: " + _err(self._p))
+        return rc
 
     def png_encode(self, width: int, height: int, d: int, src: bytes):
         """PNG bytes of an RGB8 (d=3) / RGBA8 (d=4) image (png_encoder::saveToFile), or None."""
@@ -690,6 +759,19 @@ def exr_probe(data: bytes):
     return code, w.value, h.value
 
 
+def tga_probe(data: bytes):
+    """Host header walk of the Targa read -> (code, width, height, channels)."""
+    w, h, d = C.c_int(), C.c_int(), C.c_int()
+    buf = C.create_string_buffer(bytes(data), max(1, len(data)))
+    code = lib().icx_tga_probe(buf, len(data), C.byref(w), C.byref(h), C.byref(d))
+    return code, w.value, h.value, d.value
+
+
+def tga_encode_bound(width: int, height: int, d: int) -> int:
+    """icx_tga_encode_bound: 18 + w*h*(d+1), or 0 for arguments the write refuses."""
+    return int(lib().icx_tga_encode_bound(width, height, d))
+
+
 def png_probe(data: bytes):
     """Host chunk walk of the PNG read (signature, IHDR, PLTE / tRNS, IDAT present) -> (code, width, height)."""
     w, h = C.c_int(), C.c_int()
@@ -731,6 +813,39 @@ class PngBatch:
         return {names[i].decode(): float(ms[i]) for i in range(k)}
 
 
+class TgaBatch:
+    """Device-resident batched Targa decode (icx_tga_batch_*): image i is
+    d_data[d_offsets[i] .. + d_sizes[i]); its bytes at d_out + i*out_stride, status in d_status[i],
+    {width, height, channels} in d_dims[3i..]."""
+
+    def __init__(self, ctx: Context, max_images: int, max_width: int, max_height: int):
+        self.ctx = ctx
+        self._p = lib().icx_tga_batch_create(ctx.ptr, max_images, max_width, max_height)
+        if not self._p:
+            raise ICXError("icx_tga_batch_create failed: " + _err(ctx.ptr))
+        self.max_images, self.max_width, self.max_height = max_images, max_width, max_height
+
+    def close(self):
+        if getattr(self, "_p", None):
+            lib().icx_tga_batch_destroy(self._p)
+            self._p = None
+
+    def __del__(self):
+        self.close()
+
+    def decode_device(self, n, d_data, d_offsets, d_sizes, d_out, out_stride, d_status, d_dims, stream=0):
+        rc = lib().icx_tga_batch_decode(self._p, n, d_data, d_offsets, d_sizes, d_out, out_stride,
+                                        d_status, d_dims, stream or None)
+        if rc != TGA_OK:
+            raise ICXError(f"icx_tga_batch_decode -> {rc}: {_err(self.ctx.ptr)}")
+
+    def stage_times(self) -> dict:
+        names = (C.c_char_p * 8)()
+        ms = (C.c_float * 8)()
+        k = lib().icx_tga_batch_stage_times(self._p, names, ms, 8)
+        return {names[i].decode(): float(ms[i]) for i in range(k)}
+
+
 class HdrBatch:
     """Device-resident batched Radiance .hdr decode (icx_hdr_batch_*): image i is
     d_data[d_offsets[i] .. + d_sizes[i]); 4 floats per pixel at d_out + i*out_stride floats."""
@@ -768,7 +883,8 @@ class Image:
 
     read()/write() dispatch on the lower-cased extension like Image::read/write
     (codecs.cpp:53-122): read .jpg/.jpeg (readJpg), .png (readPng: d = 4, type UBYTE) and .hdr
-    (readHdr: d = 4, type FLOAT, the floats' bytes in pixels_) and .exr, write .jpg/.jpeg, .png and .exr. Other extensions raise ValueError (the
+    (readHdr: d = 4, type FLOAT, the floats' bytes in pixels_), .exr and .tga (readTga: d = 1, 3 or
+    4, type UBYTE), write .jpg/.jpeg, .png, .exr and .tga (uncompressed). Other extensions raise ValueError (the
     reference's std::invalid_argument for unknown types)."""
 
     UBYTE, USHORT, FLOAT = range(3)  # ImageCodecs::Type (codecs.h:14)
@@ -795,6 +911,9 @@ class Image:
             return
         if ext == ".png":
             self._read_png(filepath)
+            return
+        if ext == ".tga":
+            self._read_tga(filepath)
             return
         if ext not in (".jpg", ".jpeg"):
             raise ValueError("Cannot parse filetype")
@@ -830,6 +949,17 @@ class Image:
         self.pixels_ = px.reshape(-1).copy()
         self.type_ = Image.UBYTE
 
+    def _read_tga(self, filepath: str):
+        """readTga (codecs.cpp:1304-1407): d = 1, 3 or 4, type UBYTE, rows top-down. Every failure is
+        Image::read's RuntimeError("Could not read image data") (:85-88: pixels_ stays null)."""
+        data = open(filepath, "rb").read()
+        code, w, h, d, px = self.context().tga_decode(data)
+        if code != TGA_OK:
+            raise RuntimeError("Could not read image data")
+        self.w_, self.h_, self.d_ = w, h, d
+        self.pixels_ = px.reshape(-1).copy()
+        self.type_ = Image.UBYTE
+
     def _read_exr(self, filepath: str):
         """readExr (codecs.cpp:464-493): LoadEXRFromMemory -> d = 4, type FLOAT, the floats' bytes in
         pixels_; a failure raises RuntimeError("Could not load .exr") (:489). (The reference reads
@@ -854,6 +984,14 @@ class Image:
                 px = np.frombuffer(self.pixels_.tobytes(), np.float32, self.w_ * self.h_ * self.d_)
                 out = self.context().exr_encode(px.reshape(self.h_, self.w_, self.d_))
             except (ICXError, ValueError):
+                return
+        elif ext == ".tga":  # writeTga (codecs.cpp:1410-1437): uncompressed; nothing is thrown on failure
+            try:
+                px = np.frombuffer(self.pixels_.tobytes(), np.uint8, self.w_ * self.h_ * self.d_)
+                code, out = self.context().tga_encode(px.reshape(self.h_, self.w_, self.d_))
+            except (ICXError, ValueError, AttributeError):
+                return
+            if code != TGA_OK:
                 return
         else:
             raise ValueError("Cannot parse filetype")

@@ -19,6 +19,7 @@
 #include "icx_internal.h"
 #include "icx_mem.h"
 #include "icx_step.h"
+#include "icx_tga_core.h"
 
 using namespace icx;
 
@@ -32,6 +33,7 @@ struct icx_ctx {
     icx_batch* single = nullptr;  // cached workspace for one-image calls
     ExrWs* exr = nullptr;  // grow-only EXR read buffers (icx_exr.hip)
     ExrwWs* exrw = nullptr;  // grow-only EXR write buffers (icx_exrw.hip)
+    TgawWs* tgaw = nullptr;  // grow-only Targa write buffers (icx_tga.hip)
 };
 
 struct EventHook;
@@ -172,6 +174,7 @@ void icx_destroy(icx_ctx* c) {
     if (c->single) icx_batch_destroy(c->single);
     if (c->exr) exr_ws_destroy(c->exr);
     if (c->exrw) exrw_ws_destroy(c->exrw);
+    if (c->tgaw) tgaw_ws_destroy(c->tgaw);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
 }
@@ -1299,6 +1302,218 @@ int icx_exr_save_to_file(icx_ctx* ctx, const char* path, const float* data, int 
         return ICX_EXR_INTERNAL_ERR;
     }
     return ICX_EXR_SUCCESS;
+}
+
+// --------------------------------------------------------- Targa (Image::readTga / writeTga)
+struct icx_tga_batch {
+    icx_ctx* ctx = nullptr;
+    TgaWs ws;
+    Blocks mem;  // the device memory ws points into
+    std::unique_ptr<EventHook> hook;
+};
+
+int icx_tga_probe(const uint8_t* data, size_t size, int* w, int* h, int* channels) {
+    int ww = 0, hh = 0, dd = 0;
+    const int rc = data ? tga_probe(data, (int64_t)size, &ww, &hh, &dd) : ICX_TGA_BAD_HEADER;
+    if (w) *w = rc == ICX_TGA_OK ? ww : 0;
+    if (h) *h = rc == ICX_TGA_OK ? hh : 0;
+    if (channels) *channels = rc == ICX_TGA_OK ? dd : 0;
+    return rc;
+}
+
+// rle false: a workspace for raw files only (no tile tables, no RLE kernels launched).
+static icx_tga_batch* tga_batch_new(icx_ctx* ctx, int max_images, int max_w, int max_h, bool rle) {
+    // (images are one grid dimension; pixel indices are 32-bit in the tile tables)
+    if (!ctx || max_images <= 0 || max_images > 65535 || max_w <= 0 || max_h <= 0 || max_w > 65535 || max_h > 65535 ||
+        (int64_t)max_w * max_h > ((int64_t)1 << 30)) {
+        if (ctx) ctx->err = "icx_tga_batch_create: bad arguments";
+        return nullptr;
+    }
+    ICX_HIP(ctx, hipSetDevice(ctx->device), nullptr);
+    auto* b = new icx_tga_batch();
+    b->ctx = ctx;
+    b->hook = std::make_unique<EventHook>();
+    if (!tga_ws_alloc(b->ws, b->mem, max_images, max_w, max_h, rle)) {
+        ctx->err = std::string("icx_tga_batch_create: out of device memory: ") + hipGetErrorString(hipGetLastError());
+        delete b;
+        return nullptr;
+    }
+    return b;
+}
+
+icx_tga_batch* icx_tga_batch_create(icx_ctx* ctx, int max_images, int max_w, int max_h) {
+    return tga_batch_new(ctx, max_images, max_w, max_h, true);
+}
+
+void icx_tga_batch_destroy(icx_tga_batch* b) {
+    if (!b) return;
+    (void)hipSetDevice(b->ctx->device);
+    delete b;
+}
+
+int icx_tga_batch_decode(icx_tga_batch* b, int n, const uint8_t* d_data, const uint64_t* d_off, const uint64_t* d_size,
+                         uint8_t* d_out, uint64_t out_stride, int32_t* d_status, int32_t* d_dims, void* stream) {
+    if (!b) return ICX_TGA_INTERNAL_ERR;
+    icx_ctx* ctx = b->ctx;
+    if (n < 0 || n > b->ws.max_images) { ctx->err = "icx_tga_batch_decode: n exceeds batch capacity"; return ICX_TGA_INTERNAL_ERR; }
+    if (n == 0) return ICX_TGA_OK;
+    if (!d_data || !d_off || !d_size || !d_out || !d_status || !d_dims) { ctx->err = "null pointer"; return ICX_TGA_INTERNAL_ERR; }
+    if (out_stride < 4ull * b->ws.max_w * b->ws.max_h) { ctx->err = "icx_tga_batch_decode: out_stride too small"; return ICX_TGA_INTERNAL_ERR; }
+    ICX_HIP(ctx, hipSetDevice(ctx->device), ICX_TGA_INTERNAL_ERR);
+    hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
+    const RoctxRange range("icx_tga_batch_decode");
+    b->hook->reset();
+    launch_tga_decode(b->ws, n, d_data, d_off, d_size, d_out, out_stride, d_status, d_dims, st, b->hook.get());
+    ICX_HIP(ctx, hipGetLastError(), ICX_TGA_INTERNAL_ERR);
+    return ICX_TGA_OK;
+}
+
+int icx_tga_batch_stage_times(const icx_tga_batch* b, const char** names, float* ms, int cap) {
+    if (!b) return 0;
+    static const Stage order[4] = {kStParse, kStUnstuff, kStEntropy, kStConvert};
+    static const char* const label[4] = {"parse", "locate", "expand", "raw"};
+    float acc[kStCount];
+    b->hook->sum(acc);
+    for (int k = 0; k < 4 && k < cap; ++k) {
+        if (names) names[k] = label[k];
+        if (ms) ms[k] = acc[order[k]];
+    }
+    return 4;
+}
+
+int icx_tga_decode(icx_ctx* ctx, const uint8_t* data, size_t size, uint8_t** out, int* w, int* h, int* channels) {
+    if (out) *out = nullptr;
+    if (w) *w = 0;
+    if (h) *h = 0;
+    if (channels) *channels = 0;
+    if (!ctx || !out) return ICX_TGA_INTERNAL_ERR;
+    int ww = 0, hh = 0, dd = 0;
+    const int prc = icx_tga_probe(data, size, &ww, &hh, &dd);
+    if (prc != ICX_TGA_OK) return prc;  // header errors need no device work
+    if ((int64_t)ww * hh > ((int64_t)1 << 30)) return ICX_TGA_TOO_LARGE;  // (no batch workspace is that large)
+    ICX_HIP(ctx, hipSetDevice(ctx->device), ICX_TGA_INTERNAL_ERR);
+    // (declared before the buffers: they are freed first, then the batch)
+    // (the probe accepted the header: byte 2 is the image type, 9-11 run-length coded; a raw file
+    // needs no tile tables, and the one slot holds just the image's w*h*d bytes)
+    std::unique_ptr<icx_tga_batch, void (*)(icx_tga_batch*)> b(tga_batch_new(ctx, 1, ww, hh, data[2] >= 9), icx_tga_batch_destroy);
+    if (!b) return ICX_TGA_INTERNAL_ERR;
+    const uint64_t nout = (uint64_t)ww * hh * dd, stride = nout;
+    Buf<uint8_t> d_in, d_out;
+    Buf<uint64_t> d_meta;
+    Buf<int32_t> d_res;
+    int rc = ICX_TGA_INTERNAL_ERR;
+    const uint64_t meta[2] = {0, (uint64_t)size};
+    int32_t res[4] = {0, 0, 0, 0};
+    hipStream_t st = ctx->stream;
+    if (d_in.reserve(size) && d_out.reserve(stride) && d_meta.reserve(16) && d_res.reserve(16) &&
+        hipMemcpyAsync(d_in.p, data, size, hipMemcpyHostToDevice, st) == hipSuccess &&
+        hipMemcpyAsync(d_meta.p, meta, 16, hipMemcpyHostToDevice, st) == hipSuccess &&
+        (launch_tga_decode(b->ws, 1, d_in.p, d_meta.p, d_meta.p + 1, d_out.p, stride, d_res.p, d_res.p + 1, st, nullptr),
+         hipGetLastError() == hipSuccess) &&
+        hipMemcpyAsync(res, d_res.p, 16, hipMemcpyDeviceToHost, st) == hipSuccess && hipStreamSynchronize(st) == hipSuccess) {
+        rc = res[0];
+        if (rc == ICX_TGA_OK) {
+            uint8_t* hostp = (uint8_t*)std::malloc(nout);
+            if (hostp && hipMemcpy(hostp, d_out.p, nout, hipMemcpyDeviceToHost) == hipSuccess) {
+                *out = hostp;
+                if (w) *w = res[1];
+                if (h) *h = res[2];
+                if (channels) *channels = res[3];
+            } else {
+                std::free(hostp);
+                ctx->err = "icx_tga_decode: host allocation or copy failed";
+                rc = ICX_TGA_INTERNAL_ERR;
+            }
+        }
+    } else if (ctx->err.empty()) {
+        ctx->err = "icx_tga_decode: HIP failure";
+    }
+    return rc;
+}
+
+size_t icx_tga_encode_bound(int width, int height, int d) { return (size_t)tga_encode_bound(width, height, d); }
+
+int icx_tga_encode_device_batch(icx_ctx* ctx, int n, const uint8_t* const* d_src, const int32_t* widths,
+                                const int32_t* heights, int d, int rle, uint8_t* d_out, uint64_t out_stride,
+                                uint64_t* d_sizes, int32_t* d_status, void* stream) {
+    if (!ctx) return ICX_TGA_INTERNAL_ERR;
+    if (n < 0 || n > 65535 || (d != 1 && d != 3 && d != 4) ||
+        (n > 0 && (!d_src || !widths || !heights || !d_out || !d_sizes || !d_status)))
+        return ICX_TGA_INVALID_ARGUMENT;
+    if (n == 0) return ICX_TGA_OK;
+    ICX_HIP(ctx, hipSetDevice(ctx->device), ICX_TGA_INTERNAL_ERR);
+    const RoctxRange range("icx_tga_encode_device_batch");
+    std::string err;
+    int rc;
+    try {  // (nothing may cross the C ABI: a host allocation failure is an internal error)
+        if (!ctx->tgaw) ctx->tgaw = tgaw_ws_create();
+        rc = tga_encode_batch(stream ? (hipStream_t)stream : ctx->stream, *ctx->tgaw, n, d_src, widths, heights, d,
+                              rle != 0, d_out, out_stride, d_sizes, d_status, err);
+    } catch (const std::exception& e) {
+        err = std::string("icx_tga_encode_device_batch: ") + e.what();
+        rc = -1;
+    }
+    if (rc != 0) {
+        ctx->err = err.empty() ? "icx_tga_encode_device_batch: HIP failure" : err;
+        return ICX_TGA_INTERNAL_ERR;
+    }
+    return ICX_TGA_OK;
+}
+
+int icx_tga_save_to_memory(icx_ctx* ctx, const uint8_t* pixels, int width, int height, int d, int rle, uint8_t** out,
+                           size_t* size) {
+    if (out) *out = nullptr;
+    if (size) *size = 0;
+    if (!ctx) return ICX_TGA_INTERNAL_ERR;
+    const uint64_t bound = tga_encode_bound(width, height, d);
+    if (!pixels || !out || !size || bound == 0) return ICX_TGA_INVALID_ARGUMENT;
+    ICX_HIP(ctx, hipSetDevice(ctx->device), ICX_TGA_INTERNAL_ERR);
+    const uint64_t npx = (uint64_t)width * height * d;
+    Buf<uint8_t> d_px, d_file;
+    Buf<uint64_t> d_res;  // the file's size, then its status
+    uint64_t res[2] = {0, 0};
+    hipStream_t st = ctx->stream;
+    if (!(d_px.reserve(npx) && d_file.reserve(bound) && d_res.reserve(16) &&
+          hipMemcpyAsync(d_px.p, pixels, npx, hipMemcpyHostToDevice, st) == hipSuccess)) {
+        ctx->err = std::string("icx_tga_save_to_memory: ") + hipGetErrorString(hipGetLastError());
+        return ICX_TGA_INTERNAL_ERR;
+    }
+    const uint8_t* src = d_px.p;
+    const int32_t w = width, h = height;
+    const int rc = icx_tga_encode_device_batch(ctx, 1, &src, &w, &h, d, rle, d_file.p, bound, d_res.p,
+                                               reinterpret_cast<int32_t*>(d_res.p + 1), st);
+    if (rc != ICX_TGA_OK) return rc;
+    ICX_HIP(ctx, hipMemcpy(res, d_res.p, 16, hipMemcpyDeviceToHost), ICX_TGA_INTERNAL_ERR);
+    const int code = (int32_t)(res[1] & 0xFFFFFFFFu);
+    if (code != ICX_TGA_OK) return code;
+    uint8_t* hostp = (uint8_t*)std::malloc(res[0]);
+    if (!hostp || hipMemcpy(hostp, d_file.p, res[0], hipMemcpyDeviceToHost) != hipSuccess) {
+        std::free(hostp);
+        (void)hipGetLastError();
+        ctx->err = "icx_tga_save_to_memory: host allocation or copy failed";
+        return ICX_TGA_INTERNAL_ERR;
+    }
+    *out = hostp;
+    *size = (size_t)res[0];
+    return ICX_TGA_OK;
+}
+
+int icx_tga_save_to_file(icx_ctx* ctx, const char* path, const uint8_t* pixels, int width, int height, int d, int rle) {
+    if (!ctx) return ICX_TGA_INTERNAL_ERR;
+    if (!path) return ICX_TGA_INVALID_ARGUMENT;
+    uint8_t* mem = nullptr;
+    size_t size = 0;
+    const int rc = icx_tga_save_to_memory(ctx, pixels, width, height, d, rle, &mem, &size);
+    if (rc != ICX_TGA_OK) return rc;
+    std::FILE* f = std::fopen(path, "wb");
+    const bool ok = f && std::fwrite(mem, 1, size, f) == size;
+    const bool closed = f && std::fclose(f) == 0;
+    std::free(mem);
+    if (!ok || !closed) {
+        ctx->err = std::string("icx_tga_save_to_file: cannot write ") + path;
+        return ICX_TGA_INTERNAL_ERR;
+    }
+    return ICX_TGA_OK;
 }
 
 }  // extern "C"

@@ -337,6 +337,31 @@ void launch_pngd_decode(const PngdWs& ws, int n, const uint8_t* d_data, const ui
                         uint8_t* d_out, uint64_t out_stride, int32_t* d_status, int32_t* d_dims, hipStream_t st,
                         StageHook* hook);
 
+// Targa read and write (icx_tga.hip; Image::readTga / writeTga, codecs.cpp:1304-1437). Status
+// codes: icx_tga_core.h kTga* = include/icx.h ICX_TGA_*.
+struct TgaDesc;
+struct TgaWs {
+    int max_images = 0, max_w = 0, max_h = 0;
+    int64_t tiles_cap = 0;        // stream tiles per image (any stream of max_w x max_h pixels); 0: a
+                                  // workspace for raw files only (an RLE file is TOO_LARGE there)
+    TgaDesc* desc = nullptr;      // [max_images]
+    uint32_t* summary = nullptr;  // [max_images][tiles_cap][kTgaEntries] chain summaries (k_tga_tiles)
+    int32_t* entry = nullptr;     // [max_images][tiles_cap] offset of the tile's first packet (k_tga_chain)
+    int32_t* pbase = nullptr;     // [max_images][tiles_cap] pixels decoded before it
+};
+int tga_probe(const uint8_t* data, int64_t size, int* w, int* h, int* d);
+bool tga_ws_alloc(TgaWs& ws, Blocks& mem, int max_images, int max_w, int max_h, bool rle = true);
+void launch_tga_decode(const TgaWs& ws, int n, const uint8_t* d_data, const uint64_t* d_off, const uint64_t* d_size,
+                       uint8_t* d_out, uint64_t out_stride, int32_t* d_status, int32_t* d_dims, hipStream_t st,
+                       StageHook* hook);
+struct TgawWs;  // grow-only buffers of the write
+TgawWs* tgaw_ws_create();
+void tgaw_ws_destroy(TgawWs* w);
+// 0, or -1 for a HIP failure (err says which). Synchronises with `st`.
+int tga_encode_batch(hipStream_t st, TgawWs& ws, int n, const uint8_t* const* d_src, const int32_t* widths,
+                     const int32_t* heights, int d, int rle, uint8_t* d_out, uint64_t out_stride, uint64_t* d_sizes,
+                     int32_t* d_status, std::string& err);
+
 // ---- OpenEXR read (icx_exr.hip) ----
 // tinyexr's LoadEXRFromMemory; returns its code (-100: HIP failure, err says which).
 struct ExrWs;

@@ -407,6 +407,96 @@ int icx_exr_encode_device_batch(icx_ctx* ctx, int n, const float* const* d_src, 
                                 const int32_t* heights, int components, int save_as_fp16, uint8_t* const* d_out,
                                 const size_t* caps, int32_t* codes, size_t* sizes);
 
+/* ---- Targa read (Image::readTga, codecs.cpp:1304-1407) -------------------------------------------
+ * Output as readTga returns it: Type::UBYTE, rows top-down, channels R,G,B(,A); channels is 3 or 4
+ * for colour (the map's entry size for paletted files, bits / 8 otherwise) and 1 for monochrome.
+ * Accepted: types 2 / 10 (true colour raw / RLE) at 24 or 32 bits, file order B,G,R(,A), alpha as
+ * stored; types 3 / 11 (monochrome) at 8 bits; types 1 / 9 (paletted; colour-map type 1) with map
+ * entries of 24 or 32 bits and indices of 8 or 16 bits. Type 9 is decoded (the reference leaves
+ * it as a TODO and returns zeros).
+ * Deliberate deviations: the header is 18 bytes (the reference subtracts a padded
+ * sizeof(Header) of 20 and reads two bytes too few); the ID field is *ID length* bytes (the
+ * reference skips *descriptor* bytes); palette index i selects entry i - origin, and an index
+ * outside the map gives zero bytes (the reference reads outside its buffer); descriptor bit 5
+ * (top-left origin) is honoured, so the output is always top-down (the reference always flips);
+ * bit 4 (right-to-left) is UNSUPPORTED; run-length packets may cross row ends, as in the
+ * reference; bytes after the image data (footer, extension area) are ignored.
+ * Packets are examined in stream order and the first that fails decides: its header byte or
+ * payload not wholly inside the file -> TRUNCATED, otherwise more pixels than are still missing ->
+ * MALFORMED (the reference writes past its buffer). Raw data or a colour map that run past the
+ * file are TRUNCATED. A failed image yields no pixels. */
+enum icx_tga_result {
+    ICX_TGA_OK = 0,
+    ICX_TGA_BAD_HEADER = 1,        /* < 18 bytes, zero width / height, colour-map type > 1, a paletted
+                                      type without a map, an image type not in 0-3, 9-11            */
+    ICX_TGA_UNSUPPORTED = 2,       /* 15/16-bit colour, map entries or monochrome, any other depth,
+                                      descriptor bit 4                                              */
+    ICX_TGA_NO_IMAGE = 3,          /* type 0: the reference leaves pixels_ null                      */
+    ICX_TGA_MALFORMED = 4,         /* a packet holds more pixels than are still missing             */
+    ICX_TGA_TRUNCATED = 5,         /* the file ends first                                           */
+    ICX_TGA_TOO_LARGE = 6,         /* larger than the batch workspace / the output slot             */
+    ICX_TGA_INVALID_ARGUMENT = 7,  /* write: channels not 1, 3, 4; width / height not 1..65535; null */
+    ICX_TGA_INTERNAL_ERR = -1      /* HIP failure (see icx_last_error)                              */
+};
+/* Header only (host): size and channels, or the code the header (for raw types: and the file's
+ * length) gives. The packets of an RLE file are checked by the decode. */
+int icx_tga_probe(const uint8_t* data, size_t size, int* width, int* height, int* channels);
+/* One image, host in / host out: *out receives a malloc()'d width*height*channels byte buffer
+ * (free with icx_free), null unless ICX_TGA_OK. A code the probe gives returns without touching
+ * the GPU; an image of more than 2^30 pixels is ICX_TGA_TOO_LARGE (a batch workspace holds
+ * max_width * max_height <= 2^30). The header checks run in the order BAD_HEADER, NO_IMAGE,
+ * UNSUPPORTED, TRUNCATED (ID field, colour map, raw data). */
+int icx_tga_decode(icx_ctx* ctx, const uint8_t* data, size_t size, uint8_t** out, int* width, int* height,
+                   int* channels);
+/* Device-resident batch: image i = d_data[d_offsets[i] .. + d_sizes[i]), output bytes at
+ * d_out + i*out_stride (out_stride >= 4*max_width*max_height), per-image status in d_status[i]
+ * and {width, height, channels} in d_dims[3i..] (zero for a failed image, whose slot is
+ * unspecified). Asynchronous on hip_stream (NULL = the context's stream), no host read-back.
+ * Returns ICX_TGA_OK or ICX_TGA_INTERNAL_ERR. */
+typedef struct icx_tga_batch icx_tga_batch;
+icx_tga_batch* icx_tga_batch_create(icx_ctx* ctx, int max_images, int max_width, int max_height);
+void icx_tga_batch_destroy(icx_tga_batch* b);
+int icx_tga_batch_decode(icx_tga_batch* b, int n, const uint8_t* d_data, const uint64_t* d_offsets,
+                         const uint64_t* d_sizes, uint8_t* d_out, uint64_t out_stride, int32_t* d_status,
+                         int32_t* d_dims, void* hip_stream);
+/* Milliseconds per stage of the last icx_tga_batch_decode ("parse", "locate", "expand", "raw";
+ * synchronises). Returns the number of stages. */
+int icx_tga_batch_stage_times(const icx_tga_batch* b, const char** names, float* ms, int cap);
+
+/* ---- Targa write (Image::writeTga, codecs.cpp:1410-1437) -----------------------------------------
+ * `pixels`: width*height*d bytes, rows top-down, R,G,B(,A) or one grey byte; d = 1, 3 or 4.
+ * The reference's 18 header bytes (0,0,2,0...0, w, h, d*8, 0x20) and the rows top-down.
+ * Two deviations, by evident intent: the payload is B,G,R(,A) (the reference stores R,G,B, which
+ * every TGA reader, its own included, shows with red and blue exchanged), and d = 1 is written as
+ * image type 3 (the reference writes type 2 with 8 bits, which is not a TGA form).
+ * Extension (rle != 0): type 10 (d = 3, 4) or 11 (d = 1); packets never cross a row; each row is
+ * packed by this greedy rule (serial as stated; the kernels give the same bytes):
+ *     i = 0
+ *     while i < w:
+ *         r = length of the longest stretch p[i..i+r) of equal pixels, r <= min(128, w - i)
+ *         if r >= 2:  emit 0x80 | (r-1), one pixel;             i += r
+ *         else:       n = number of pixels k = i, i+1, ... taken while k < w, k - i < 128 and
+ *                         not (k+1 < w and p[k] == p[k+1])
+ *                     emit n-1, n pixels;                        i += n
+ * Any other d, width or height outside 1..65535, or a null pointer -> ICX_TGA_INVALID_ARGUMENT. */
+/* The largest file a write can give, 18 + w*h*(d+1); 0 for arguments the writes refuse. Host only. */
+size_t icx_tga_encode_bound(int width, int height, int d);
+/* Host pixels in, *out receives the malloc()'d file (free with icx_free). Returns an icx_tga_result. */
+int icx_tga_save_to_memory(icx_ctx* ctx, const uint8_t* pixels, int width, int height, int d, int rle, uint8_t** out,
+                           size_t* size);
+/* The same file written to `path` (ICX_TGA_INTERNAL_ERR when it cannot be written). */
+int icx_tga_save_to_file(icx_ctx* ctx, const char* path, const uint8_t* pixels, int width, int height, int d, int rle);
+/* n writes with pixels and files resident on the device: image i's pixels at d_src[i] (a host
+ * array of device pointers; widths / heights are host arrays), its file to d_out + i*out_stride
+ * (any alignment), the file's length to d_sizes[i] and an icx_tga_result to d_status[i] (device
+ * arrays): INVALID_ARGUMENT for a bad size or null source, TOO_LARGE (nothing of the file
+ * written, d_sizes[i] says what it needs) when it is longer than out_stride. d not in 1, 3, 4 ->
+ * the call returns ICX_TGA_INVALID_ARGUMENT. Runs on hip_stream (NULL = the context's stream)
+ * and synchronises with it. */
+int icx_tga_encode_device_batch(icx_ctx* ctx, int n, const uint8_t* const* d_src, const int32_t* widths,
+                                const int32_t* heights, int d, int rle, uint8_t* d_out, uint64_t out_stride,
+                                uint64_t* d_sizes, int32_t* d_status, void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -12,6 +12,12 @@
  *               conversions where the reference calls libpng).
  *               ".exr" decodes OpenEXR to RGBA floats on the GPU (readExr, codecs.cpp:464-493 ->
  *               icx_exr_decode = tinyexr's LoadEXRFromMemory; scope in include/icx.h).
+ *               ".tga" decodes Targa to 8-bit R,G,B(,A) or grey, rows top-down, on the GPU (readTga,
+ *               codecs.cpp:1304-1407 -> icx_tga_decode): raw and run-length coded true colour (24 /
+ *               32 bits), monochrome (8 bits) and paletted files (8- / 16-bit indices, 24- / 32-bit
+ *               entries; type 9 included, which the reference leaves as a TODO). channels() is 3
+ *               or 4 for colour and 1 for monochrome. A file the read refuses (codes in
+ *               include/icx.h) leaves pixels_ null and read() throws "Could not read image data".
  *   write(path) -- ".jpg"/".jpeg" encode with tiny_jpeg quality 3 semantics (writeJpg,
  *                  codecs.cpp:851-854 -> icx_tje_encode_to_file, byte-identical stream).
  *               ".png" encodes with png_encoder::saveToFile semantics (writePng,
@@ -21,6 +27,9 @@
  *               codecs.cpp:495-505 -> icx_exr_save_to_file: FLOAT samples, ZIP chunks of 16
  *               lines with a GPU deflate, tinyexr's bytes everywhere else); as in the reference a
  *               failure throws nothing (lastWriteOk() tells).
+ *               ".tga" writes the reference's 18 header bytes and the rows top-down, uncompressed
+ *               (writeTga, codecs.cpp:1410-1437 -> icx_tga_save_to_file), for d = 1, 3, 4; as in
+ *               the reference nothing is thrown (lastWriteOk() tells).
  *   pixels_ is new[]-owned and delete[]-d by ~Image (codecs.h:102); load() adopts a buffer.
  * Every other extension is outside this path: it throws std::invalid_argument exactly like the
  * reference's unknown-extension branch (codecs.cpp:80-83), so a build that needs those codecs
@@ -40,6 +49,17 @@
  * :213-224); swapBR of an image with fewer than 3 channels is a no-op (the reference reads
  * past the end of the buffer there). For UBYTE images with 3 or 4 channels -- every JPEG --
  * the results equal the reference's byte for byte.
+ * Targa read: the header is 18 bytes (the reference subtracts a padded sizeof(Header) of 20 and
+ * reads two bytes too few, codecs.cpp:1343); the ID field is *ID length* bytes (the reference
+ * skips *descriptor* bytes, :1335-1336); palette index i selects entry i - origin and an index
+ * outside the map gives zero bytes (the reference reads outside its buffer, :1177); descriptor
+ * bit 5 (top-left origin) is honoured, so the output is always top-down (the reference always
+ * flips, :1403, right only for bottom-left files), and bit 4 (right-to-left) is refused;
+ * packets may cross row ends, as in the reference; a packet with more pixels than are missing
+ * is refused (the reference writes past its buffer); bytes after the image data are ignored.
+ * Targa write, by evident intent: the payload is B,G,R(,A) (the reference stores R,G,B, :1429-1434,
+ * which every TGA reader, its own included, shows with red and blue exchanged), and d = 1 is
+ * written as image type 3 (the reference's type 2 with 8 bits is not a TGA form).
  *
  * Header-only; link with -L<repo>/imagecodecs_amd/lib -licx. One icx context per process
  * (device ICX_DEVICE, default 0), created on first use and serialised by a mutex -- the
@@ -228,6 +248,38 @@ class Image {
         type_ = Type::UBYTE;
     }
 
+    // readTga (codecs.cpp:1304-1407): d = 1, 3 or 4, Type::UBYTE, rows top-down, decoded on the GPU
+    // (icx_tga_decode). As in the reference a failure (type 0 included) leaves pixels_ null, and
+    // read() throws "Could not read image data" (:85-88).
+    void readTga(const std::string& path) {
+        std::FILE* f = std::fopen(path.c_str(), "rb");
+        std::vector<uint8_t> buf;
+        if (f) {
+            uint8_t chunk[1 << 16];
+            size_t k;
+            while ((k = std::fread(chunk, 1, sizeof chunk, f)) > 0) buf.insert(buf.end(), chunk, chunk + k);
+            std::fclose(f);
+        }
+        auto& P = detail::icx_process();
+        std::lock_guard<std::mutex> lock(P.mu);
+        uint8_t* out = nullptr;
+        int w = 0, h = 0, d = 0;
+        const int rc = icx_tga_decode(P.get(), buf.data(), buf.size(), &out, &w, &h, &d);
+        delete[] pixels_;
+        pixels_ = nullptr;
+        w_ = h_ = d_ = 0;
+        if (rc == ICX_TGA_INTERNAL_ERR) throw std::runtime_error(std::string("icx_tga_decode: ") + icx_last_error(P.get()));
+        if (rc != ICX_TGA_OK) return;
+        const size_t n = (size_t)w * h * d;
+        pixels_ = new unsigned char[n ? n : 1];
+        if (n) std::memcpy(pixels_, out, n);
+        icx_free(out);
+        w_ = w;
+        h_ = h;
+        d_ = d;
+        type_ = Type::UBYTE;
+    }
+
     void writeJpg(const std::string& path) {
         auto& P = detail::icx_process();
         std::lock_guard<std::mutex> lock(P.mu);
@@ -260,6 +312,25 @@ class Image {
         const int rc = icx_exr_save_to_file(c, path.c_str(), reinterpret_cast<const float*>(pixels_), w_, h_, d_, 0);
         last_write_ok_ = rc == ICX_EXR_SUCCESS;
         if (!last_write_ok_) std::fprintf(stderr, "icx_exr_save_to_file -> %d %s\n", rc, icx_last_error(c));
+    }
+
+    // writeTga (codecs.cpp:1410-1437): uncompressed, d = 1, 3, 4. As in the reference nothing is
+    // thrown: a failure -- no usable GPU included -- only prints the message; the result stays
+    // queryable.
+    void writeTga(const std::string& path) {
+        auto& P = detail::icx_process();
+        std::lock_guard<std::mutex> lock(P.mu);
+        last_write_ok_ = false;
+        icx_ctx* c = nullptr;
+        try {
+            c = P.get();
+        } catch (const std::runtime_error& e) {
+            std::fprintf(stderr, "%s\n", e.what());
+            return;
+        }
+        const int rc = icx_tga_save_to_file(c, path.c_str(), pixels_, w_, h_, d_, 0);
+        last_write_ok_ = rc == ICX_TGA_OK;
+        if (!last_write_ok_) std::fprintf(stderr, "icx_tga_save_to_file -> %d %s\n", rc, icx_last_error(c));
     }
 
 public:
@@ -323,6 +394,7 @@ public:
         else if (ext == ".png") readPng(filepath);
         else if (ext == ".hdr") readHdr(filepath);
         else if (ext == ".exr") readExr(filepath);
+        else if (ext == ".tga") readTga(filepath);
         else throw std::invalid_argument("Cannot parse filetype");
         if (pixels_ == nullptr) throw std::runtime_error("Could not read image data");
     }
@@ -332,6 +404,7 @@ public:
         if (ext == ".jpg" || ext == ".jpeg") writeJpg(filepath);
         else if (ext == ".png") writePng(filepath);
         else if (ext == ".exr") writeExr(filepath);
+        else if (ext == ".tga") writeTga(filepath);
         else throw std::invalid_argument("Cannot parse filetype");
     }
 };
