@@ -296,6 +296,36 @@ ICX_HD bool exr_inflate(const uint8_t* src, int64_t n, uint8_t* dst, int64_t cap
     return true;
 }
 
+// Adler-32 of dst[0, out) as the wave's inflate computes it afterwards (icx_inflate_wave.h; out
+// below 2^30): a = 1 + sum b_p, b = out + sum (out - p) b_p (mod 65521). adler_wave_lane is lane l
+// of 64: the dwords at 4 l + 256 m (independent loads; the last one byte by byte). The wave adds
+// the lanes' sums (tests/emu: a loop over the lanes) and adler_wave_combine makes the checksum.
+// Bounds: a lane's positions weigh sum (out - p) < out^2 / 128 + 4 out, so its s2 stays below
+// 255 * (2^53 + 2^32) < 2^61 for out < 2^30 and needs no folding inside the loop; all lanes
+// together reach 255 * out (out + 1) / 2, which passes 2^64 from out = 380,368,697 bytes of 0xFF on. So
+// every lane reduces its s2 before the sum: 64 values below 65521. s1 <= 255 * 2^30 < 2^38 in all.
+ICX_HD void adler_wave_lane(const uint8_t* dst, uint32_t out, uint32_t lane, uint64_t& s1, uint64_t& s2) {
+    s1 = 0;
+    s2 = 0;
+    for (uint32_t i = 4u * lane; i < out; i += 256u) {
+        const bool whole = i + 4u <= out;
+        const uint32_t v = whole ? *reinterpret_cast<const uint32_t*>(dst + i) : 0u;
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+        for (uint32_t j = 0; j < 4; ++j) {
+            const uint32_t b = whole ? (v >> (8 * j)) & 255u : (i + j < out ? (uint32_t)dst[i + j] : 0u);
+            s1 += b;
+            s2 += (uint64_t)(out - (i + j)) * b;
+        }
+    }
+    s2 %= 65521u;
+}
+ICX_HD uint32_t adler_wave_combine(uint64_t s1, uint64_t s2, uint32_t out) {
+    const uint32_t a1 = (uint32_t)((1 + s1) % 65521u), a2 = (uint32_t)((s2 + (uint64_t)out) % 65521u);
+    return (a2 << 16) | a1;
+}
+
 // DecompressRle's run decode (the byte transform follows): true when exactly `cap` bytes come out.
 ICX_HD bool exr_unrle(const uint8_t* src, int64_t n, uint8_t* dst, int64_t cap) {
     if (n <= 2) return false;

@@ -290,24 +290,14 @@ __device__ __forceinline__ bool exr_inflate_wave(const uint8_t* src, int64_t n64
     if (in.past_end()) return false;
     // Adler-32 of the output: a = 1 + sum b_i, b = out + sum (out - i) b_i (mod 65521)
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    uint64_t s1 = 0, s2 = 0;
-    for (uint32_t i = 4u * lane; i < out; i += 256u) {
-        const bool whole = i + 4u <= out;
-        const uint32_t v = whole ? *reinterpret_cast<const uint32_t*>(dst + i) : 0u;
-#pragma unroll
-        for (uint32_t j = 0; j < 4; ++j) {
-            const uint32_t b = whole ? (v >> (8 * j)) & 255u : (i + j < out ? (uint32_t)dst[i + j] : 0u);
-            s1 += b;
-            s2 += (uint64_t)(out - (i + j)) * b;
-        }
-    }
+    uint64_t s1, s2;
+    adler_wave_lane(dst, out, lane, s1, s2);
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
         s1 += __shfl_xor(s1, o);
         s2 += __shfl_xor(s2, o);
     }
-    const uint32_t a1 = (uint32_t)((1 + s1) % 65521u), a2 = (uint32_t)((s2 + (uint64_t)out) % 65521u);
-    if (exr_uni(adler) != exr_uni((a2 << 16) | a1)) return false;
+    if (exr_uni(adler) != exr_uni(adler_wave_combine(s1, s2, out))) return false;
     *produced = out;
     return true;
 }

@@ -68,6 +68,19 @@ int emu_exr_inflate_ring(const uint8_t* src, int64_t n, uint8_t* dst, int64_t ca
     return exr_inflate<16384>(src, n, dst, cap, produced, *st, win.data()) ? 1 : 0;
 }
 
+// The wave inflate's Adler-32 of dst[0, out): its 64 lanes one after the other, their sums added
+// as the wave's butterfly adds them (64-bit, wrapping), then the combine.
+uint32_t emu_adler_wave(const uint8_t* dst, uint32_t out) {
+    uint64_t s1 = 0, s2 = 0;
+    for (uint32_t lane = 0; lane < 64; ++lane) {
+        uint64_t l1, l2;
+        adler_wave_lane(dst, out, lane, l1, l2);
+        s1 += l1;
+        s2 += l2;
+    }
+    return adler_wave_combine(s1, s2, out);
+}
+
 // The whole read: the tinyexr code; on success w*h*4 float bits in out (cap_px pixels at most).
 int emu_exr_decode(const uint8_t* data, int64_t size, uint32_t* out, int64_t cap_px, int* w, int* h) {
     ExrPlan P;
