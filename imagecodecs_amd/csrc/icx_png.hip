@@ -735,7 +735,8 @@ __global__ __launch_bounds__(256) void k_png_seam(const uint8_t* __restrict__ F,
         int64_t bp = s0;      // ... and the stream position it starts at
         int64_t q = s0 + o;   // the re-parse position
         bool joined = false;
-        for (;;) {  // wave-uniform: every lane walks the same tokens
+        // ICX_PNG_SEAM=0: no walk, every overhanging match is cut, also where B's parse would meet it
+        if (join) for (;;) {  // wave-uniform: every lane walks the same tokens
             while (si <= last && bp < q) {
                 const uint32_t t = tokat(si);
                 if (t < 256) {
@@ -755,7 +756,7 @@ __global__ __launch_bounds__(256) void k_png_seam(const uint8_t* __restrict__ F,
                 joined = true;
                 break;
             }
-            if ((si > last && !final_seg) || nh + 2 > kHead || !join || q >= s0 + kSeamReach) break;  // no join: cut A
+            if ((si > last && !final_seg) || nh + 2 > kHead || q >= s0 + kSeamReach) break;  // no join: cut A
             int len0, dist0, len1;
             seam_score(V, N, q, cand, lane, len0, dist0, len1);
             if (len0 >= 3 && !(q + 1 < N && len1 > len0)) {

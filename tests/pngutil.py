@@ -122,3 +122,31 @@ def synth_rgba(seed: int, w: int, h: int, opaque: bool = False) -> np.ndarray:
 
 def read_fixture_png(path: str) -> np.ndarray:
     return decode_rgba(open(path, "rb").read())
+
+
+def check(ctx, px, decode=True):
+    """The encoder's parity contract on one image: lodepng's colour type, depth, palette and tRNS
+    (the oracle's), an IDAT that inflates to the oracle's filtered stream, and (decode) a file that
+    reads back to the input pixels. -> the file."""
+    from oracle import pyoracle as O
+    h, w, d = px.shape
+    png = ctx.png_encode(w, h, d, px.tobytes())
+    assert png is not None
+    I = info(png)  # also verifies every chunk CRC
+    m = O.png_choose(px.tobytes(), w, h, d)
+    assert (I["colortype"], I["bitdepth"]) == (m.colortype, m.bitdepth)
+    if m.colortype == 3:
+        pal = np.frombuffer(bytes(m.pal[: 4 * m.npal]), np.uint8).reshape(-1, 4)
+        assert I["plte"] == pal[:, :3].tobytes()
+        a = pal[:, 3]
+        nz = np.nonzero(a != 255)[0]
+        assert I["trns"] == (a[: nz[-1] + 1].tobytes() if len(nz) else None)
+    elif m.key_defined:
+        k = [m.key_r, m.key_g, m.key_b] if m.colortype == 2 else [m.key_r]
+        assert I["trns"] == b"".join(int(v).to_bytes(2, "big") for v in k)
+    else:
+        assert I["trns"] is None
+    assert zlib.decompress(I["idat"]) == O.png_filtered(px.tobytes(), w, h, d, m)
+    if decode:
+        np.testing.assert_array_equal(decode_rgba(png), to_rgba(px))
+    return png

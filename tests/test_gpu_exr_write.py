@@ -7,6 +7,7 @@ import pytest
 
 import imagecodecs_amd as icx
 from oracle import exr_oracle as O
+import deflate_read as R
 import exrw_util as U
 
 pytestmark = pytest.mark.gpu
@@ -30,6 +31,36 @@ def check(ctx, a, fp16, golden=None):
     assert code == 0 and (np.ascontiguousarray(img).view(np.uint32) == want).all(), "GPU read-back"
     assert len(data) <= icx.lib().icx_exr_encode_bound(a.shape[1], a.shape[0], a.shape[2], int(fp16))
     return data, nraw
+
+
+def audit_file(a, fp16, data):
+    """The token-level audit (deflate_read.audit) of every compressed chunk of a file of ours: its
+    tokens give the predictor bytes, its codes are complete, free of unused symbols and cost the
+    optimum, its headers are tight; and no match crosses a 4 KiB segment end (matches
+    are cut there). -> [(blocks, audit's figures)] per compressed chunk."""
+    out = []
+    for k, (y, size, payload, at) in enumerate(U.split(a, fp16, data)[2]):
+        raw = U.chunk_raw(a, fp16, k)
+        if size == len(raw):
+            continue
+        blocks = R.read_zlib(payload)
+        stats = R.audit(blocks, U.predict(raw), log=print)
+        assert R.crossing(blocks, 4096) == [], ("a match crosses a segment end", k)
+        out.append((blocks, stats))
+    return out
+
+
+def from_predictor_bytes(v, w):
+    """The 16 x w one-channel float image whose single chunk has the predictor bytes `v` (64 w of
+    them): the predictor and the reorder of CompressZip undone."""
+    v = np.asarray(v, np.int64)
+    assert len(v) == 64 * w
+    t = np.cumsum(np.concatenate([v[:1], v[1:] - 128])) & 255
+    raw = np.empty(len(v), np.uint8)
+    raw[0::2], raw[1::2] = t[: len(v) // 2], t[len(v) // 2:]
+    a = raw.view(np.float32).reshape(16, w, 1)
+    assert U.predict(U.chunk_raw(a, False, 0)) == v.astype(np.uint8).tobytes()
+    return a
 
 
 @pytest.mark.parametrize("name", ["none_9x8_rgba", "none_15x15_rgb", "none_1x1_a"])
@@ -61,13 +92,18 @@ def test_fp16_edge_table(ctx):
 def test_several_segments_long_distances(ctx, w, h):
     """76,800- and 281,600-byte chunks: many segments per chunk, one past 256 KiB; the previous
     line is 2400 / 8800 bytes back, inside the window."""
-    data, nraw = check(ctx, U.smooth(w, h, 4, 20 + w), False)
+    a = U.smooth(w, h, 4, 20 + w)
+    data, nraw = check(ctx, a, False)
     assert nraw == 0
+    audited = audit_file(a, False, data)
+    assert len(audited) == U.nchunks(a, False) and any(len(b) > 1 for b, _ in audited)  # (several deflate blocks)
 
 
 def test_wide_drops_the_line_candidate(ctx):
     """4200 x 16 RGBA float: the previous line is 33,600 bytes back, past the 32 KiB window."""
-    check(ctx, U.smooth(4200, 16, 4, 30), False)
+    a = U.smooth(4200, 16, 4, 30)
+    data, nraw = check(ctx, a, False)
+    assert len(audit_file(a, False, data)) + nraw == U.nchunks(a, False)
 
 
 @pytest.mark.parametrize("fp16", [False, True])
@@ -80,6 +116,64 @@ def test_flat_finds_runs(ctx, fp16):
     raw = a.size * (2 if fp16 else 4)
     print("flat", "fp16" if fp16 else "float", "payload bytes", sum(sizes), "of", raw)
     assert sum(sizes) < 0.02 * raw
+    audited = audit_file(a, fp16, data)
+    assert len(audited) == U.nchunks(a, fp16)
+
+
+def flat_and_geometric_tail(n, nflat, ratio, top, seed, first=60):
+    """n predictor bytes, shuffled: a tail of values with counts 1, ratio, ratio^2 ... up to `top`
+    (rounded, increasing) and `nflat` values sharing the rest equally. With the end-of-block code
+    as one more leaf of weight 1 the tail is a chain in the Huffman tree, one level per value, and
+    the flat values add log2(nflat) levels above it; a ratio near 2 keeps the chain when a few
+    length symbols of chance matches fall among its weights (Fibonacci counts lose it). Many flat
+    values keep 4-byte repeats inside a segment rare, so the stream stays literals."""
+    tail, x = [], 1.0
+    while round(x) <= top:
+        if not tail or round(x) > tail[-1]:
+            tail.append(int(round(x)))
+        x *= ratio
+    cnt = np.array([(n - sum(tail)) // nflat] * nflat + tail[::-1], np.int64)
+    cnt[0] += n - cnt.sum()
+    v = np.repeat(first + np.arange(len(cnt)), cnt)
+    np.random.default_rng(seed).shuffle(v)
+    return v
+
+
+@pytest.mark.parametrize("ratio", [1.9, 1.8])
+def test_limiter_on_skewed_predictor_bytes(ctx, ratio):
+    """A 2048 x 16 one-channel chunk: 131,072 predictor bytes in two deflate blocks of 16 segments
+    (64 KiB, the largest this writer makes), each block 64 flat values and a tail of counts
+    1, 2, 4, 7, 13 ... up to 1000 (ratio 1.9 or 1.8). The unlimited literal/length tree of the
+    GPU's own tokens is deeper than 15 in both blocks (measured 17 and 18), so the 15-bit limiter
+    of icx_exrw.hip runs; the audit holds its code complete, within the limit and close to the
+    package-merge optimum (measured: equal to it at 1.9, 1.0000351 of it at 1.8)."""
+    v = np.concatenate([flat_and_geometric_tail(65536, 64, ratio, 1000, 50 + k) for k in range(2)])
+    a = from_predictor_bytes(v, 2048)
+    data, nraw = check(ctx, a, False)
+    assert nraw == 0
+    (blocks, stats), = audit_file(a, False, data)
+    assert [b.out for b in blocks] == [(0, 65536), (65536, 131072)]
+    for bi, b in enumerate(blocks):
+        depth = {s["code"]: s["depth"] for s in stats if s["block"] == bi}
+        ratio = max(s["ratio"] for s in stats if s["block"] == bi)
+        print("exr limiter: block", bi, "unlimited depths", depth, "tokens", len(b.tokens), "matches", len(b.matches()),
+              "worst ratio", ratio)
+        assert len(b.tokens) + 1 >= 1597
+        assert depth["ll"] > 15 and max(b.ll_lens) == 15, depth
+
+
+def test_block_without_a_match(ctx):
+    """32,768 predictor bytes of 160-value noise (two deflate blocks): the Huffman codes alone make
+    the stream smaller than the samples, and a block with no match carries the two forced 1-bit
+    distance codes."""
+    v = np.random.default_rng(51).integers(40, 200, 64 * 512)
+    a = from_predictor_bytes(v, 512)
+    data, nraw = check(ctx, a, False)
+    assert nraw == 0
+    (blocks, stats), = audit_file(a, False, data)
+    assert len(blocks) == 2
+    bare = [b for b in blocks if not b.matches()]
+    assert bare and all(b.hdist + 1 == 2 and b.d_lens == [1, 1] for b in bare)
 
 
 def _dev(arr):

@@ -22,28 +22,7 @@ def ctx():
     c.close()
 
 
-def check(ctx, px, decode=True):
-    h, w, d = px.shape
-    png = ctx.png_encode(w, h, d, px.tobytes())
-    assert png is not None
-    I = P.info(png)  # also verifies every chunk CRC
-    m = O.png_choose(px.tobytes(), w, h, d)
-    assert (I["colortype"], I["bitdepth"]) == (m.colortype, m.bitdepth)
-    if m.colortype == 3:
-        pal = np.frombuffer(bytes(m.pal[: 4 * m.npal]), np.uint8).reshape(-1, 4)
-        assert I["plte"] == pal[:, :3].tobytes()
-        a = pal[:, 3]
-        nz = np.nonzero(a != 255)[0]
-        assert I["trns"] == (a[: nz[-1] + 1].tobytes() if len(nz) else None)
-    elif m.key_defined:
-        k = [m.key_r, m.key_g, m.key_b] if m.colortype == 2 else [m.key_r]
-        assert I["trns"] == b"".join(int(v).to_bytes(2, "big") for v in k)
-    else:
-        assert I["trns"] is None
-    assert zlib.decompress(I["idat"]) == O.png_filtered(px.tobytes(), w, h, d, m)
-    if decode:
-        np.testing.assert_array_equal(P.decode_rgba(png), P.to_rgba(px))
-    return png
+check = P.check  # (shared with test_gpu_png_deflate.py)
 
 
 @pytest.mark.parametrize("w,h", [(1, 1), (3, 2), (37, 23), (257, 5), (64, 64)])
@@ -156,9 +135,10 @@ def test_png_device_batch(ctx, monkeypatch, inflight):
         assert out[i * stride: i * stride + sz[i]].tobytes() == wb, i
     # a slot smaller than the files: every image reports ICX_OUT_OF_MEM with its size
     small = 1000
-    d_small = torch.zeros(len(pxs) * small, dtype=torch.uint8, device="cuda")
+    d_small = torch.full((len(pxs) * small,), 0xAB, dtype=torch.uint8, device="cuda")
     st2, sz2 = enc.encode_device_batch(w, h, 4, [t.data_ptr() for t in d_src], d_small.data_ptr(), small)
     assert (st2 == icx.OUT_OF_MEM).all() and list(sz2) == [len(x) for x in want]
+    assert bool((d_small == 0xAB).all())  # nothing written to a slot that is too small
     enc.close()
 
 
@@ -284,3 +264,123 @@ def test_png_size_photo_4096(ctx, capsys):
     with capsys.disabled():
         print(f"\n  photo 4096^2 RGBA: GPU IDAT / zlib-6 = {r:.3f}")
     assert r <= 1.05, r
+
+
+# ---------------------------------------------------------------- colour-set and colour-key edges
+def _hash32(c):
+    """The colour sets' hash (k_png_stats): the top 12 bits of c x 2654435761 mod 2^32."""
+    return ((np.asarray(c, np.uint64) * 2654435761) & 0xFFFFFFFF) >> 20
+
+
+def _colours(n, seed, white=False):
+    """n distinct opaque RGBA colours, none of them grey, none white (unless asked: then the last is)."""
+    rng = np.random.default_rng(seed)
+    c = np.unique(rng.integers(0, 1 << 24, 4 * n + 16, dtype=np.uint32))
+    rng.shuffle(c)
+    c = c[((c & 255) != ((c >> 8) & 255))][:n]
+    out = np.stack([c & 255, (c >> 8) & 255, (c >> 16) & 255, np.full(n, 255)], axis=1).astype(np.uint8)
+    if white:
+        out[-1] = 255
+    return out
+
+
+def _cycle(cols, w, h, order=None):
+    idx = np.arange(w * h) % len(cols) if order is None else order
+    return np.ascontiguousarray(cols[idx].reshape(h, w, 4))
+
+
+def colour_set_case(case):
+    """-> (RGBA image, (colour type, bit depth) lodepng chooses). 64 x 64 = 16 workgroups of
+    k_png_stats unless said otherwise."""
+    w = h = 64
+    n = w * h
+    if case in ("exact256", "exact257"):  # the 257th colour at the last pixel only
+        cols = _colours(257, 1)
+        idx = np.arange(n) % 256
+        if case == "exact257":
+            idx[-1] = 256
+        return _cycle(cols, w, h, idx), (3, 8) if case == "exact256" else (2, 8)
+    if case in ("halves256", "halves257"):  # 200 colours per half: no workgroup sees more than 200
+        cols = _colours(257, 2)
+        lo = 56 if case == "halves256" else 57
+        idx = np.concatenate([np.arange(n // 2) % 200, lo + np.arange(n // 2) % 200])
+        return _cycle(cols, w, h, idx), (3, 8) if case == "halves256" else (2, 8)
+    if case in ("white+256", "white+255"):  # white has a slot of its own beside a workgroup's 256
+        k = 257 if case == "white+256" else 256
+        return _cycle(_colours(k, 3, white=True), w, h), (2, 8) if k == 257 else (3, 8)
+    if case in ("white_first", "white_last"):
+        cols = _colours(100, 4, white=True)
+        idx = np.arange(n) % 99
+        idx[0 if case == "white_first" else -1] = 99
+        return _cycle(cols, w, h, idx), (3, 8)
+    if case == "hash_collide":  # 256 colours in one probe chain that wraps around both tables
+        c = np.arange(1 << 24, dtype=np.uint32) | 0xFF000000
+        c = c[_hash32(c) == 4095]
+        c = c[((c & 255) != ((c >> 8) & 255))][:256]
+        assert len(c) == 256 and (_hash32(c) % 1024 == 1023).all()
+        cols = np.stack([c & 255, (c >> 8) & 255, (c >> 16) & 255, c >> 24], axis=1).astype(np.uint8)
+        return _cycle(cols, w, h), (3, 8)
+    if case == "grid_stride":  # 1100 x 1000 > 4096 x 256 pixels: the workgroups take a second pixel each
+        w, h = 1100, 1000
+        rng = np.random.default_rng(5)
+        cols = _colours(200, 5)
+        idx = rng.integers(0, 8, w * h)
+        at = rng.permutation(w * h)[: 192 * 3].reshape(192, 3)
+        at[-1, 0] = w * h - 1  # (one colour first seen at the last pixel, in the second stride)
+        for k in range(192):
+            idx[at[k]] = 8 + k
+        return _cycle(cols, w, h, idx), (3, 8)
+    # colour keys: 300 x 200 opaque colour noise, transparent pixels of one colour K late in the image
+    w, h = 300, 200
+    rng = np.random.default_rng(6)
+    px = rng.integers(0, 256, (h, w, 4), dtype=np.uint8)
+    px[..., 3] = 255
+    K = (10, 200, 30)
+    px[(px[..., :3] == K).all(axis=2), 0] = 11  # no pixel of colour K by chance
+    px[150:153, 100:140] = K + (0,)
+    if case == "key_late":
+        return px, (2, 8)
+    if case == "key_a2":  # a transparent pixel of another colour
+        px[199, 299] = (1, 2, 3, 0)
+        return px, (6, 8)
+    if case == "key_a3_before":  # an opaque pixel of the key colour before the first transparent one
+        px[0, 5] = K + (255,)
+        return px, (6, 8)
+    if case == "key_a3_after":
+        px[199, 299] = K + (255,)
+        return px, (6, 8)
+    if case == "key_16px":  # a key needs more than 16 pixels
+        px = np.ascontiguousarray(px[150:154, 97:101])
+        assert px[0, 3, 3] == 0 and px[..., 3].max() == 255
+        return px, (6, 8)
+    depth = {"key_grey1": 1, "key_grey2": 2, "key_grey4": 4}[case]
+    levels = (1 << depth) - 1  # opaque levels 0 .. levels - 1, the key is the top level (255)
+    g = (rng.integers(0, levels, (h, w)) * (255 // levels)).astype(np.uint8)
+    px = np.stack([g, g, g, np.full((h, w), 255, np.uint8)], axis=2)
+    px[150:153, 100:140] = (255, 255, 255, 0)
+    return px, (0, depth)
+
+
+COLOUR_SET_CASES = ["exact256", "exact257", "halves256", "halves257", "white+256", "white+255", "white_first", "white_last",
+                    "hash_collide", "grid_stride", "key_late", "key_a2", "key_a3_before", "key_a3_after", "key_16px",
+                    "key_grey1", "key_grey2", "key_grey4"]
+
+
+@pytest.mark.parametrize("case", COLOUR_SET_CASES)
+def test_png_colour_set_edges(ctx, case):
+    """k_png_stats / k_png_keycheck where several workgroups meet: the 256 / 257 colour boundary
+    (in one place, and as the union of two halves), opaque white's own slot, probe chains that wrap
+    around both hash tables, the grid-stride pass, and the colour-key cases (a second transparent
+    colour, an opaque pixel of the key colour, a key in 16 pixels, grey keys masked to 1 / 2 / 4
+    bits): lodepng's choice, palette order and tRNS through `check`."""
+    px, mode = colour_set_case(case)
+    png = check(ctx, px)
+    I = P.info(png)
+    assert (I["colortype"], I["bitdepth"]) == mode
+    if case.startswith("white_"):
+        k = 0 if case == "white_first" else 99
+        assert len(I["plte"]) == 300 and I["plte"][3 * k: 3 * k + 3] == b"\xff\xff\xff"
+    if case == "key_late":
+        assert I["trns"] == bytes([0, 10, 0, 200, 0, 30])
+    if case.startswith("key_grey"):
+        assert I["trns"] == bytes([0, (1 << mode[1]) - 1])
