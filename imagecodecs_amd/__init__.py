@@ -17,7 +17,9 @@ callers (tests, bench): it binds the C ABI with ctypes and offers
   * ``Context.exr_encode``        -- Image::writeExr's float pixels -> OpenEXR (tinyexr SaveEXR)
   * ``Context.tga_decode`` / ``tga_encode`` -- Image::readTga / writeTga (codecs.cpp:1304-1437), RLE included
   * ``TgaBatch``                  -- device-resident batched .tga decode
-  * ``Image``                     -- ImageCodecs::Image (codecs.h:16-103) for .jpg/.jpeg/.png/.hdr/.exr/.tga
+  * ``Context.gif_decode``        -- Image::readGif (codecs.cpp:507-542): first frame, wave LZW decode
+  * ``GifBatch``                  -- device-resident batched .gif decode
+  * ``Image``                     -- ImageCodecs::Image (codecs.h:16-103) for .jpg/.jpeg/.png/.hdr/.exr/.tga/.gif
 
 There is deliberately no CPU fallback: if libicx.so is missing or no GPU is visible every
 entry point raises ``ICXError``.
@@ -38,7 +40,8 @@ __all__ = ["ICXError", "Context", "Batch", "HdrBatch", "Image", "lib", "build", 
            "PNGR_BAD_DATA", "PNGR_TOO_LARGE", "PNGR_INTERNAL_ERR", "EXR_SUCCESS", "EXR_INVALID_DATA", "Multi", "RECORD_DTYPE", "records_device",
            "checksum64", "multi_shard", "TgaBatch", "tga_probe", "tga_encode_bound", "TGA_OK", "TGA_BAD_HEADER",
            "TGA_UNSUPPORTED", "TGA_NO_IMAGE", "TGA_MALFORMED", "TGA_TRUNCATED", "TGA_TOO_LARGE", "TGA_INVALID_ARGUMENT",
-           "TGA_INTERNAL_ERR"]
+           "TGA_INTERNAL_ERR", "GifBatch", "gif_probe", "GIF_OK", "GIF_NOT_GIF", "GIF_BAD_HEADER", "GIF_MALFORMED",
+           "GIF_BAD_DATA", "GIF_TRUNCATED", "GIF_TOO_LARGE", "GIF_INTERNAL_ERR"]
 
 OK, NO_JPEG, UNSUPPORTED, OUT_OF_MEM, INTERNAL_ERR, SYNTAX_ERROR = range(6)  # nj_result_t
 RESULT_NAMES = ["NJ_OK", "NJ_NO_JPEG", "NJ_UNSUPPORTED", "NJ_OUT_OF_MEM", "NJ_INTERNAL_ERR", "NJ_SYNTAX_ERROR"]
@@ -139,6 +142,12 @@ _SIGS = {
     "icx_tga_batch_destroy": (None, [_vp]),
     "icx_tga_batch_decode": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _vp]),
     "icx_tga_batch_stage_times": (_i32, [_vp, _vp, _vp, _i32]),
+    "icx_gif_probe": (_i32, [_vp, _sz, C.POINTER(_i32), C.POINTER(_i32)]),
+    "icx_gif_decode": (_i32, [_vp, _vp, _sz, C.POINTER(_vp), C.POINTER(_i32), C.POINTER(_i32)]),
+    "icx_gif_batch_create": (_vp, [_vp, _i32, _i32, _i32]),
+    "icx_gif_batch_destroy": (None, [_vp]),
+    "icx_gif_batch_decode": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _vp]),
+    "icx_gif_batch_stage_times": (_i32, [_vp, _vp, _vp, _i32]),
     "icx_tga_encode_bound": (_sz, [_i32, _i32, _i32]),
     "icx_tga_save_to_memory": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, C.POINTER(_vp), C.POINTER(_sz)]),
     "icx_tga_save_to_file": (_i32, [_vp, C.c_char_p, _vp, _i32, _i32, _i32, _i32]),
@@ -165,6 +174,9 @@ EXR_UNSUPPORTED_FORMAT, EXR_INVALID_HEADER, EXR_UNSUPPORTED_FEATURE, EXR_INTERNA
 (TGA_OK, TGA_BAD_HEADER, TGA_UNSUPPORTED, TGA_NO_IMAGE, TGA_MALFORMED, TGA_TRUNCATED, TGA_TOO_LARGE,
  TGA_INVALID_ARGUMENT) = range(8)
 TGA_INTERNAL_ERR = -1
+# icx_gif_result (include/icx.h): Image::readGif outcomes
+GIF_OK, GIF_NOT_GIF, GIF_BAD_HEADER, GIF_MALFORMED, GIF_BAD_DATA, GIF_TRUNCATED, GIF_TOO_LARGE = range(7)
+GIF_INTERNAL_ERR = -1
 
 WRITE_FUNC = C.CFUNCTYPE(None, C.c_void_p, C.c_void_p, C.c_int)
 
@@ -437,6 +449,22 @@ class Context:
             arr = np.frombuffer(C.string_at(out.value, n), np.uint8).reshape(h.value, w.value, d.value).copy()
             lib().icx_free(out)
         return code, w.value, h.value, d.value, arr
+
+    def gif_decode(self, data: bytes):
+        """Image::readGif (codecs.cpp:507-542; contract in include/icx.h) on the GPU -> (code, w, h,
+        uint8 (h, w, 3) or None); code is an icx_gif_result."""
+        buf = C.create_string_buffer(bytes(data), max(1, len(data)))
+        out = C.c_void_p()
+        w, h = C.c_int(), C.c_int()
+        code = lib().icx_gif_decode(self._p, buf, len(data), C.byref(out), C.byref(w), C.byref(h))
+        if code == GIF_INTERNAL_ERR:
+            raise ICXError("icx_gif_decode: " + _err(self._p))
+        arr = None
+        if out.value:
+            n = w.value * h.value * 3
+            arr = np.frombuffer(C.string_at(out.value, n), np.uint8).reshape(h.value, w.value, 3).copy()
+            lib().icx_free(out)
+        return code, w.value, h.value, arr
 
     def tga_encode(self, px, rle: bool = False):
         """Image::writeTga (codecs.cpp:1410-1437) on the GPU: uint8 (h, w) or (h, w, d), d in 1, 3, 4,
@@ -767,6 +795,14 @@ def tga_probe(data: bytes):
     return code, w.value, h.value, d.value
 
 
+def gif_probe(data: bytes):
+    """Host container walk of the GIF read, up to the first image descriptor -> (code, width, height)."""
+    w, h = C.c_int(), C.c_int()
+    buf = C.create_string_buffer(bytes(data), max(1, len(data)))
+    code = lib().icx_gif_probe(buf, len(data), C.byref(w), C.byref(h))
+    return code, w.value, h.value
+
+
 def tga_encode_bound(width: int, height: int, d: int) -> int:
     """icx_tga_encode_bound: 18 + w*h*(d+1), or 0 for arguments the write refuses."""
     return int(lib().icx_tga_encode_bound(width, height, d))
@@ -846,6 +882,39 @@ class TgaBatch:
         return {names[i].decode(): float(ms[i]) for i in range(k)}
 
 
+class GifBatch:
+    """Device-resident batched GIF decode (icx_gif_batch_*): image i is
+    d_data[d_offsets[i] .. + d_sizes[i]); its R,G,B bytes at d_out + i*out_stride, status in
+    d_status[i], {width, height, 3} in d_dims[3i..]."""
+
+    def __init__(self, ctx: Context, max_images: int, max_width: int, max_height: int):
+        self.ctx = ctx
+        self._p = lib().icx_gif_batch_create(ctx.ptr, max_images, max_width, max_height)
+        if not self._p:
+            raise ICXError("icx_gif_batch_create failed: " + _err(ctx.ptr))
+        self.max_images, self.max_width, self.max_height = max_images, max_width, max_height
+
+    def close(self):
+        if getattr(self, "_p", None):
+            lib().icx_gif_batch_destroy(self._p)
+            self._p = None
+
+    def __del__(self):
+        self.close()
+
+    def decode_device(self, n, d_data, d_offsets, d_sizes, d_out, out_stride, d_status, d_dims, stream=0):
+        rc = lib().icx_gif_batch_decode(self._p, n, d_data, d_offsets, d_sizes, d_out, out_stride,
+                                        d_status, d_dims, stream or None)
+        if rc != GIF_OK:
+            raise ICXError(f"icx_gif_batch_decode -> {rc}: {_err(self.ctx.ptr)}")
+
+    def stage_times(self) -> dict:
+        names = (C.c_char_p * 8)()
+        ms = (C.c_float * 8)()
+        k = lib().icx_gif_batch_stage_times(self._p, names, ms, 8)
+        return {names[i].decode(): float(ms[i]) for i in range(k)}
+
+
 class HdrBatch:
     """Device-resident batched Radiance .hdr decode (icx_hdr_batch_*): image i is
     d_data[d_offsets[i] .. + d_sizes[i]); 4 floats per pixel at d_out + i*out_stride floats."""
@@ -883,8 +952,8 @@ class Image:
 
     read()/write() dispatch on the lower-cased extension like Image::read/write
     (codecs.cpp:53-122): read .jpg/.jpeg (readJpg), .png (readPng: d = 4, type UBYTE) and .hdr
-    (readHdr: d = 4, type FLOAT, the floats' bytes in pixels_), .exr and .tga (readTga: d = 1, 3 or
-    4, type UBYTE), write .jpg/.jpeg, .png, .exr and .tga (uncompressed). Other extensions raise ValueError (the
+    (readHdr: d = 4, type FLOAT, the floats' bytes in pixels_), .exr, .tga (readTga: d = 1, 3 or
+    4, type UBYTE) and .gif (readGif: the first frame, d = 3, type UBYTE), write .jpg/.jpeg, .png, .exr and .tga (uncompressed). Other extensions raise ValueError (the
     reference's std::invalid_argument for unknown types)."""
 
     UBYTE, USHORT, FLOAT = range(3)  # ImageCodecs::Type (codecs.h:14)
@@ -914,6 +983,9 @@ class Image:
             return
         if ext == ".tga":
             self._read_tga(filepath)
+            return
+        if ext == ".gif":
+            self._read_gif(filepath)
             return
         if ext not in (".jpg", ".jpeg"):
             raise ValueError("Cannot parse filetype")
@@ -957,6 +1029,17 @@ class Image:
         if code != TGA_OK:
             raise RuntimeError("Could not read image data")
         self.w_, self.h_, self.d_ = w, h, d
+        self.pixels_ = px.reshape(-1).copy()
+        self.type_ = Image.UBYTE
+
+    def _read_gif(self, filepath: str):
+        """readGif (codecs.cpp:507-542): the first frame on the logical screen, d = 3, type UBYTE,
+        rows top-down. Every failure is Image::read's RuntimeError("Could not read image data")."""
+        data = open(filepath, "rb").read()
+        code, w, h, px = self.context().gif_decode(data)
+        if code != GIF_OK:
+            raise RuntimeError("Could not read image data")
+        self.w_, self.h_, self.d_ = w, h, 3
         self.pixels_ = px.reshape(-1).copy()
         self.type_ = Image.UBYTE
 

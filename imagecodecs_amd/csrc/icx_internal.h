@@ -362,6 +362,21 @@ int tga_encode_batch(hipStream_t st, TgawWs& ws, int n, const uint8_t* const* d_
                      const int32_t* heights, int d, int rle, uint8_t* d_out, uint64_t out_stride, uint64_t* d_sizes,
                      int32_t* d_status, std::string& err);
 
+// GIF read (icx_gif.hip; Image::readGif, codecs.cpp:507-542). Status codes: icx_gif_core.h
+// kGif* = include/icx.h ICX_GIF_*.
+struct GifDesc;
+struct GifWs {
+    int max_images = 0, max_w = 0, max_h = 0;
+    int64_t plane_stride = 0;  // bytes per image of plane (a multiple of 16)
+    GifDesc* desc = nullptr;   // [max_images]
+    uint8_t* plane = nullptr;  // [max_images][plane_stride] palette indices of the clipped frame rectangle
+};
+int gif_probe(const uint8_t* data, int64_t size, int* w, int* h);
+bool gif_ws_alloc(GifWs& ws, Blocks& mem, int max_images, int max_w, int max_h);
+void launch_gif_decode(const GifWs& ws, int n, const uint8_t* d_data, const uint64_t* d_off, const uint64_t* d_size,
+                       uint8_t* d_out, uint64_t out_stride, int32_t* d_status, int32_t* d_dims, hipStream_t st,
+                       StageHook* hook);
+
 // ---- OpenEXR read (icx_exr.hip) ----
 // tinyexr's LoadEXRFromMemory; returns its code (-100: HIP failure, err says which).
 struct ExrWs;

@@ -497,6 +497,76 @@ int icx_tga_encode_device_batch(icx_ctx* ctx, int n, const uint8_t* const* d_src
                                 const int32_t* heights, int d, int rle, uint8_t* d_out, uint64_t out_stride,
                                 uint64_t* d_sizes, int32_t* d_status, void* hip_stream);
 
+/* ---- GIF read (Image::readGif, codecs.cpp:507-542; gd_open_gif / gd_get_frame / gd_render_frame,
+ * gif.cpp:43-524) -----------------------------------------------------------------------------------
+ * Output as readGif returns it for a well-formed file: Type::UBYTE, 3 channels, the logical
+ * screen's width x height, rows top-down, R,G,B, the first frame only.
+ * Canvas and palette: the canvas starts as the global colour table's entry `bgindex`; the frame
+ * rectangle is drawn over it through the active palette (the local table if present, else the
+ * global one); a pixel whose index equals the transparent index of the last graphic control
+ * extension before the first image descriptor (flag bit 0 set) is skipped and leaves background.
+ * Interlaced frames (descriptor bit 6) use the 8/8/4/2 row order. A palette index or bgindex at or
+ * beyond its table's size gives (0,0,0) (the reference's arrays are zero there). The data ends at
+ * the stop code, at the block terminator or when fw*fh pixels have been produced, whichever comes
+ * first; pixels the stream did not reach hold index bgindex, drawn and skipped like any other, and
+ * that is a success, as in the reference; anything after the stop code is ignored. At 4096 entries
+ * the table freezes and codes stay 12 bits until a clear code. A second frame and everything after
+ * it are not examined. A ';' before any image descriptor is OK with a background-only canvas.
+ * Deliberate deviations:
+ *  - GIF87a is accepted (the reference demands 89a).
+ *  - No global table is accepted when the frame has a local one; the background is then black.
+ *    With neither table the file is MALFORMED.
+ *  - A stream that does not begin with a clear code is decoded as if it did (the reference uses an
+ *    uninitialised length).
+ *  - A code above the next free entry, or a first code after a clear that is not a literal, is
+ *    BAD_DATA (the reference reads outside its table).
+ *  - A string running past fw*fh is cut there (the reference writes past the frame).
+ *  - A frame wider or taller than the canvas is clipped by column and row, stream rows keeping the
+ *    descriptor's width and the interlace order the descriptor's height (the reference re-wraps at
+ *    the clipped width).
+ *  - The interlace passes of a frame lower than 5 rows are empty where they have no row (the
+ *    reference's pass sizes put rows outside such a frame).
+ *  - Every extension, known or unknown label, is walked as a sub-block chain; the graphic control
+ *    values come from its first sub-block when that has >= 4 bytes.
+ *  - A file that ends inside a header, table, extension or data sub-block is TRUNCATED (the
+ *    reference ignores short reads). The data chain is read only as far as the decode goes: a
+ *    file cut after the stop code, or after the sub-block that completes the frame, is OK.
+ * A failed image yields no pixels. */
+enum icx_gif_result {
+    ICX_GIF_OK = 0,
+    ICX_GIF_NOT_GIF = 1,     /* the first 6 bytes are not "GIF87a" / "GIF89a"                        */
+    ICX_GIF_BAD_HEADER = 2,  /* fewer than 13 bytes; zero width or height                            */
+    ICX_GIF_MALFORMED = 3,   /* a separator byte not ',' '!' ';'; fx >= width or fy >= height; no
+                                palette at all                                                       */
+    ICX_GIF_BAD_DATA = 4,    /* minimum code size outside 2..8; an invalid code                      */
+    ICX_GIF_TRUNCATED = 5,   /* the file ends first                                                  */
+    ICX_GIF_TOO_LARGE = 6,   /* larger than the batch workspace                                      */
+    ICX_GIF_INTERNAL_ERR = -1 /* HIP failure (see icx_last_error)                                    */
+};
+/* The container walk up to the first image descriptor (host only, no GPU touched): the canvas
+ * size, or the code the walk gives. The checks run in file order; a file shorter than 6 bytes is
+ * BAD_HEADER. The code stream is checked by the decode. */
+int icx_gif_probe(const uint8_t* data, size_t size, int* width, int* height);
+/* One image, host in / host out: *out receives a malloc()'d width*height*3 byte buffer (free with
+ * icx_free), null unless ICX_GIF_OK. A code the probe gives returns without touching the GPU; a
+ * canvas of more than 2^30 pixels is ICX_GIF_TOO_LARGE. */
+int icx_gif_decode(icx_ctx* ctx, const uint8_t* data, size_t size, uint8_t** out, int* width, int* height);
+/* Device-resident batch: image i = d_data[d_offsets[i] .. + d_sizes[i]), output bytes at
+ * d_out + i*out_stride (out_stride >= 3*max_width*max_height), per-image status in d_status[i]
+ * and {width, height, 3} in d_dims[3i..] (zero for a failed image, whose slot is unspecified).
+ * A canvas wider than max_width or higher than max_height is ICX_GIF_TOO_LARGE. Asynchronous on
+ * hip_stream (NULL = the context's stream), no host read-back. Returns ICX_GIF_OK or
+ * ICX_GIF_INTERNAL_ERR. max_images <= 65535, max_width * max_height <= 2^30. */
+typedef struct icx_gif_batch icx_gif_batch;
+icx_gif_batch* icx_gif_batch_create(icx_ctx* ctx, int max_images, int max_width, int max_height);
+void icx_gif_batch_destroy(icx_gif_batch* b);
+int icx_gif_batch_decode(icx_gif_batch* b, int n, const uint8_t* d_data, const uint64_t* d_offsets,
+                         const uint64_t* d_sizes, uint8_t* d_out, uint64_t out_stride, int32_t* d_status,
+                         int32_t* d_dims, void* hip_stream);
+/* Milliseconds per stage of the last icx_gif_batch_decode ("parse", "lzw", "render";
+ * synchronises). Returns the number of stages. */
+int icx_gif_batch_stage_times(const icx_gif_batch* b, const char** names, float* ms, int cap);
+
 #ifdef __cplusplus
 }
 #endif

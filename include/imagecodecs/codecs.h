@@ -18,6 +18,11 @@
  *               entries; type 9 included, which the reference leaves as a TODO). channels() is 3
  *               or 4 for colour and 1 for monochrome. A file the read refuses (codes in
  *               include/icx.h) leaves pixels_ null and read() throws "Could not read image data".
+ *               ".gif" decodes the first frame of a GIF onto its logical screen, 8-bit R,G,B, rows
+ *               top-down, on the GPU (readGif, codecs.cpp:507-542 -> icx_gif_decode): global and
+ *               local palettes, transparency, interlace, frames smaller than or clipped by the
+ *               canvas. A file the read refuses (codes in include/icx.h) leaves pixels_ null and
+ *               read() throws "Could not read image data". write(".gif") stays outside this path.
  *   write(path) -- ".jpg"/".jpeg" encode with tiny_jpeg quality 3 semantics (writeJpg,
  *                  codecs.cpp:851-854 -> icx_tje_encode_to_file, byte-identical stream).
  *               ".png" encodes with png_encoder::saveToFile semantics (writePng,
@@ -60,6 +65,18 @@
  * Targa write, by evident intent: the payload is B,G,R(,A) (the reference stores R,G,B, :1429-1434,
  * which every TGA reader, its own included, shows with red and blue exchanged), and d = 1 is
  * written as image type 3 (the reference's type 2 with 8 bits is not a TGA form).
+ * GIF read (full list in include/icx.h): GIF87a is accepted (the reference demands 89a); a file
+ * without a global table is accepted when the frame has a local one (black background), and is
+ * refused with neither; a stream that does not begin with a clear code is decoded as if it did
+ * (the reference uses an uninitialised length); a code above the next free entry, or a first code
+ * after a clear that is not a literal, is refused (the reference reads outside its table); a
+ * string running past the frame is cut there (the reference writes past the frame); a frame wider
+ * or taller than the canvas is clipped by column and row, stream rows keeping the descriptor's
+ * width (the reference re-wraps at the clipped width); the interlace passes of a frame lower than
+ * 5 rows are empty where they have no row (the reference's pass sizes put rows outside it); every
+ * extension is walked as a sub-block chain, the graphic control values coming from its first
+ * sub-block when that has at least 4 bytes; a file that ends inside a header, table, extension or
+ * data sub-block the decode still needs is refused (the reference ignores short reads).
  *
  * Header-only; link with -L<repo>/imagecodecs_amd/lib -licx. One icx context per process
  * (device ICX_DEVICE, default 0), created on first use and serialised by a mutex -- the
@@ -314,6 +331,38 @@ class Image {
         if (!last_write_ok_) std::fprintf(stderr, "icx_exr_save_to_file -> %d %s\n", rc, icx_last_error(c));
     }
 
+    // readGif (codecs.cpp:507-542): the first frame on the logical screen, d = 3, Type::UBYTE, rows
+    // top-down, decoded on the GPU (icx_gif_decode). A failure leaves pixels_ null, and read() throws
+    // "Could not read image data" (:85-88).
+    void readGif(const std::string& path) {
+        std::FILE* f = std::fopen(path.c_str(), "rb");
+        std::vector<uint8_t> buf;
+        if (f) {
+            uint8_t chunk[1 << 16];
+            size_t k;
+            while ((k = std::fread(chunk, 1, sizeof chunk, f)) > 0) buf.insert(buf.end(), chunk, chunk + k);
+            std::fclose(f);
+        }
+        auto& P = detail::icx_process();
+        std::lock_guard<std::mutex> lock(P.mu);
+        uint8_t* out = nullptr;
+        int w = 0, h = 0;
+        const int rc = icx_gif_decode(P.get(), buf.data(), buf.size(), &out, &w, &h);
+        delete[] pixels_;
+        pixels_ = nullptr;
+        w_ = h_ = d_ = 0;
+        if (rc == ICX_GIF_INTERNAL_ERR) throw std::runtime_error(std::string("icx_gif_decode: ") + icx_last_error(P.get()));
+        if (rc != ICX_GIF_OK) return;
+        const size_t n = (size_t)w * h * 3;
+        pixels_ = new unsigned char[n ? n : 1];
+        if (n) std::memcpy(pixels_, out, n);
+        icx_free(out);
+        w_ = w;
+        h_ = h;
+        d_ = 3;
+        type_ = Type::UBYTE;
+    }
+
     // writeTga (codecs.cpp:1410-1437): uncompressed, d = 1, 3, 4. As in the reference nothing is
     // thrown: a failure -- no usable GPU included -- only prints the message; the result stays
     // queryable.
@@ -395,6 +444,7 @@ public:
         else if (ext == ".hdr") readHdr(filepath);
         else if (ext == ".exr") readExr(filepath);
         else if (ext == ".tga") readTga(filepath);
+        else if (ext == ".gif") readGif(filepath);
         else throw std::invalid_argument("Cannot parse filetype");
         if (pixels_ == nullptr) throw std::runtime_error("Could not read image data");
     }
