@@ -11,6 +11,7 @@ callers (tests, bench): it binds the C ABI with ctypes and offers
   * ``Batch``                     -- device-resident batched decode (the throughput path)
   * ``Context.hdr_decode``        -- Image::readHdr's Radiance RGBE -> float decode (codecs.cpp:706-777)
   * ``HdrBatch``                  -- device-resident batched .hdr decode
+  * ``Context.hdr_encode``        -- Image::writeHdr's float -> Radiance RGBE write (codecs.cpp:779-818), RLE rows included
   * ``Context.png_decode``        -- Image::readPng's PNG -> RGBA8 decode (codecs.cpp:903-1020)
   * ``PngBatch``                  -- device-resident batched PNG decode
   * ``Context.exr_decode``        -- Image::readExr's OpenEXR -> RGBA float (tinyexr LoadEXRFromMemory)
@@ -35,7 +36,7 @@ import numpy as np
 __all__ = ["ICXError", "Context", "Batch", "HdrBatch", "Image", "lib", "build", "LIB_PATH",
            "OK", "NO_JPEG", "UNSUPPORTED", "OUT_OF_MEM", "INTERNAL_ERR", "SYNTAX_ERROR",
            "HDR_OK", "HDR_NOT_RADIANCE", "HDR_BAD_HEADER", "HDR_MALFORMED", "HDR_TRUNCATED",
-           "HDR_TOO_LARGE", "HDR_INTERNAL_ERR", "hdr_probe", "exr_probe",
+           "HDR_TOO_LARGE", "HDR_INVALID_ARGUMENT", "HDR_INTERNAL_ERR", "hdr_probe", "hdr_encode_bound", "exr_probe",
            "PngBatch", "png_probe", "PNGR_OK", "PNGR_NOT_PNG", "PNGR_BAD_HEADER", "PNGR_UNSUPPORTED", "PNGR_MALFORMED",
            "PNGR_BAD_DATA", "PNGR_TOO_LARGE", "PNGR_INTERNAL_ERR", "EXR_SUCCESS", "EXR_INVALID_DATA", "Multi", "RECORD_DTYPE", "records_device",
            "checksum64", "multi_shard", "TgaBatch", "tga_probe", "tga_encode_bound", "TGA_OK", "TGA_BAD_HEADER",
@@ -111,6 +112,10 @@ _SIGS = {
     "icx_hdr_batch_destroy": (None, [_vp]),
     "icx_hdr_batch_decode": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _vp]),
     "icx_hdr_batch_stage_times": (_i32, [_vp, _vp, _vp, _i32]),
+    "icx_hdr_encode_bound": (_sz, [_i32, _i32, _i32, _i32]),
+    "icx_hdr_save_to_memory": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, C.POINTER(_vp), C.POINTER(_sz)]),
+    "icx_hdr_save_to_file": (_i32, [_vp, C.c_char_p, _vp, _i32, _i32, _i32, _i32]),
+    "icx_hdr_encode_device_batch": (_i32, [_vp, _i32, _vp, _vp, _vp, _i32, _i32, _vp, _u64, _vp, _vp, _vp]),
     "icx_png_probe": (_i32, [_vp, _sz, C.POINTER(_i32), C.POINTER(_i32)]),
     "icx_png_decode": (_i32, [_vp, _vp, _sz, C.POINTER(_vp), C.POINTER(_i32), C.POINTER(_i32)]),
     "icx_png_batch_create": (_vp, [_vp, _i32, _i32, _i32]),
@@ -160,6 +165,7 @@ RECORD_DTYPE = np.dtype([("status", "<i4"), ("width", "<i4"), ("height", "<i4"),
 
 # icx_hdr_result (include/icx.h): Image::readHdr outcomes
 HDR_OK, HDR_NOT_RADIANCE, HDR_BAD_HEADER, HDR_MALFORMED, HDR_TRUNCATED, HDR_TOO_LARGE = range(6)
+HDR_INVALID_ARGUMENT = 6  # the write's refused arguments
 HDR_INTERNAL_ERR = -1
 
 # icx_png_read_result (include/icx.h): Image::readPng outcomes
@@ -320,6 +326,39 @@ class Context:
             arr = np.frombuffer(C.string_at(out.value, n * 4), np.float32).reshape(h.value, w.value, 4).copy()
             lib().icx_free(out)
         return code, w.value, h.value, rows.value, arr
+
+    def hdr_encode(self, arr, rle: bool = False):
+        """Image::writeHdr (codecs.cpp:779-818; contract in include/icx.h) on the GPU: float32 (h, w, 4)
+        R, G, B, E as the read returns them, or (h, w, 3) plain R, G, B -> (code, the file's bytes or
+        None). rle: rows run-length coded where the width allows (8..32767)."""
+        a = np.ascontiguousarray(arr, np.float32)
+        if a.ndim != 3:
+            return HDR_INVALID_ARGUMENT, None
+        h, w, d = a.shape
+        out, size = C.c_void_p(), C.c_size_t()
+        code = lib().icx_hdr_save_to_memory(self._p, a.ctypes.data if a.size else None, w, h, d, 1 if rle else 0,
+                                            C.byref(out), C.byref(size))
+        if code == HDR_INTERNAL_ERR:
+            raise ICXError("icx_hdr_save_to_memory: " + _err(self._p))
+        if code != HDR_OK:
+            return code, None
+        data = C.string_at(out.value, size.value)
+        lib().icx_free(out)
+        return code, data
+
+    def hdr_encode_device_batch(self, d_srcs, widths, heights, d: int, rle: bool, d_out: int, out_stride: int,
+                                d_sizes: int, d_status: int, stream=0) -> int:
+        """icx_hdr_encode_device_batch: image i's floats at device address d_srcs[i], its file to
+        d_out + i*out_stride, size (uint64) and status (int32) to the device arrays -> the call's code."""
+        n = len(d_srcs)
+        sp = (C.c_void_p * max(1, n))(*d_srcs)
+        ws = np.ascontiguousarray(widths, np.int32)
+        hs = np.ascontiguousarray(heights, np.int32)
+        rc = lib().icx_hdr_encode_device_batch(self._p, n, sp, ws.ctypes.data, hs.ctypes.data, d, 1 if rle else 0, d_out,
+                                               out_stride, d_sizes, d_status, stream or None)
+        if rc == HDR_INTERNAL_ERR:
+            raise ICXError("icx_hdr_encode_device_batch: " + _err(self._p))
+        return rc
 
     def png_decode(self, data: bytes):
         """Image::readPng (codecs.cpp:903-1020) on the GPU -> (code, w, h, uint8 (h, w, 4) RGBA or
@@ -787,6 +826,11 @@ def exr_probe(data: bytes):
     return code, w.value, h.value
 
 
+def hdr_encode_bound(width: int, height: int, d: int, rle: bool = False) -> int:
+    """icx_hdr_encode_bound: the largest file the write can give, or 0 for arguments it refuses."""
+    return int(lib().icx_hdr_encode_bound(width, height, d, 1 if rle else 0))
+
+
 def tga_probe(data: bytes):
     """Host header walk of the Targa read -> (code, width, height, channels)."""
     w, h, d = C.c_int(), C.c_int(), C.c_int()
@@ -953,7 +997,8 @@ class Image:
     read()/write() dispatch on the lower-cased extension like Image::read/write
     (codecs.cpp:53-122): read .jpg/.jpeg (readJpg), .png (readPng: d = 4, type UBYTE) and .hdr
     (readHdr: d = 4, type FLOAT, the floats' bytes in pixels_), .exr, .tga (readTga: d = 1, 3 or
-    4, type UBYTE) and .gif (readGif: the first frame, d = 3, type UBYTE), write .jpg/.jpeg, .png, .exr and .tga (uncompressed). Other extensions raise ValueError (the
+    4, type UBYTE) and .gif (readGif: the first frame, d = 3, type UBYTE), write .jpg/.jpeg, .png, .exr,
+    .tga (uncompressed) and .hdr (flat RGBE; d = 4 only). Other extensions raise ValueError (the
     reference's std::invalid_argument for unknown types)."""
 
     UBYTE, USHORT, FLOAT = range(3)  # ImageCodecs::Type (codecs.h:14)
@@ -1075,6 +1120,16 @@ class Image:
             except (ICXError, ValueError, AttributeError):
                 return
             if code != TGA_OK:
+                return
+        elif ext == ".hdr":  # writeHdr (codecs.cpp:779-818): flat RGBE; d != 4 throws (:781-784)
+            if self.d_ != 4:
+                raise RuntimeError("HDR data must contain a 4th channel of exposure values")
+            try:  # (type_ is not consulted: pixels_ is read as floats, as for .exr)
+                px = np.frombuffer(self.pixels_.tobytes(), np.float32, self.w_ * self.h_ * 4)
+                code, out = self.context().hdr_encode(px.reshape(self.h_, self.w_, 4))
+            except (ICXError, ValueError, AttributeError):
+                return
+            if code != HDR_OK:
                 return
         else:
             raise ValueError("Cannot parse filetype")

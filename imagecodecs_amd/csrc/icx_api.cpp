@@ -20,6 +20,7 @@
 #include "icx_mem.h"
 #include "icx_step.h"
 #include "icx_tga_core.h"
+#include "icx_hdrw_core.h"
 #include "icx_gif_core.h"
 
 using namespace icx;
@@ -35,6 +36,7 @@ struct icx_ctx {
     ExrWs* exr = nullptr;  // grow-only EXR read buffers (icx_exr.hip)
     ExrwWs* exrw = nullptr;  // grow-only EXR write buffers (icx_exrw.hip)
     TgawWs* tgaw = nullptr;  // grow-only Targa write buffers (icx_tga.hip)
+    HdrwWs* hdrw = nullptr;  // grow-only Radiance write buffers (icx_hdrw.hip)
 };
 
 struct EventHook;
@@ -176,6 +178,7 @@ void icx_destroy(icx_ctx* c) {
     if (c->exr) exr_ws_destroy(c->exr);
     if (c->exrw) exrw_ws_destroy(c->exrw);
     if (c->tgaw) tgaw_ws_destroy(c->tgaw);
+    if (c->hdrw) hdrw_ws_destroy(c->hdrw);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
 }
@@ -1515,6 +1518,92 @@ int icx_tga_save_to_file(icx_ctx* ctx, const char* path, const uint8_t* pixels, 
         return ICX_TGA_INTERNAL_ERR;
     }
     return ICX_TGA_OK;
+}
+
+// --------------------------------------------------------- Radiance .hdr write (Image::writeHdr)
+size_t icx_hdr_encode_bound(int width, int height, int d, int rle) { return (size_t)hdrw_encode_bound(width, height, d, rle); }
+
+int icx_hdr_encode_device_batch(icx_ctx* ctx, int n, const float* const* d_src, const int32_t* widths,
+                                const int32_t* heights, int d, int rle, uint8_t* d_out, uint64_t out_stride,
+                                uint64_t* d_sizes, int32_t* d_status, void* stream) {
+    if (n < 0 || n > 65535 || (d != 3 && d != 4) ||
+        (n > 0 && (!d_src || !widths || !heights || !d_out || !d_sizes || !d_status)))
+        return ICX_HDR_INVALID_ARGUMENT;
+    if (!ctx) return ICX_HDR_INTERNAL_ERR;
+    if (n == 0) return ICX_HDR_OK;
+    ICX_HIP(ctx, hipSetDevice(ctx->device), ICX_HDR_INTERNAL_ERR);
+    const RoctxRange range("icx_hdr_encode_device_batch");
+    std::string err;
+    int rc;
+    try {  // (nothing may cross the C ABI: a host allocation failure is an internal error)
+        if (!ctx->hdrw) ctx->hdrw = hdrw_ws_create();
+        rc = hdr_encode_batch(stream ? (hipStream_t)stream : ctx->stream, *ctx->hdrw, n, d_src, widths, heights, d,
+                              rle != 0, d_out, out_stride, d_sizes, d_status, err);
+    } catch (const std::exception& e) {
+        err = std::string("icx_hdr_encode_device_batch: ") + e.what();
+        rc = -1;
+    }
+    if (rc != 0) {
+        ctx->err = err.empty() ? "icx_hdr_encode_device_batch: HIP failure" : err;
+        return ICX_HDR_INTERNAL_ERR;
+    }
+    return ICX_HDR_OK;
+}
+
+int icx_hdr_save_to_memory(icx_ctx* ctx, const float* pixels, int width, int height, int d, int rle, uint8_t** out,
+                           size_t* size) {
+    if (out) *out = nullptr;
+    if (size) *size = 0;
+    const uint64_t bound = hdrw_encode_bound(width, height, d, rle);
+    if (!pixels || !out || !size || bound == 0) return ICX_HDR_INVALID_ARGUMENT;  // (before any device work)
+    if (!ctx) return ICX_HDR_INTERNAL_ERR;
+    ICX_HIP(ctx, hipSetDevice(ctx->device), ICX_HDR_INTERNAL_ERR);
+    const uint64_t nbytes = (uint64_t)width * height * d * sizeof(float);
+    Buf<float> d_px;
+    Buf<uint8_t> d_file;
+    Buf<uint64_t> d_res;  // the file's size, then its status
+    uint64_t res[2] = {0, 0};
+    hipStream_t st = ctx->stream;
+    if (!(d_px.reserve(nbytes) && d_file.reserve(bound) && d_res.reserve(16) &&
+          hipMemcpyAsync(d_px.p, pixels, nbytes, hipMemcpyHostToDevice, st) == hipSuccess)) {
+        ctx->err = std::string("icx_hdr_save_to_memory: ") + hipGetErrorString(hipGetLastError());
+        return ICX_HDR_INTERNAL_ERR;
+    }
+    const float* src = d_px.p;
+    const int32_t w = width, h = height;
+    const int rc = icx_hdr_encode_device_batch(ctx, 1, &src, &w, &h, d, rle, d_file.p, bound, d_res.p,
+                                               reinterpret_cast<int32_t*>(d_res.p + 1), st);
+    if (rc != ICX_HDR_OK) return rc;
+    ICX_HIP(ctx, hipMemcpy(res, d_res.p, 16, hipMemcpyDeviceToHost), ICX_HDR_INTERNAL_ERR);
+    const int code = (int32_t)(res[1] & 0xFFFFFFFFu);
+    if (code != ICX_HDR_OK) return code;
+    uint8_t* hostp = (uint8_t*)std::malloc(res[0]);
+    if (!hostp || hipMemcpy(hostp, d_file.p, res[0], hipMemcpyDeviceToHost) != hipSuccess) {
+        std::free(hostp);
+        (void)hipGetLastError();
+        ctx->err = "icx_hdr_save_to_memory: host allocation or copy failed";
+        return ICX_HDR_INTERNAL_ERR;
+    }
+    *out = hostp;
+    *size = (size_t)res[0];
+    return ICX_HDR_OK;
+}
+
+int icx_hdr_save_to_file(icx_ctx* ctx, const char* path, const float* pixels, int width, int height, int d, int rle) {
+    if (!path) return ICX_HDR_INVALID_ARGUMENT;
+    uint8_t* mem = nullptr;
+    size_t size = 0;
+    const int rc = icx_hdr_save_to_memory(ctx, pixels, width, height, d, rle, &mem, &size);
+    if (rc != ICX_HDR_OK) return rc;
+    std::FILE* f = std::fopen(path, "wb");
+    const bool ok = f && std::fwrite(mem, 1, size, f) == size;
+    const bool closed = f && std::fclose(f) == 0;
+    std::free(mem);
+    if (!ok || !closed) {
+        ctx->err = std::string("icx_hdr_save_to_file: cannot write ") + path;
+        return ICX_HDR_INTERNAL_ERR;
+    }
+    return ICX_HDR_OK;
 }
 
 // --------------------------------------------------------- GIF (Image::readGif)

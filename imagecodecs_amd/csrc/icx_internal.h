@@ -362,6 +362,15 @@ int tga_encode_batch(hipStream_t st, TgawWs& ws, int n, const uint8_t* const* d_
                      const int32_t* heights, int d, int rle, uint8_t* d_out, uint64_t out_stride, uint64_t* d_sizes,
                      int32_t* d_status, std::string& err);
 
+// Radiance .hdr write (icx_hdrw.hip; arithmetic and codes in icx_hdrw_core.h).
+struct HdrwWs;  // grow-only buffers of the write
+HdrwWs* hdrw_ws_create();
+void hdrw_ws_destroy(HdrwWs* w);
+// 0, or -1 for a HIP failure (err says which). Synchronises with `st`.
+int hdr_encode_batch(hipStream_t st, HdrwWs& ws, int n, const float* const* d_src, const int32_t* widths,
+                     const int32_t* heights, int d, int rle, uint8_t* d_out, uint64_t out_stride, uint64_t* d_sizes,
+                     int32_t* d_status, std::string& err);
+
 // GIF read (icx_gif.hip; Image::readGif, codecs.cpp:507-542). Status codes: icx_gif_core.h
 // kGif* = include/icx.h ICX_GIF_*.
 struct GifDesc;

@@ -303,7 +303,8 @@ enum icx_hdr_result {
     ICX_HDR_BAD_HEADER = 2,    /* header / resolution line not as readHdr parses it   */
     ICX_HDR_MALFORMED = 3,     /* run-length data the reference cannot decode (UB)     */
     ICX_HDR_TRUNCATED = 4,     /* the file ends first: rows < height                   */
-    ICX_HDR_TOO_LARGE = 5,     /* larger than the batch workspace                      */
+    ICX_HDR_TOO_LARGE = 5,     /* larger than the batch workspace / the write's slot   */
+    ICX_HDR_INVALID_ARGUMENT = 6, /* the write refuses these arguments (below)          */
     ICX_HDR_INTERNAL_ERR = -1  /* HIP failure (see icx_last_error)                     */
 };
 /* Header only (host): width/height of a well-formed header, else the error code. */
@@ -325,6 +326,72 @@ int icx_hdr_batch_decode(icx_hdr_batch* b, int n, const uint8_t* d_data, const u
 /* Milliseconds per stage of the last icx_hdr_batch_decode ("parse", "locate", "unpack",
  * "convert"; synchronises). Returns the number of stages. */
 int icx_hdr_batch_stage_times(const icx_hdr_batch* b, const char** names, float* ms, int cap);
+
+/* ---- Radiance .hdr write (Image::writeHdr, codecs.cpp:779-818) ----------------------------------
+ * The file: the reference's header bytes (:791),
+ *     "#?RADIANCE\nSOFTWARE=GEGL\nFORMAT=32-bit_rle_rgbe\n\n-Y <h> +X <w>\n",
+ * then the rows in the order of the input. icx_hdr_decode and the reference's readHdr both parse it.
+ *
+ * d = 4 (the reference's form; what the read returns): per pixel four floats R, G, B, Ef. In exact
+ * arithmetic,
+ *     E   = Ef truncated toward zero and clamped to 0..255 (NaN gives 0)
+ *     m_c = min(255, floor(v_c * 2^(136 - E)))   for finite v_c > 0
+ *     m_c = 255 for +inf;  m_c = 0 for NaN, negative values and +-0
+ * and the bytes written are m_R, m_G, m_B, E. This is the reference's
+ * (unsigned char)(val * 256.0f * pow(0.5f, E - 128)) with invConvertComponent's arguments in the
+ * intended order (the reference swaps them, :810) and the out-of-range casts, undefined there,
+ * defined. It is the exact inverse of the read (v = m * 2^(E - 136), bit for bit): writing what the
+ * read returned reproduces every RGBE byte of every pixel. The values hold whatever the denormal
+ * mode: they are taken from the floats' exponent and mantissa bits (subnormal inputs included).
+ *
+ * d = 3 (extension: plain float R, G, B, no exponent channel): NaN and negative components count
+ * as 0 and +inf as FLT_MAX; mx = the largest component. mx < 1e-32f (Radiance's setcolr threshold)
+ * writes 0, 0, 0, 0. Otherwise mx = f * 2^e with f in [0.5, 1), E = min(255, e + 128), and the
+ * mantissas follow the d = 4 formula with that E, so the largest mantissa is in 128..255 whenever
+ * e + 128 <= 255. The scale is the power of two 2^(136 - E), not setcolr's frexp(d) * 256 / d: it
+ * is exact and cannot produce 256.
+ *
+ * Pixel data, rle == 0: four bytes per pixel, what the reference writes. One property is shared
+ * with the reference: a flat row whose first pixel is (2, 2, B < 128, .) is taken by every reader
+ * for a run-length coded row, and a flat pixel (1, 1, 1, .) for an old-style repeat. Only d = 4
+ * input with unnormalised mantissas can produce these; d = 3 output never does (its largest
+ * mantissa is >= 128).
+ *
+ * Pixel data, rle != 0 (extension): when 8 <= w <= 32767 each row is 2, 2, w>>8, w&255 followed by
+ * its four component planes (all R, then all G, all B, all E), each packed by this rule (serial as
+ * stated; the kernels give the same bytes); outside that width range the file is flat.
+ *     i = 0
+ *     while i < w:
+ *         r = length of the longest stretch p[i..i+r) of equal bytes, r <= min(127, w - i)
+ *         if r >= 4:  emit 128 + r, p[i];                               i += r
+ *         else:       n = number of bytes k = i, i+1, ... taken while k < w, k - i < 128 and
+ *                         not (k > i and p[k] == p[k+1] == p[k+2] == p[k+3], all four inside the row)
+ *                     emit n, then the n bytes;                          i += n
+ * Run codes are 129..255 (1..127 repeats), literal codes 1..128: what decrunchHDR (:686-700) reads.
+ * A plane never exceeds w + ceil(w/128) bytes.
+ *
+ * Any other d, a width or height < 1, w*h > 2^30 or a null pointer -> ICX_HDR_INVALID_ARGUMENT
+ * (checked before any device work). */
+/* The largest file a write can give: the header + h*(4 + 4*(w + ceil(w/128))) for the run-length
+ * form, the header + 4*w*h (the exact size) for flat; 0 for arguments the writes refuse. Host only. */
+size_t icx_hdr_encode_bound(int width, int height, int d, int rle);
+/* Host pixels in (width*height*d floats), *out receives the malloc()'d file (free with icx_free).
+ * Returns an icx_hdr_result. */
+int icx_hdr_save_to_memory(icx_ctx* ctx, const float* pixels, int width, int height, int d, int rle, uint8_t** out,
+                           size_t* size);
+/* The same file written to `path` (ICX_HDR_INTERNAL_ERR when it cannot be written). */
+int icx_hdr_save_to_file(icx_ctx* ctx, const char* path, const float* pixels, int width, int height, int d, int rle);
+/* n writes with pixels and files resident on the device: image i's pixels at d_src[i] (a host
+ * array of device pointers; widths / heights are host arrays), its file to d_out + i*out_stride
+ * (any alignment), the file's length to d_sizes[i] and an icx_hdr_result to d_status[i] (device
+ * arrays): INVALID_ARGUMENT for a bad size or null source, TOO_LARGE (nothing of the file
+ * written, d_sizes[i] says what it needs) when it is longer than out_stride. d not 3 or 4, n < 0,
+ * n > 65535 (one call's limit: split larger batches) or a null array with n > 0 -> the call returns
+ * ICX_HDR_INVALID_ARGUMENT and writes nothing. Runs on hip_stream (NULL = the context's stream) and
+ * synchronises with it. */
+int icx_hdr_encode_device_batch(icx_ctx* ctx, int n, const float* const* d_src, const int32_t* widths,
+                                const int32_t* heights, int d, int rle, uint8_t* d_out, uint64_t out_stride,
+                                uint64_t* d_sizes, int32_t* d_status, void* hip_stream);
 
 /* ---- OpenEXR read (Image::readExr, codecs.cpp:464-493 -> tinyexr LoadEXRFromMemory, tinyexr.h:6645) ----
  * Output as LoadEXRFromMemory returns it: width*height*4 floats (R, G, B, A by channel name; a
@@ -490,7 +557,8 @@ int icx_tga_save_to_file(icx_ctx* ctx, const char* path, const uint8_t* pixels, 
  * array of device pointers; widths / heights are host arrays), its file to d_out + i*out_stride
  * (any alignment), the file's length to d_sizes[i] and an icx_tga_result to d_status[i] (device
  * arrays): INVALID_ARGUMENT for a bad size or null source, TOO_LARGE (nothing of the file
- * written, d_sizes[i] says what it needs) when it is longer than out_stride. d not in 1, 3, 4 ->
+ * written, d_sizes[i] says what it needs) when it is longer than out_stride. d not in 1, 3, 4,
+ * n < 0, n > 65535 (one call's limit: split larger batches) or a null array with n > 0 ->
  * the call returns ICX_TGA_INVALID_ARGUMENT. Runs on hip_stream (NULL = the context's stream)
  * and synchronises with it. */
 int icx_tga_encode_device_batch(icx_ctx* ctx, int n, const uint8_t* const* d_src, const int32_t* widths,

@@ -35,6 +35,11 @@
  *               ".tga" writes the reference's 18 header bytes and the rows top-down, uncompressed
  *               (writeTga, codecs.cpp:1410-1437 -> icx_tga_save_to_file), for d = 1, 3, 4; as in
  *               the reference nothing is thrown (lastWriteOk() tells).
+ *               ".hdr" writes pixels_ as w*h*4 floats R, G, B, E -- what read(".hdr") returns -- as
+ *               the reference's header and four RGBE bytes per pixel (writeHdr, codecs.cpp:779-818
+ *               -> icx_hdr_save_to_file, rle = 0); writing what was read reproduces every RGBE
+ *               byte. d != 4 throws std::runtime_error("HDR data must contain a 4th channel of
+ *               exposure values") (:781-784); any other failure throws nothing (lastWriteOk() tells).
  *   pixels_ is new[]-owned and delete[]-d by ~Image (codecs.h:102); load() adopts a buffer.
  * Every other extension is outside this path: it throws std::invalid_argument exactly like the
  * reference's unknown-extension branch (codecs.cpp:80-83), so a build that needs those codecs
@@ -65,6 +70,11 @@
  * Targa write, by evident intent: the payload is B,G,R(,A) (the reference stores R,G,B, :1429-1434,
  * which every TGA reader, its own included, shows with red and blue exchanged), and d = 1 is
  * written as image type 3 (the reference's type 2 with 8 bits is not a TGA form).
+ * Radiance write, by evident intent: the mantissas are floor(v * 2^(136 - E)) clamped to 0..255, the
+ * exact inverse of the read (the reference calls invConvertComponent with its arguments swapped,
+ * :810, and its out-of-range casts are undefined); NaN, negative values and zero write 0, +inf 255,
+ * and E is the fourth float truncated and clamped to 0..255 (contract in include/icx.h). A file
+ * that cannot be opened leaves lastWriteOk() false (the reference throws "Cannot open output file.").
  * GIF read (full list in include/icx.h): GIF87a is accepted (the reference demands 89a); a file
  * without a global table is accepted when the frame has a local one (black background), and is
  * refused with neither; a stream that does not begin with a clear code is decoded as if it did
@@ -382,6 +392,27 @@ class Image {
         if (!last_write_ok_) std::fprintf(stderr, "icx_tga_save_to_file -> %d %s\n", rc, icx_last_error(c));
     }
 
+    // writeHdr (codecs.cpp:779-818): the reference's header and four RGBE bytes per pixel. As in the
+    // reference d != 4 throws (:781-784) and type_ is not consulted (pixels_ is read as w*h*4
+    // floats). Any other failure -- no usable GPU included -- only prints the message; the result
+    // stays queryable.
+    void writeHdr(const std::string& path) {
+        if (d_ != 4) throw std::runtime_error("HDR data must contain a 4th channel of exposure values");
+        auto& P = detail::icx_process();
+        std::lock_guard<std::mutex> lock(P.mu);
+        last_write_ok_ = false;
+        icx_ctx* c = nullptr;
+        try {
+            c = P.get();
+        } catch (const std::runtime_error& e) {
+            std::fprintf(stderr, "%s\n", e.what());
+            return;
+        }
+        const int rc = icx_hdr_save_to_file(c, path.c_str(), reinterpret_cast<const float*>(pixels_), w_, h_, 4, 0);
+        last_write_ok_ = rc == ICX_HDR_OK;
+        if (!last_write_ok_) std::fprintf(stderr, "icx_hdr_save_to_file -> %d %s\n", rc, icx_last_error(c));
+    }
+
 public:
     Image() = default;
     Image(const Image&) = delete;  // the reference's implicit copy double-frees pixels_
@@ -455,6 +486,7 @@ public:
         else if (ext == ".png") writePng(filepath);
         else if (ext == ".exr") writeExr(filepath);
         else if (ext == ".tga") writeTga(filepath);
+        else if (ext == ".hdr") writeHdr(filepath);
         else throw std::invalid_argument("Cannot parse filetype");
     }
 };
