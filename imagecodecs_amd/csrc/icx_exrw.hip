@@ -20,8 +20,9 @@
 //                  offset table and chunk headers
 //   k_exrw_emit    one wave per segment: LSB-first bit packing at its offset in the chunk's stream
 //   k_exrw_gather  each payload (stream or raw sample bytes) to its place in the file
-// The deflate stages follow the PNG coder's (icx_png.hip); its device functions are restated here
-// rather than shared, so that encoder's bytes cannot change with this file.
+// The deflate stages follow the PNG coder's (icx_png.hip), and the back end (tables, Huffman code
+// lengths and codes, token bits, window parse, bit packing) is one text for both:
+// icx_deflate_core.h and icx_deflate_wave.h. tests/test_gpu_deflate_pin.py pins both writers' bytes.
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 
@@ -31,6 +32,7 @@
 #include <string>
 #include <vector>
 
+#include "icx_deflate_wave.h"
 #include "icx_exrw_core.h"
 #include "icx_internal.h"
 #include "icx_mem.h"
@@ -39,13 +41,12 @@ namespace icx {
 
 namespace exrw {
 
+using namespace deflate;  // the deflate back end shared with icx_png.hip
+
 constexpr int kSeg = 4096;            // LZ77 / emit segment (predictor bytes)
 constexpr int kSlots = kSeg;          // token slots per segment: a match takes 2 slots for >= 3 bytes
-constexpr int kNLL = 286, kND = 30;   // literal/length and distance alphabets
-constexpr int kHdrWords = 96;         // the block header's bits (<= 3072)
 constexpr int kBlockSegs = 16;        // deflate blocks of at most 64 KiB ...
 constexpr int kMinBlockSegs = 4;      // ... and a chunk under 32 KiB is one block (a header is ~80 bytes)
-constexpr uint32_t kAdlerMod = 65521;
 constexpr int kOk = 0, kInvalidArgument = -3;  // TINYEXR_SUCCESS, TINYEXR_ERROR_INVALID_ARGUMENT
 constexpr uint32_t kMaxTreeWeight = 1u << 18;  // symbol counts are scaled under this before the code
                                                // is built (tree depth < 40, huff_lengths' histogram)
@@ -80,37 +81,6 @@ struct Block {
 struct Out {
     unsigned long long total, fits;  // file bytes; total <= cap (only then is anything written)
 };
-struct BlockCodes {
-    uint16_t ll_code[kNLL];  // bit-reversed (LSB-first emission)
-    uint8_t ll_len[kNLL];
-    uint16_t d_code[kND];
-    uint8_t d_len[kND];
-    uint32_t hdr[kHdrWords];
-    uint32_t hdr_bits;
-    uint32_t pad_;
-};
-static_assert(sizeof(BlockCodes) % 4 == 0, "staged a dword at a time");
-
-// ---- deflate tables (RFC 1951 3.2.5)
-__constant__ uint16_t kLenBase[29] = {3, 4, 5, 6, 7, 8, 9, 10, 11, 13, 15, 17, 19, 23, 27, 31,
-                                      35, 43, 51, 59, 67, 83, 99, 115, 131, 163, 195, 227, 258};
-__constant__ uint8_t kLenExtra[29] = {0, 0, 0, 0, 0, 0, 0, 0, 1, 1, 1, 1, 2, 2, 2, 2, 3, 3, 3, 3, 4, 4, 4, 4, 5, 5, 5, 5, 0};
-__constant__ uint16_t kDistBase[30] = {1, 2, 3, 4, 5, 7, 9, 13, 17, 25, 33, 49, 65, 97, 129, 193, 257, 385, 513, 769,
-                                       1025, 1537, 2049, 3073, 4097, 6145, 8193, 12289, 16385, 24577};
-__constant__ uint8_t kClOrder[19] = {16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15};
-__constant__ uint8_t kDistExtra[30] = {0, 0, 0, 0, 1, 1, 2, 2, 3, 3, 4, 4, 5, 5, 6, 6, 7, 7, 8, 8, 9, 9, 10, 10, 11, 11, 12, 12, 13, 13};
-
-__device__ __forceinline__ int len_code(int len) {  // 3..258 -> 0..28
-    int c = 0;
-    while (c < 28 && kLenBase[c + 1] <= len) ++c;
-    return c;
-}
-__device__ __forceinline__ int dist_code(int d) {  // 1..32768 -> 0..29
-    int c = 0;
-    while (c < 29 && kDistBase[c + 1] <= d) ++c;
-    return c;
-}
-__device__ __forceinline__ int rdl(int v, int i) { return __builtin_amdgcn_readlane(v, i); }
 
 // -------------------------------------------------------------------------------- pack
 // Thread t of segment workgroup: 16 consecutive predictor bytes (17 reordered bytes), one 16-byte
@@ -180,21 +150,6 @@ struct View {
         return __builtin_amdgcn_alignbyte(w[1], w[0], (uint32_t)(o & 3));
     }
 };
-__device__ __forceinline__ void stage_view(const uint8_t* __restrict__ F, int64_t N, int64_t b0, uint8_t* lds, int lane) {
-    for (int k = lane; k < kView / 16; k += 64) {
-        const int64_t g = b0 + 16 * k;
-        uint4 v;
-        if (g >= 0 && g + 16 <= N) {
-            v = *reinterpret_cast<const uint4*>(F + g);
-        } else {
-            uint8_t t[16];
-#pragma unroll
-            for (int j = 0; j < 16; ++j) t[j] = (g + j >= 0 && g + j < N) ? F[g + j] : 0;
-            __builtin_memcpy(&v, t, 16);
-        }
-        *reinterpret_cast<uint4*>(lds + 16 * k) = v;
-    }
-}
 // Length of the match at p (view A) against p - dist (view B), at most maxlen.
 __device__ __forceinline__ int match_len(const View& A, const View& B, int64_t p, int64_t dist, int maxlen) {
     int l = 0;
@@ -244,7 +199,7 @@ __global__ __launch_bounds__(64 * kLzWaves) void k_exrw_lz77(const Img* __restri
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
         V[k].p = views[wave][k];
-        stage_view(F, N, V[k].b0, views[wave][k], lane);
+        stage_view(F, N, V[k].b0, views[wave][k], lane, kView);
     }
     uint32_t* SH = s_h[wave];
     for (int i = lane; i < kNLL + kND; i += 64) SH[i] = 0;
@@ -253,7 +208,7 @@ __global__ __launch_bounds__(64 * kLzWaves) void k_exrw_lz77(const Img* __restri
     __builtin_amdgcn_wave_barrier();
     uint16_t* T = tok + seg * kSlots;
     uint32_t xbits = 0;  // length / distance extra bits of the segment's matches (lane 0)
-    uint32_t nt = 0;
+    uint32_t nt = 0, nm = 0;  // token slots, matches (not used here)
     int64_t pos = s0;  // first position not yet covered by a token
     for (int64_t p0 = s0; p0 < s1; p0 += 64) {
         const int64_t q = p0 + lane;
@@ -294,37 +249,7 @@ __global__ __launch_bounds__(64 * kLzWaves) void k_exrw_lz77(const Img* __restri
                 }
             }
         }
-        const uint64_t cmask = __ballot(best >= 3);
-        const int wend = (int)min((int64_t)64, s1 - p0);  // live lanes of this window
-        while (pos < p0 + wend) {  // wave-uniform
-            const int li = (int)(pos - p0);
-            uint64_t m = cmask & (~0ull << li);
-            int mi = m ? __ffsll((unsigned long long)m) - 1 : 64;
-            while (mi + 1 < wend && rdl(best, mi + 1) > rdl(best, mi)) {
-                m &= m - 1;
-                mi = __ffsll((unsigned long long)m) - 1;
-            }
-            const int le = min(mi, wend);
-            if (lane >= li && lane < le) {  // the literal run li .. le-1
-                T[nt + (lane - li)] = (uint16_t)lit;
-                atomicAdd(&SH[lit], 1u);
-            }
-            nt += (uint32_t)(le - li);
-            pos = p0 + le;
-            if (mi < wend) {  // the match at lane mi
-                const int len = rdl(best, mi), dist = rdl(bd, mi);
-                if (lane == 0) {
-                    T[nt] = (uint16_t)(0x4000u | (uint32_t)(len - 3));
-                    T[nt + 1] = (uint16_t)(0x8000u | (uint32_t)(dist - 1));
-                    const int lc = len_code(len), dc = dist_code(dist);
-                    SH[257 + lc] += 1u;
-                    SH[kNLL + dc] += 1u;
-                    xbits += kLenExtra[lc] + kDistExtra[dc];
-                }
-                nt += 2;
-                pos += len;
-            }
-        }
+        parse_window(best, bd, lit, lane, p0, s1, T, SH, nt, nm, pos, xbits);
     }
     if (lane == 0) {
         ntok[seg] = nt;
@@ -336,115 +261,6 @@ __global__ __launch_bounds__(64 * kLzWaves) void k_exrw_lz77(const Img* __restri
 }
 
 // ------------------------------------------------------------------------------ Huffman
-// The used symbols of freq[0..n) in (freq, symbol) ascending order, by rank counting over the
-// workgroup (the caller synchronises before and after).
-__device__ void rank_order(const uint32_t* freq, int n, uint16_t* order) {
-    for (int i = threadIdx.x; i < n; i += blockDim.x) {
-        const uint32_t f = freq[i];
-        if (!f) continue;
-        int r = 0;
-        for (int j = 0; j < n; ++j) {
-            const uint32_t gq = freq[j];
-            r += gq && (gq < f || (gq == f && j < i));
-        }
-        order[r] = (uint16_t)i;
-    }
-}
-// Code lengths for freq[0..n) limited to maxbits (Huffman by sorting + JPEG Annex K.3 "adjust
-// bits", which keeps the code complete). Single thread; presorted: order[] holds rank_order's.
-__device__ void huff_lengths(const uint32_t* freq, int n, int maxbits, uint8_t* len, uint16_t* order, uint32_t* wt,
-                             int16_t* parent, bool presorted) {
-    int m = 0;
-    for (int i = 0; i < n; ++i) {
-        len[i] = 0;
-        if (freq[i]) {
-            if (!presorted) order[m] = (uint16_t)i;
-            ++m;
-        }
-    }
-    if (m == 0) return;
-    if (m == 1) {
-        len[order[0]] = 1;
-        return;
-    }
-    for (int a = 1; a < m && !presorted; ++a) {  // insertion sort by (freq, symbol) ascending
-        const uint16_t v = order[a];
-        int b = a - 1;
-        while (b >= 0 && (freq[order[b]] > freq[v] || (freq[order[b]] == freq[v] && order[b] > v))) {
-            order[b + 1] = order[b];
-            --b;
-        }
-        order[b + 1] = v;
-    }
-    // two-queue Huffman: leaves 0..m-1 (sorted), internal nodes m..2m-2
-    for (int i = 0; i < m; ++i) wt[i] = freq[order[i]];
-    int li = 0, ii = m, in_end = m;
-    for (int k = 0; k < m - 1; ++k) {
-        int pick[2];
-        for (int q = 0; q < 2; ++q) {
-            if (li < m && (ii >= in_end || wt[li] <= wt[ii])) pick[q] = li++;
-            else pick[q] = ii++;
-        }
-        wt[in_end] = wt[pick[0]] + wt[pick[1]];
-        parent[pick[0]] = (int16_t)in_end;
-        parent[pick[1]] = (int16_t)in_end;
-        ++in_end;
-    }
-    uint32_t* dep = wt;  // depths top-down (a parent has a larger index than its children)
-    dep[in_end - 1] = 0;
-    for (int k = in_end - 2; k >= 0; --k) dep[k] = dep[parent[k]] + 1;
-    int bl[40];
-    for (int i = 0; i < 40; ++i) bl[i] = 0;
-    int maxd = 0;
-    for (int i = 0; i < m; ++i) {
-        const int dd = dep[i] > 39 ? 39 : (int)dep[i];
-        ++bl[dd];
-        maxd = dd > maxd ? dd : maxd;
-    }
-    for (int i = maxd; i > maxbits; --i) {  // Annex K.3 Adjust_BITS
-        while (bl[i] > 0) {
-            int j = i - 2;
-            while (j > 1 && bl[j] == 0) --j;
-            bl[i] -= 2;
-            bl[i - 1] += 1;
-            bl[j + 1] += 2;
-            bl[j] -= 1;
-        }
-    }
-    int k = m - 1;  // most frequent symbols get the shortest codes
-    for (int l = 1; l <= maxbits; ++l)
-        for (int cq = 0; cq < bl[l]; ++cq) len[order[k--]] = (uint8_t)l;
-}
-__device__ void canon_codes(const uint8_t* len, int n, uint16_t* code) {  // RFC 1951 3.2.2, bit-reversed
-    int bl[16] = {0};
-    for (int i = 0; i < n; ++i) ++bl[len[i]];
-    bl[0] = 0;
-    int next[16];
-    int c = 0;
-    for (int b = 1; b < 16; ++b) {
-        c = (c + bl[b - 1]) << 1;
-        next[b] = c;
-    }
-    for (int i = 0; i < n; ++i) {
-        const int l = len[i];
-        code[i] = 0;
-        if (!l) continue;
-        const uint32_t v = (uint32_t)next[l]++;
-        code[i] = (uint16_t)(__brev(v) >> (32 - l));
-    }
-}
-struct BitW {
-    uint32_t* w;
-    uint32_t n = 0;  // bits written
-    __device__ void put(uint32_t v, int nb) {
-        if (!nb) return;
-        const uint32_t s = n & 31;
-        w[n >> 5] |= v << s;
-        if (s + nb > 32) w[(n >> 5) + 1] |= v >> (32 - s);
-        n += nb;
-    }
-};
-
 // One workgroup per deflate block. Thread 0 builds the codes and the header (deterministic, tiny);
 // then the workgroup computes the bits of each of the block's segments from its symbol counts and
 // the code lengths (k_exrw_scan turns them into offsets).
@@ -485,16 +301,7 @@ __global__ __launch_bounds__(64) void k_exrw_huff(const Img* __restrict__ imgs, 
             for (int i = 0; i < kND; ++i)
                 if (f_d[i]) f_d[i] = max(1u, f_d[i] >> sh);
         }
-        // at least two codes per tree keeps every code complete
-        int u = 0;
-        for (int i = 0; i < kNLL; ++i) u += f_ll[i] != 0;
-        if (u < 2) f_ll[f_ll[0] ? 1 : 0] = 1;
-        u = 0;
-        for (int i = 0; i < kND; ++i) u += f_d[i] != 0;
-        if (u < 2) {
-            if (!f_d[0]) f_d[0] = 1;
-            if (!f_d[1]) f_d[1] = 1;
-        }
+        pad_block_counts(f_ll, f_d);
     }
     __syncthreads();
     rank_order(f_ll, kNLL, order);
@@ -574,7 +381,7 @@ __global__ __launch_bounds__(64) void k_exrw_huff(const Img* __restrict__ imgs, 
         while (hclen > 4 && l_cl[kClOrder[hclen - 1]] == 0) --hclen;
         BitW bw{B.hdr};
         bw.put(K.last ? 1u : 0u, 1);  // BFINAL
-        bw.put(2u, 2);  // BTYPE = dynamic
+        bw.put(2u, 2);                // BTYPE = dynamic
         bw.put((uint32_t)(hlit - 257), 5);
         bw.put((uint32_t)(hdist - 1), 5);
         bw.put((uint32_t)(hclen - 4), 4);
@@ -661,64 +468,6 @@ __global__ __launch_bounds__(256) void k_exrw_layout(const Img* __restrict__ img
 }
 
 // --------------------------------------------------------------------------------- emit
-// Token slot -> (bits, count), LSB-first: a literal; or, at a match's length slot, code, length
-// extra, distance code, distance extra (at most 48 bits); a distance slot emits nothing.
-__device__ __forceinline__ uint64_t token_code(const BlockCodes& B, uint32_t t, uint32_t tnext, int& nb) {
-    if (t < 256) {
-        nb = B.ll_len[t];
-        return B.ll_code[t];
-    }
-    if (t & 0x8000u) {
-        nb = 0;
-        return 0;
-    }
-    const int len = (int)(t & 255) + 3, dist = (int)(tnext & 0x7FFFu) + 1;
-    const int lc = len_code(len), dc = dist_code(dist);
-    uint64_t v = B.ll_code[257 + lc];
-    int n = B.ll_len[257 + lc];
-    v |= (uint64_t)(len - kLenBase[lc]) << n;
-    n += kLenExtra[lc];
-    v |= (uint64_t)B.d_code[dc] << n;
-    n += B.d_len[dc];
-    v |= (uint64_t)(dist - kDistBase[dc]) << n;
-    nb = n + kDistExtra[dc];
-    return v;
-}
-__device__ __forceinline__ void or_bits(uint32_t* w, unsigned long long bitpos, uint64_t v, int nb) {
-    if (!nb) return;
-    const unsigned long long wi = bitpos >> 5;
-    const int sh = (int)(bitpos & 31);
-    const uint64_t hi = sh ? (v >> (32 - sh)) : (v >> 32);  // the bits above word wi
-    atomicOr(w + wi, (uint32_t)(v << sh));
-    if (sh + nb > 32) atomicOr(w + wi + 1, (uint32_t)hi);
-    if (sh + nb > 64) atomicOr(w + wi + 2, (uint32_t)(hi >> 32));
-}
-// The segment's bits OR-ed into W (word 0 = the word holding bit `pos`'s word base; zeroed): each
-// round of 64 tokens gets bit offsets from a wave prefix sum.
-__device__ __forceinline__ void emit_segment(uint32_t* W, unsigned long long pos, const BlockCodes& B, const uint16_t* T,
-                                             uint32_t nt, bool head, bool eob, int lane) {
-    if (head) {  // the block header: its words, shifted into place
-        const uint32_t hb = B.hdr_bits;
-        for (uint32_t i = lane; i * 32 < hb; i += 64) {
-            const int n = (int)min(32u, hb - i * 32);
-            or_bits(W, pos + i * 32, n == 32 ? B.hdr[i] : (B.hdr[i] & ((1u << n) - 1u)), n);
-        }
-        pos += hb;
-    }
-    for (uint32_t i0 = 0; i0 < nt; i0 += 64) {
-        const uint32_t i = i0 + lane;
-        int nb = 0;
-        uint64_t v = 0;
-        if (i < nt) v = token_code(B, T[i], i + 1 < nt ? T[i + 1] : 0u, nb);
-        uint32_t inc;
-        using WScan = rocprim::warp_scan<uint32_t, 64>;
-        typename WScan::storage_type wst;
-        WScan().inclusive_scan((uint32_t)nb, inc, wst);
-        or_bits(W, pos + inc - nb, v, nb);
-        pos += (uint32_t)rdl((int)inc, 63);
-    }
-    if (eob && lane == 0) or_bits(W, pos, B.ll_code[256], B.ll_len[256]);
-}
 // One wave per segment: its bits are built in the wave's LDS image of its output words and leave
 // with coalesced stores -- the two boundary words (shared with the neighbouring segments) with
 // atomicOr into the zeroed stream workspace. A segment whose bits exceed the image ORs straight
@@ -759,13 +508,13 @@ __global__ __launch_bounds__(256) void k_exrw_emit(const Img* __restrict__ imgs,
     const int nw = (int)min((unsigned long long)kEmitWords + 1, wl - w0 + 1);
     const uint16_t* T = tok + seg * kSlots;
     if (nw > kEmitWords) {
-        emit_segment(out + w0, o0 & 31, B, T, ntok[seg], head, eob, lane);
+        emit_segment(out + w0, o0 & 31, B, nullptr, 0, T, ntok[seg], head, eob, lane);
         return;
     }
     uint32_t* W = img[wave];
     for (int i = lane; i < nw; i += 64) W[i] = 0;
     __builtin_amdgcn_wave_barrier();
-    emit_segment(W, o0 & 31, B, T, ntok[seg], head, eob, lane);
+    emit_segment(W, o0 & 31, B, nullptr, 0, T, ntok[seg], head, eob, lane);
     __builtin_amdgcn_wave_barrier();
     for (int i = lane; i < nw; i += 64) {
         const uint32_t v = W[i];

@@ -23,6 +23,8 @@
 //   k_png_segbits    bits per segment -> (scan) bit offsets
 //   k_png_emit       one lane per segment: LSB-first bit packing of its tokens at its offset
 //   k_png_crc*       CRC-32 of the IDAT chunk: per-segment table CRCs combined by x^(8n) shifts
+// The deflate back end (tables, Huffman code lengths and codes, token bits, window parse, bit
+// packing) is icx_deflate_core.h / icx_deflate_wave.h, shared with icx_exrw.hip.
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 
@@ -31,12 +33,15 @@
 #include <cstring>
 #include <vector>
 
+#include "icx_deflate_wave.h"
 #include "icx_internal.h"
 #include "icx_mem.h"
 
 namespace icx {
 
 namespace png {
+
+using namespace deflate;  // the deflate back end shared with icx_exrw.hip
 
 #ifndef ICX_PNG_SEG
 #define ICX_PNG_SEG 4096
@@ -45,10 +50,7 @@ constexpr int kSeg = ICX_PNG_SEG;     // LZ77 / emit segment (bytes of the filte
 constexpr int kSlots = kSeg + 8;      // token slots per segment: up to kSeg - 1 literals + a match
                                       // overhanging the segment end (16-byte multiple)
 constexpr int kSegPerBlock = 262144 / kSeg;  // 256 KiB deflate blocks (lodepng's size at this scale, :1830)
-constexpr int kNLL = 286, kND = 30;   // literal/length and distance alphabets
-constexpr int kHdrWords = 96;         // per-block header bit buffer (<= 3072 bits)
 constexpr int kCrcSeg = 1024;         // CRC-32 segment, one lane each
-constexpr uint32_t kAdlerMod = 65521;
 enum { kGrey = 0, kRGB = 2, kPalette = 3, kGreyAlpha = 4, kRGBA = 6 };
 
 struct Stats {
@@ -69,36 +71,6 @@ struct Mode {
     int64_t lb;                        // bytes per (padded) row
     int npal;
     uint32_t pal[256];                 // RGBA packed r | g<<8 | b<<16 | a<<24
-};
-
-// ---- deflate tables (RFC 1951 3.2.5)
-__constant__ uint16_t kLenBase[29] = {3, 4, 5, 6, 7, 8, 9, 10, 11, 13, 15, 17, 19, 23, 27, 31,
-                                      35, 43, 51, 59, 67, 83, 99, 115, 131, 163, 195, 227, 258};
-__constant__ uint8_t kLenExtra[29] = {0, 0, 0, 0, 0, 0, 0, 0, 1, 1, 1, 1, 2, 2, 2, 2, 3, 3, 3, 3, 4, 4, 4, 4, 5, 5, 5, 5, 0};
-__constant__ uint16_t kDistBase[30] = {1, 2, 3, 4, 5, 7, 9, 13, 17, 25, 33, 49, 65, 97, 129, 193, 257, 385, 513, 769,
-                                       1025, 1537, 2049, 3073, 4097, 6145, 8193, 12289, 16385, 24577};
-__constant__ uint8_t kClOrder[19] = {16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15};
-__constant__ uint8_t kDistExtra[30] = {0, 0, 0, 0, 1, 1, 2, 2, 3, 3, 4, 4, 5, 5, 6, 6, 7, 7, 8, 8, 9, 9, 10, 10, 11, 11, 12, 12, 13, 13};
-
-__device__ __forceinline__ int len_code(int len) {  // 3..258 -> 0..28
-    int c = 0;
-    while (c < 28 && kLenBase[c + 1] <= len) ++c;
-    return c;
-}
-__device__ __forceinline__ int dist_code(int d) {  // 1..32768 -> 0..29
-    int c = 0;
-    while (c < 29 && kDistBase[c + 1] <= d) ++c;
-    return c;
-}
-
-struct BlockCodes {
-    uint16_t ll_code[kNLL];  // bit-reversed (LSB-first emission)
-    uint8_t ll_len[kNLL];
-    uint16_t d_code[kND];
-    uint8_t d_len[kND];
-    uint32_t hdr[kHdrWords];  // header bits, LSB-first
-    uint32_t hdr_bits;
-    uint32_t pad_;
 };
 
 __device__ __forceinline__ uint32_t required_bits(uint32_t v) {  // :3349-3355
@@ -466,26 +438,6 @@ struct SegView {
         return __builtin_amdgcn_alignbyte(w[1], w[0], (uint32_t)(o & 3));
     }
 };
-__device__ __forceinline__ void stage_view(const uint8_t* __restrict__ F, int64_t N, int64_t b0, uint8_t* lds, int lane,
-                                           int nbytes = kStage) {
-    for (int k = lane; k < nbytes / 16; k += 64) {
-        const int64_t g = b0 + 16 * k;
-        uint4 v;
-        if (g >= 0 && g + 16 <= N) {
-            v = *reinterpret_cast<const uint4*>(F + g);
-        } else {
-            uint8_t t[16];
-#pragma unroll
-            for (int j = 0; j < 16; ++j) t[j] = (g + j >= 0 && g + j < N) ? F[g + j] : 0;
-            __builtin_memcpy(&v, t, 16);
-        }
-        *reinterpret_cast<uint4*>(lds + 16 * k) = v;
-    }
-}
-// A lane's value at a wave-uniform lane index: v_readlane into a scalar register (__shfl is an LDS
-// permute, and its round trip sat on the parse's serial chain)
-__device__ __forceinline__ int rdl(int v, int i) { return __builtin_amdgcn_readlane(v, i); }
-
 // Length of the match at p against p - dist, at most maxlen: four bytes per step, the first
 // differing byte from the lowest set bit of the XOR.
 __device__ __forceinline__ int match_len(const SegView& V, int64_t p, int64_t dist, int maxlen) {
@@ -540,8 +492,8 @@ __global__ __launch_bounds__(256) void k_png_lz77(const uint8_t* __restrict__ F,
         V.nearp = views[wave][0];
         V.farp = views[wave][1];
         __builtin_amdgcn_wave_barrier();
-        stage_view(F, N, V.nb0, views[wave][0], lane);
-        stage_view(F, N, V.fb0, views[wave][1], lane);
+        stage_view(F, N, V.nb0, views[wave][0], lane, kStage);
+        stage_view(F, N, V.fb0, views[wave][1], lane, kStage);
         __builtin_amdgcn_wave_barrier();
         // Adler-32 partials: sum b, sum (N - g) b (reduced mod 65521 at the end)
         uint64_t a1 = 0, a2 = 0;
@@ -583,40 +535,7 @@ __global__ __launch_bounds__(256) void k_png_lz77(const uint8_t* __restrict__ F,
                     }
                 }
             }
-            const uint64_t cmask = __ballot(best >= 3);
-            const int wend = (int)min((int64_t)64, s1 - p0);  // live lanes of this window
-            while (pos < p0 + wend) {  // wave-uniform
-                const int li = (int)(pos - p0);
-                uint64_t m = cmask & (~0ull << li);
-                int mi = m ? __ffsll((unsigned long long)m) - 1 : 64;
-                // lazy evaluation (zlib's deflate_slow): a match start whose successor has a
-                // longer match becomes a literal, and the successor is considered in turn
-                while (mi + 1 < wend && rdl(best, mi + 1) > rdl(best, mi)) {
-                    m &= m - 1;
-                    mi = __ffsll((unsigned long long)m) - 1;
-                }
-                const int le = min(mi, wend);
-                if (lane >= li && lane < le) {  // the literal run li .. le-1
-                    T[nt + (lane - li)] = (uint16_t)lit;
-                    atomicAdd(&SH[lit], 1u);
-                }
-                nt += (uint32_t)(le - li);
-                pos = p0 + le;
-                if (mi < wend) {  // the match at lane mi
-                    const int len = rdl(best, mi), dist = rdl(bd, mi);
-                    if (lane == 0) {
-                        T[nt] = (uint16_t)(0x4000u | (uint32_t)(len - 3));    // match: length slot,
-                        T[nt + 1] = (uint16_t)(0x8000u | (uint32_t)(dist - 1));  // then distance slot
-                        const int lc = len_code(len), dc = dist_code(dist);
-                        SH[257 + lc] += 1u;
-                        SH[kNLL + dc] += 1u;
-                        xbits += kLenExtra[lc] + kDistExtra[dc];
-                    }
-                    nt += 2;
-                    nm += 1;
-                    pos += len;
-                }
-            }
+            parse_window(best, bd, lit, lane, p0, s1, T, SH, nt, nm, pos, xbits);
         }
         if (lane == 0) {
             ntok[seg] = nt;
@@ -832,123 +751,6 @@ __global__ __launch_bounds__(256) void k_png_seam_apply(const uint8_t* __restric
 }
 
 // ------------------------------------------------------------------------------ Huffman
-// Code lengths for freq[0..n) limited to maxbits (Huffman by sorting + JPEG Annex K.3
-// "adjust bits" length limiting, which keeps the code complete). Single thread; scratch in LDS.
-// The used symbols of freq[0..n) in (freq, symbol) ascending order, by rank counting over all
-// lanes of the workgroup (blockDim.x lanes; the caller synchronises before and after).
-__device__ void rank_order(const uint32_t* freq, int n, uint16_t* order) {
-    for (int i = threadIdx.x; i < n; i += blockDim.x) {
-        const uint32_t f = freq[i];
-        if (!f) continue;
-        int r = 0;
-        for (int j = 0; j < n; ++j) {
-            const uint32_t g = freq[j];
-            r += g && (g < f || (g == f && j < i));
-        }
-        order[r] = (uint16_t)i;
-    }
-}
-
-// presorted: order[] already holds the used symbols sorted (rank_order).
-__device__ void huff_lengths(const uint32_t* freq, int n, int maxbits, uint8_t* len, uint16_t* order, uint32_t* wt,
-                             int16_t* parent, int* nused_out, bool presorted = false) {
-    int m = 0;
-    for (int i = 0; i < n; ++i) {
-        len[i] = 0;
-        if (freq[i]) {
-            if (!presorted) order[m] = (uint16_t)i;
-            ++m;
-        }
-    }
-    *nused_out = m;
-    if (m == 0) return;
-    if (m == 1) {
-        len[order[0]] = 1;
-        return;
-    }
-    // insertion sort by (freq, symbol) ascending
-    for (int a = 1; a < m && !presorted; ++a) {
-        const uint16_t v = order[a];
-        int b = a - 1;
-        while (b >= 0 && (freq[order[b]] > freq[v] || (freq[order[b]] == freq[v] && order[b] > v))) {
-            order[b + 1] = order[b];
-            --b;
-        }
-        order[b + 1] = v;
-    }
-    // two-queue Huffman: leaves 0..m-1 (sorted), internal nodes m..2m-2
-    for (int i = 0; i < m; ++i) wt[i] = freq[order[i]];
-    int li = 0, ii = m, in_end = m;
-    for (int k = 0; k < m - 1; ++k) {
-        int pick[2];
-        for (int q = 0; q < 2; ++q) {
-            if (li < m && (ii >= in_end || wt[li] <= wt[ii])) pick[q] = li++;
-            else pick[q] = ii++;
-        }
-        wt[in_end] = wt[pick[0]] + wt[pick[1]];
-        parent[pick[0]] = (int16_t)in_end;
-        parent[pick[1]] = (int16_t)in_end;
-        ++in_end;
-    }
-    // depths top-down (a parent always has a larger index than its children); wt is reused
-    uint32_t* dep = wt;
-    dep[in_end - 1] = 0;
-    for (int k = in_end - 2; k >= 0; --k) dep[k] = dep[parent[k]] + 1;
-    int bl[40];
-    for (int i = 0; i < 40; ++i) bl[i] = 0;
-    int maxd = 0;
-    for (int i = 0; i < m; ++i) {
-        const int dd = dep[i] > 39 ? 39 : (int)dep[i];
-        ++bl[dd];
-        maxd = dd > maxd ? dd : maxd;
-    }
-    for (int i = maxd; i > maxbits; --i) {  // Annex K.3 Adjust_BITS
-        while (bl[i] > 0) {
-            int j = i - 2;
-            while (j > 1 && bl[j] == 0) --j;
-            bl[i] -= 2;
-            bl[i - 1] += 1;
-            bl[j + 1] += 2;
-            bl[j] -= 1;
-        }
-    }
-    // most frequent symbols get the shortest codes: walk sorted order from the top
-    int k = m - 1;
-    for (int l = 1; l <= maxbits; ++l)
-        for (int c = 0; c < bl[l]; ++c) len[order[k--]] = (uint8_t)l;
-}
-
-__device__ void canon_codes(const uint8_t* len, int n, uint16_t* code) {  // RFC 1951 3.2.2, bit-reversed
-    int bl[16] = {0};
-    for (int i = 0; i < n; ++i) ++bl[len[i]];
-    bl[0] = 0;
-    int next[16];
-    int c = 0;
-    for (int b = 1; b < 16; ++b) {
-        c = (c + bl[b - 1]) << 1;
-        next[b] = c;
-    }
-    for (int i = 0; i < n; ++i) {
-        const int l = len[i];
-        code[i] = 0;
-        if (!l) continue;
-        const uint32_t v = (uint32_t)next[l]++;
-        code[i] = (uint16_t)(__brev(v) >> (32 - l));
-    }
-}
-
-struct BitW {
-    uint32_t* w;
-    uint32_t n = 0;  // bits written
-    __device__ void put(uint32_t v, int nb) {
-        if (!nb) return;
-        const uint32_t s = n & 31;
-        w[n >> 5] |= v << s;
-        if (s + nb > 32) w[(n >> 5) + 1] |= v >> (32 - s);
-        n += nb;
-    }
-};
-
 // Deflate blocks: k_png_lz77 counts symbols per 256 KiB base block; consecutive base blocks
 // with few tokens between them share one deflate block (one header), as zlib's blocks end at
 // kBlockTokens symbols (lit_bufsize at memLevel 8) -- highly compressible input would otherwise
@@ -1005,25 +807,14 @@ __global__ __launch_bounds__(64) void k_png_huff(const uint32_t* __restrict__ hi
     BlockCodes& B = bc[blk];
     for (int i = threadIdx.x; i < kHdrWords; i += 64) B.hdr[i] = 0;
     __syncthreads();
-    if (threadIdx.x == 0) {  // at least two codes per tree keeps every code complete
-        int u = 0;
-        for (int i = 0; i < kNLL; ++i) u += f_ll[i] != 0;
-        if (u < 2) f_ll[f_ll[0] ? 1 : 0] = 1;
-        u = 0;
-        for (int i = 0; i < kND; ++i) u += f_d[i] != 0;
-        if (u < 2) {
-            if (!f_d[0]) f_d[0] = 1;
-            if (!f_d[1]) f_d[1] = 1;
-        }
-    }
+    if (threadIdx.x == 0) pad_block_counts(f_ll, f_d);
     __syncthreads();
     rank_order(f_ll, kNLL, order);
     rank_order(f_d, kND, order_d);
     __syncthreads();
     if (threadIdx.x != 0) return;
-    int used;
-    huff_lengths(f_ll, kNLL, 15, l_ll, order, wt, parent, &used, true);
-    huff_lengths(f_d, kND, 15, l_d, order_d, wt, parent, &used, true);
+    huff_lengths(f_ll, kNLL, 15, l_ll, order, wt, parent, true);
+    huff_lengths(f_d, kND, 15, l_d, order_d, wt, parent, true);
     canon_codes(l_ll, kNLL, B.ll_code);
     canon_codes(l_d, kND, B.d_code);
     for (int i = 0; i < kNLL; ++i) B.ll_len[i] = l_ll[i];
@@ -1089,13 +880,13 @@ __global__ __launch_bounds__(64) void k_png_huff(const uint32_t* __restrict__ hi
     }
     uint8_t l_cl[19];
     uint16_t c_cl[19];
-    huff_lengths(f_cl, 19, 7, l_cl, order, wt, parent, &used);
+    huff_lengths(f_cl, 19, 7, l_cl, order, wt, parent, false);
     canon_codes(l_cl, 19, c_cl);
     int hclen = 19;
     while (hclen > 4 && l_cl[kClOrder[hclen - 1]] == 0) --hclen;
     BitW bw{B.hdr};
     bw.put(glast == nblk - 1 ? 1u : 0u, 1);  // BFINAL
-    bw.put(2u, 2);                          // BTYPE = dynamic
+    bw.put(2u, 2);                // BTYPE = dynamic
     bw.put((uint32_t)(hlit - 257), 5);
     bw.put((uint32_t)(hdist - 1), 5);
     bw.put((uint32_t)(hclen - 4), 4);
@@ -1150,141 +941,12 @@ __global__ __launch_bounds__(256) void k_png_segbits(int64_t nseg, const uint16_
     }
 }
 
-// Token slot i -> (bits, count), LSB-first: a literal; or, at a match's length slot, code, length
-// extra, distance code, distance extra (at most 15 + 5 + 15 + 13 = 48 bits); a distance slot
-// emits nothing (its match's length slot took it).
-__device__ __forceinline__ uint64_t token_code(const BlockCodes& B, uint32_t t, uint32_t tnext, int& nb) {
-    if (t < 256) {
-        nb = B.ll_len[t];
-        return B.ll_code[t];
-    }
-    if (t & 0x8000u) {
-        nb = 0;
-        return 0;
-    }
-    const int len = (int)(t & 255) + 3, dist = (int)(tnext & 0x7FFFu) + 1;
-    const int lc = len_code(len), dc = dist_code(dist);
-    uint64_t v = B.ll_code[257 + lc];
-    int n = B.ll_len[257 + lc];
-    v |= (uint64_t)(len - kLenBase[lc]) << n;
-    n += kLenExtra[lc];
-    v |= (uint64_t)B.d_code[dc] << n;
-    n += B.d_len[dc];
-    v |= (uint64_t)(dist - kDistBase[dc]) << n;
-    nb = n + kDistExtra[dc];
-    return v;
-}
-
-// One wave per segment: each round of 64 tokens gets bit offsets from a wave prefix sum and is
-// OR-ed into the wave's LDS image of the segment's output words (aligned to the output's word
-// grid), which then leaves with coalesced stores -- the two boundary words (shared with the
-// neighbouring segments) with atomicOr. Segments whose bits exceed the LDS image (pathological
-// token mixes only) OR their words straight into the output.
+// One wave per segment: its tokens are packed (emit_segment_runs) into the wave's LDS image of the
+// segment's output words (aligned to the output's word grid), which then leaves with coalesced
+// stores -- the two boundary words (shared with the neighbouring segments) with atomicOr. Segments
+// whose bits exceed the LDS image (pathological token mixes only) OR their words straight into the
+// output (emit_segment).
 constexpr int kEmitWords = 2048;  // 64 Kbit per wave (a 4 KiB segment averages ~22 Kbit)
-__device__ __forceinline__ void or_bits(uint32_t* w, unsigned long long bitpos, uint64_t v, int nb) {
-    if (!nb) return;
-    const unsigned long long wi = bitpos >> 5;
-    const int sh = (int)(bitpos & 31);
-    const uint64_t hi = sh ? (v >> (32 - sh)) : (v >> 32);  // the bits above word wi
-    atomicOr(w + wi, (uint32_t)(v << sh));
-    if (sh + nb > 32) atomicOr(w + wi + 1, (uint32_t)hi);
-    if (sh + nb > 64) atomicOr(w + wi + 2, (uint32_t)(hi >> 32));
-}
-// The segment's bits into W (word 0 = output word w0; zeroed), starting at bit `pos`: its nh
-// re-parsed head slots Hd, then its own slots T[0 .. nt).
-__device__ __forceinline__ void emit_segment(uint32_t* W, unsigned long long pos, const BlockCodes& B,
-                                             const uint16_t* Hd, uint32_t nh, const uint16_t* T, uint32_t nt,
-                                             bool head, bool eob, int lane) {
-    if (head) {  // the block header: its words, shifted into place
-        const uint32_t hb = B.hdr_bits;
-        for (uint32_t i = lane; i * 32 < hb; i += 64) {
-            const int n = (int)min(32u, hb - i * 32);
-            or_bits(W, pos + i * 32, n == 32 ? B.hdr[i] : (B.hdr[i] & ((1u << n) - 1u)), n);
-        }
-        pos += hb;
-    }
-    const uint32_t n = nh + nt;
-    for (uint32_t i0 = 0; i0 < n; i0 += 64) {
-        const uint32_t i = i0 + lane;
-        int nb = 0;
-        uint64_t v = 0;
-        if (i < nh) v = token_code(B, Hd[i], i + 1 < nh ? Hd[i + 1] : 0u, nb);
-        else if (i < n) v = token_code(B, T[i - nh], i + 1 < n ? T[i + 1 - nh] : 0u, nb);
-        uint32_t inc;  // inclusive scan of nb over the wave (rocprim's DPP cross-lane scan)
-        using WScan = rocprim::warp_scan<uint32_t, 64>;
-        typename WScan::storage_type wst;  // empty for the cross-lane implementation
-        WScan().inclusive_scan((uint32_t)nb, inc, wst);
-        or_bits(W, pos + inc - nb, v, nb);
-        pos += (uint32_t)rdl((int)inc, 63);
-    }
-    if (eob && lane == 0) or_bits(W, pos, B.ll_code[256], B.ll_len[256]);
-}
-// emit_segment for the wave's LDS image (round 6): each lane takes kRun consecutive token slots,
-// one wave prefix sum of the lanes' bit totals places them, and each lane packs its slots into
-// whole words in a register -- the words it fills alone are plain stores, only its first and last
-// (shared with the neighbouring lanes) are atomicOr. (One slot per lane OR-ed every token into LDS
-// with up to three atomics, several lanes on each word.)
-constexpr int kRun = 8;
-__device__ __forceinline__ void emit_segment_runs(uint32_t* W, unsigned long long pos, const BlockCodes& B,
-                                                  const uint16_t* Hd, uint32_t nh, const uint16_t* T, uint32_t nt,
-                                                  bool head, bool eob, int lane) {
-    if (head) {  // the block header: its words, shifted into place
-        const uint32_t hb = B.hdr_bits;
-        for (uint32_t i = lane; i * 32 < hb; i += 64) {
-            const int n = (int)min(32u, hb - i * 32);
-            or_bits(W, pos + i * 32, n == 32 ? B.hdr[i] : (B.hdr[i] & ((1u << n) - 1u)), n);
-        }
-        pos += hb;
-    }
-    const uint32_t n = nh + nt;
-    auto slot = [&](uint32_t i) -> uint32_t { return i < nh ? (uint32_t)Hd[i] : (uint32_t)T[i - nh]; };
-    for (uint32_t i0 = 0; i0 < n; i0 += 64 * kRun) {
-        const uint32_t ib = i0 + (uint32_t)lane * kRun;
-        uint64_t v[kRun];
-        int nb[kRun];
-        uint32_t tot = 0;
-#pragma unroll
-        for (int r = 0; r < kRun; ++r) {
-            const uint32_t i = ib + r;
-            nb[r] = 0;
-            v[r] = i < n ? token_code(B, slot(i), i + 1 < n ? slot(i + 1) : 0u, nb[r]) : 0;
-            tot += (uint32_t)nb[r];
-        }
-        uint32_t inc;  // inclusive scan of the lanes' bit totals (rocprim's DPP cross-lane scan)
-        using WScan = rocprim::warp_scan<uint32_t, 64>;
-        typename WScan::storage_type wst;
-        WScan().inclusive_scan(tot, inc, wst);
-        const unsigned long long s0 = pos + inc - tot;
-        uint32_t wi = (uint32_t)(s0 >> 5);
-        int an = (int)(s0 & 31);
-        uint64_t acc = 0;
-        bool first = true;
-        auto put = [&](uint32_t piece, int k) {  // k <= 32 bits; an < 32 before
-            acc |= (uint64_t)piece << an;
-            an += k;
-            if (an >= 32) {
-                if (first) atomicOr(W + wi, (uint32_t)acc);  // (shared with the lane before)
-                else W[wi] = (uint32_t)acc;
-                first = false;
-                ++wi;
-                acc >>= 32;
-                an -= 32;
-            }
-        };
-#pragma unroll
-        for (int r = 0; r < kRun; ++r) {
-            if (nb[r] > 32) {
-                put((uint32_t)v[r], 32);
-                put((uint32_t)(v[r] >> 32), nb[r] - 32);
-            } else if (nb[r] > 0) {
-                put((uint32_t)v[r], nb[r]);
-            }
-        }
-        if (tot && an > 0) atomicOr(W + wi, (uint32_t)acc);  // (shared with the lane after)
-        pos += (uint32_t)rdl((int)inc, 63);
-    }
-    if (eob && lane == 0) or_bits(W, pos, B.ll_code[256], B.ll_len[256]);
-}
 
 // The file's layout once the deflate stream's length is known, on the device (k_png_size): the
 // rest of the encode reads it there, so no host read-back sits between the deflate and the file.
