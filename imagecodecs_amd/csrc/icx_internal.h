@@ -83,11 +83,13 @@ struct GwOut {
     uint64_t g0;     // first block start at or after the lane's start: pack_state(pos, b, 0)
     int32_t k;       // blocks the lane stored (slots 0 .. k-1)
     int32_t ds[3];   // lane-local DC sums over them (predictors relative to g0)
-    int32_t err;     // slot of the first block whose decode failed (INT32_MAX: none)
+    int32_t err;     // slot of the first block whose decode failed since the last record (INT32_MAX: none)
     int32_t chunk0;  // first overflow chunk (pool block / kGwChunk), -1: none
-    int32_t nrec;    // block-start records (RecState, b = 0: MCU starts) taken after g0
-    int32_t over;    // the pool ran out: the image goes sequential
+    int32_t nrec;    // block-start records (RecState: MCU starts) taken after g0
+    int16_t over;    // the pool ran out: the image goes sequential
+    int16_t rerr;    // some record carries a failure of the stretch before it (RecState::b = its slot + 1)
 };
+static_assert(sizeof(GwOut) == 40, "the lane records size the workspace (ws_per_slot)");
 struct GcRec {
     int32_t chunk0;  // the count lane's blocks: a chain of pool chunks (-1: none)
     int32_t pad_;

@@ -980,8 +980,9 @@ __global__ __launch_bounds__(NL) void k_spec_write(int want, int n, const Desc* 
 //  1. the lead: from `lead` bits before the lane's start to its first block start at or after
 //     the start (g0), with the scan tables (runs of symbols per lookup; nothing is stored). The
 //     scan tables sit in the LDS the slots use later, so they cost no occupancy.
-//  2. k_spec_write's loop from g0 -- one lookup per lane per iteration, completed blocks
-//     assembled in LDS slots and flushed by the whole wave -- storing every block until the
+//  2. k_spec_write's loop from g0 -- one refill and one lookup per lane per iteration, and a second
+//     lookup of the same block for lanes whose window needs no refill (write_step_more); completed
+//     blocks assembled in LDS slots and flushed by the whole wave -- storing every block until the
 //     first block start at or after the lane's end (the exit), recording MCU starts for the
 //     count lanes' splice.
 #ifndef ICX_GW_MINW  // (timing experiments: waves per SIMD k_gw_lane is compiled for)
@@ -1067,6 +1068,8 @@ __global__ __launch_bounds__(NL, ICX_GW_MINW) void k_gw_lane(int n, const Desc* 
         // in SGPRs, and a lane reads its bit by lane_in (round 6: 6 VALU per lookup fewer than
         // per-lane bools, whose ballots and opaque selects cost two each).
         uint64_t lm = wave_ballot(act);
+        // (over: bit 0 the pool ran out for this lane, bit 1 some record carries a failure, GwOut::rerr --
+        // kept in one register: the budget is 104 VGPRs, see the CHK note above)
         int32_t k = 0, err = INT32_MAX, chunk = -1, chunk0 = -1, over = 0, addr = 0;
         // Lane-local DC sums rotated with the current block's component: dc0 is the sum of block
         // b's component, dc1 / dc2 those of the next two in MCU order. An MCU runs through the
@@ -1104,7 +1107,9 @@ __global__ __launch_bounds__(NL, ICX_GW_MINW) void k_gw_lane(int n, const Desc* 
                     if (lane_in(rcm)) {
                         RecState e;
                         e.rel = u - pre;
-                        e.b = 0;
+                        e.b = err == INT32_MAX ? 0 : err + 1;  // (gw_guess_err: failures are noted per stretch)
+                        over |= err == INT32_MAX ? 0 : 2;
+                        err = INT32_MAX;
                         e.cnt = k;
                         e.ds[0] = dc0;  // (b == 0: the rotation is at component 0)
                         e.ds[1] = dc1;
@@ -1126,15 +1131,15 @@ __global__ __launch_bounds__(NL, ICX_GW_MINW) void k_gw_lane(int n, const Desc* 
                         chunk = c;
                         nxt = c * kGwChunk;
                     } else {
-                        over = 1;
+                        over |= 1;
                         nxt = scratch;
                     }
-                    left = over ? INT32_MAX : kGwChunk;
+                    left = (over & 1) ? INT32_MAX : kGwChunk;
                 }
-                any_over = any_over || wave_any(over != 0);
+                any_over = any_over || wave_any((over & 1) != 0);
             }
             addr = own_bs ? nxt : addr;
-            nxt = add_lane_bit(nxt, any_over ? om & ~wave_ballot(over != 0) : om);  // nxt += own_bs && !over
+            nxt = add_lane_bit(nxt, any_over ? om & ~wave_ballot((over & 1) != 0) : om);  // nxt += own_bs && !over
             left = sub_lane_bit(left, om);                                           // left -= own_bs
             // one lookup (every lane: the reader moves on idle lanes too, see k_spec_write)
             const uint32_t u0 = r.used;
@@ -1152,6 +1157,19 @@ __global__ __launch_bounds__(NL, ICX_GW_MINW) void k_gw_lane(int n, const Desc* 
             // block is a discarded speculative one or the image fails)
             sv[slot_elem(threadIdx.x, o.n2)] = (int16_t)(o.w2 ? o.v2 : 0);
             sv[slot_elem(threadIdx.x, o.n1)] = (int16_t)(bs ? cell : o.v1);
+            // A second lookup of the same block where the block did not end and the window still
+            // holds more than 32 bits (write_step_more: no refill, so one refill per iteration
+            // stays the reader's slot rule): 1.75 lookups per iteration on photographic streams
+            // for one iteration's masks, refill, DC rotation and flush. Block starts stay at the
+            // top of an iteration; k and bcur are those of the first lookup (the same block).
+            if (z != 0 && r.nb > 32) {
+                const uint32_t u1 = r.used;
+                const WriteOut o2 = write_step_more(r, T, H, S, b, z, CHK ? eb.near(u1) : false);
+                const bool fail2 = CHK ? eb.fail(u1, o2.err, r.used) : o2.err;
+                err = lane_in(lm) && fail2 && err == INT32_MAX ? k : err;
+                sv[slot_elem(threadIdx.x, o2.n2)] = (int16_t)(o2.w2 ? o2.v2 : 0);
+                sv[slot_elem(threadIdx.x, o2.n1)] = (int16_t)o2.v1;
+            }
             const uint64_t m = wave_ballot(z == 0) & lm;
             const bool done = lane_in(m);
             k = add_lane_bit(k, m);  // k += done
@@ -1201,9 +1219,10 @@ __global__ __launch_bounds__(NL, ICX_GW_MINW) void k_gw_lane(int n, const Desc* 
             g.err = err;
             g.chunk0 = chunk0;
             g.nrec = nrec;
-            g.over = over;
+            g.over = (int16_t)(over & 1);
+            g.rerr = (int16_t)(over >> 1);
             gwo[f] = g;
-            if (over) atomicOr(&s.err, kSpecGiveUp);
+            if (over & 1) atomicOr(&s.err, kSpecGiveUp);
         }
     }
 }

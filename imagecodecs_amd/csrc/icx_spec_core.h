@@ -440,10 +440,10 @@ ICX_HD int32_t extend_mag(uint32_t raw, uint32_t nbx) {
 // One step-table lookup (icx_step.h) for block b's DC (dc) or AC code: refill, peek, entry
 // (table chosen by T.bsel[b]); long codes behind wave-uniform branches whose bodies are selects
 // (a wave where no lane needs one skips it): the pool, and the canonical walk for windows the
-// pool does not hold (pathological tables only).
+// pool does not hold (pathological tables only). step_entry is the lookup without the refill, for
+// a window that already holds 32 valid bits (nb >= 32).
 template <class Tab>
-ICX_HD uint32_t step_lookup(Reader& r, const Tab& T, const Huff* H, const Sel& S, int b, bool dc, uint32_t& x) {
-    r.refill();
+ICX_HD uint32_t step_entry(const Reader& r, const Tab& T, const Huff* H, const Sel& S, int b, bool dc, uint32_t& x) {
     x = (uint32_t)(r.buf >> 32);
     uint32_t e = T.look_b(b, dc, x);
     if (wave_any((e & kStSlow) != 0u)) {
@@ -455,6 +455,11 @@ ICX_HD uint32_t step_lookup(Reader& r, const Tab& T, const Huff* H, const Sel& S
         e = (e & kStSub) ? ep : e;
     }
     return e;
+}
+template <class Tab>
+ICX_HD uint32_t step_lookup(Reader& r, const Tab& T, const Huff* H, const Sel& S, int b, bool dc, uint32_t& x) {
+    r.refill();
+    return step_entry(r, T, H, S, b, dc, x);
 }
 static_assert(sizeof(ScanTab::bsel) / sizeof(ScanTab::bsel[0]) == kSpecMaxBpm, "bsel covers every block of an MCU");
 template <class Tab>
@@ -509,11 +514,9 @@ struct WriteOut {
     // a discarded speculative one, or a failing image).
     int n1, n2;
 };
-template <class Tab>
-ICX_HD WriteOut write_step(Reader& r, const Tab& T, const Huff* H, const Sel& S, int& b, int& z, bool near_err) {
-    const bool dc = z == 0;
-    uint32_t x;
-    const uint32_t e = step_lookup(r, T, H, S, b, dc, x);
+// The decode of one write-table entry e at peek x in the state (b, z): what write_step and
+// write_step_more share.
+ICX_HD WriteOut write_decode(Reader& r, uint32_t e, uint32_t x, const Sel& S, int& b, int& z, bool near_err) {
     const uint32_t tot1 = st_tot1(e), nbx1 = st_nbx1(e), zad1 = st_zad1(e);
     const uint32_t tot2 = (e >> 16) & 15u, nbx2 = (e >> 20) & 15u, zad2 = (e >> 24) & 31u, eob2 = (e >> 29) & 1u;
     const bool pair = tot2 != 0u && (uint32_t)z + zad1 + zad2 + eob2 <= 64u && !near_err;
@@ -539,6 +542,22 @@ ICX_HD WriteOut write_step(Reader& r, const Tab& T, const Huff* H, const Sel& S,
     b = endb ? bn : b;
     z = endb ? 0 : zn;
     return o;
+}
+template <class Tab>
+ICX_HD WriteOut write_step(Reader& r, const Tab& T, const Huff* H, const Sel& S, int& b, int& z, bool near_err) {
+    uint32_t x;
+    const uint32_t e = step_lookup(r, T, H, S, b, z == 0, x);
+    return write_decode(r, e, x, S, b, z, near_err);
+}
+// A further AC lookup of the block in progress (z != 0) out of the window the last write_step left,
+// without a refill: only when that window still holds more than 32 bits (r.nb > 32), which is what
+// a refill guarantees -- so the refill left out would have moved nothing, and the reader's slot
+// phase (one refill per lane-loop iteration) is untouched. Same entry, same decode, same WriteOut.
+template <class Tab>
+ICX_HD WriteOut write_step_more(Reader& r, const Tab& T, const Huff* H, const Sel& S, int& b, int& z, bool near_err) {
+    uint32_t x;
+    const uint32_t e = step_entry(r, T, H, S, b, false, x);
+    return write_decode(r, e, x, S, b, z, near_err);
 }
 
 // ------------------------------------------------------------------------ lane logic
@@ -878,12 +897,24 @@ ICX_HD int32_t gw_lane_total(const GwOut& g, const GcRec& c, const RecState* rec
 // Block index (lane-relative) of the first true-path decode failure, INT32_MAX if none: the
 // count lane's blocks, then the guess lane's after the splice (its blocks before are not on the
 // true path).
+// A guess lane notes its first failure per stretch between records: record i carries in b the first
+// failed block since record i - 1, plus 1 (0: none; g.rerr: some record carries one), and g.err the
+// first one since the last record.
+// So a failure of the lane's unsynchronised start, before the splice, cannot hide a later one on
+// the true path. (One first failure per lane did: a stream whose error followed, in the same lane,
+// a failure of the speculative decode before the splice was reported as decoded.)
+ICX_HD int32_t gw_guess_err(const GwOut& g, const RecState* rec, int from) {  // the first from record `from` on
+    if (g.rerr != 0)  // (the records are read only for a lane that noted one)
+        for (int i = from; i < g.nrec; ++i)
+            if (rec[i].b != 0) return rec[i].b - 1;
+    return g.err;
+}
 ICX_HD int32_t gw_lane_err(const GwOut& g, const GcRec& c, const RecState* rec) {
-    if (c.m == -2) return g.err;
+    if (c.m == -2) return gw_guess_err(g, rec, 0);
     if (c.err != INT32_MAX) return c.err;
-    if (c.m < 0 || g.err == INT32_MAX) return INT32_MAX;
-    const int32_t m0 = rec[c.m].cnt;
-    return g.err >= m0 ? c.c + (g.err - m0) : INT32_MAX;
+    if (c.m < 0) return INT32_MAX;
+    const int32_t e = gw_guess_err(g, rec, c.m + 1), m0 = rec[c.m].cnt;
+    return e != INT32_MAX && e >= m0 ? c.c + (e - m0) : INT32_MAX;
 }
 // Pool block of guess slot s of a lane: the static region, then the chained overflow chunks.
 struct GwSlots {
