@@ -1363,7 +1363,7 @@ __global__ __launch_bounds__(512) void k_gw_count(int n, const Desc* __restrict_
 // re-derive the following lanes until one is synchronised at its start or splices.
 __global__ __launch_bounds__(64) void k_gw_repair(int n, const Desc* __restrict__ desc, SpecImg* __restrict__ spec,
                                                   const StepSet* __restrict__ steps, const uint8_t* __restrict__ U,
-                                                  uint64_t* __restrict__ X, const uint64_t* __restrict__ Y,
+                                                  uint64_t* __restrict__ X, uint64_t* __restrict__ Y,
                                                   const GwOut* __restrict__ gwo, const RecState* __restrict__ rec,
                                                   int16_t* __restrict__ ac, int32_t* __restrict__ dcv,
                                                   int32_t* __restrict__ chunk_next, unsigned long long* __restrict__ pool_next,
@@ -1411,6 +1411,10 @@ __global__ __launch_bounds__(64) void k_gw_repair(int n, const Desc* __restrict_
             gw_count_lane(desc[i], s, steps[i], U, k, f, X[f - 1], gwo[f], rec + f * kRec, ac, dcv, chunk_next, pool_next,
                           pool_cap, crec, &ex, &give_up, RS, nrst);
             if (give_up) { give_up_walk(); return; }
+            // (the lane's count exit, as k_gw_count leaves it: k_gw_tail enters the padding from the
+            // last lane's -- left at the first pass's value, or unset for a lane the first pass found
+            // synchronised, the blocks past an early end of data were decoded from the wrong place)
+            Y[f] = ex;
             if (crec[f].m >= 0 || k + 1 == s.nsub || ex == X[f]) break;
             X[f] = ex;
         }
