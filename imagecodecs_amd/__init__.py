@@ -20,7 +20,9 @@ callers (tests, bench): it binds the C ABI with ctypes and offers
   * ``TgaBatch``                  -- device-resident batched .tga decode
   * ``Context.gif_decode``        -- Image::readGif (codecs.cpp:507-542): first frame, wave LZW decode
   * ``GifBatch``                  -- device-resident batched .gif decode
-  * ``Image``                     -- ImageCodecs::Image (codecs.h:16-103) for .jpg/.jpeg/.png/.hdr/.exr/.tga/.gif
+  * ``Context.tiff_decode``       -- Image::readTiff (codecs.cpp:1439-1484): strips / tiles, one wave per chunk
+  * ``TiffBatch``                 -- device-resident batched .tif decode
+  * ``Image``                     -- ImageCodecs::Image (codecs.h:16-103) for .jpg/.jpeg/.png/.hdr/.exr/.tga/.gif/.tif
 
 There is deliberately no CPU fallback: if libicx.so is missing or no GPU is visible every
 entry point raises ``ICXError``.
@@ -42,7 +44,9 @@ __all__ = ["ICXError", "Context", "Batch", "HdrBatch", "Image", "lib", "build", 
            "checksum64", "multi_shard", "TgaBatch", "tga_probe", "tga_encode_bound", "TGA_OK", "TGA_BAD_HEADER",
            "TGA_UNSUPPORTED", "TGA_NO_IMAGE", "TGA_MALFORMED", "TGA_TRUNCATED", "TGA_TOO_LARGE", "TGA_INVALID_ARGUMENT",
            "TGA_INTERNAL_ERR", "GifBatch", "gif_probe", "GIF_OK", "GIF_NOT_GIF", "GIF_BAD_HEADER", "GIF_MALFORMED",
-           "GIF_BAD_DATA", "GIF_TRUNCATED", "GIF_TOO_LARGE", "GIF_INTERNAL_ERR"]
+           "GIF_BAD_DATA", "GIF_TRUNCATED", "GIF_TOO_LARGE", "GIF_INTERNAL_ERR", "TiffBatch", "tiff_probe", "TIFF_OK",
+           "TIFF_NOT_TIFF", "TIFF_BAD_HEADER", "TIFF_UNSUPPORTED", "TIFF_MALFORMED", "TIFF_BAD_DATA", "TIFF_TRUNCATED",
+           "TIFF_TOO_LARGE", "TIFF_INTERNAL_ERR"]
 
 OK, NO_JPEG, UNSUPPORTED, OUT_OF_MEM, INTERNAL_ERR, SYNTAX_ERROR = range(6)  # nj_result_t
 RESULT_NAMES = ["NJ_OK", "NJ_NO_JPEG", "NJ_UNSUPPORTED", "NJ_OUT_OF_MEM", "NJ_INTERNAL_ERR", "NJ_SYNTAX_ERROR"]
@@ -153,6 +157,12 @@ _SIGS = {
     "icx_gif_batch_destroy": (None, [_vp]),
     "icx_gif_batch_decode": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _vp]),
     "icx_gif_batch_stage_times": (_i32, [_vp, _vp, _vp, _i32]),
+    "icx_tiff_probe": (_i32, [_vp, _sz, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32)]),
+    "icx_tiff_decode": (_i32, [_vp, _vp, _sz, C.POINTER(_vp), C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32)]),
+    "icx_tiff_batch_create": (_vp, [_vp, _i32, _i32, _i32]),
+    "icx_tiff_batch_destroy": (None, [_vp]),
+    "icx_tiff_batch_decode": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _vp]),
+    "icx_tiff_batch_stage_times": (_i32, [_vp, _vp, _vp, _i32]),
     "icx_tga_encode_bound": (_sz, [_i32, _i32, _i32]),
     "icx_tga_save_to_memory": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, C.POINTER(_vp), C.POINTER(_sz)]),
     "icx_tga_save_to_file": (_i32, [_vp, C.c_char_p, _vp, _i32, _i32, _i32, _i32]),
@@ -183,6 +193,10 @@ TGA_INTERNAL_ERR = -1
 # icx_gif_result (include/icx.h): Image::readGif outcomes
 GIF_OK, GIF_NOT_GIF, GIF_BAD_HEADER, GIF_MALFORMED, GIF_BAD_DATA, GIF_TRUNCATED, GIF_TOO_LARGE = range(7)
 GIF_INTERNAL_ERR = -1
+# icx_tiff_result (include/icx.h): Image::readTiff outcomes
+(TIFF_OK, TIFF_NOT_TIFF, TIFF_BAD_HEADER, TIFF_UNSUPPORTED, TIFF_MALFORMED, TIFF_BAD_DATA, TIFF_TRUNCATED,
+ TIFF_TOO_LARGE) = range(8)
+TIFF_INTERNAL_ERR = -1
 
 WRITE_FUNC = C.CFUNCTYPE(None, C.c_void_p, C.c_void_p, C.c_int)
 
@@ -504,6 +518,22 @@ class Context:
             arr = np.frombuffer(C.string_at(out.value, n), np.uint8).reshape(h.value, w.value, 3).copy()
             lib().icx_free(out)
         return code, w.value, h.value, arr
+
+    def tiff_decode(self, data: bytes):
+        """Image::readTiff (codecs.cpp:1439-1484; contract in include/icx.h) on the GPU -> (code, w, h,
+        d, uint8 (h, w, d) or None); code is an icx_tiff_result."""
+        buf = C.create_string_buffer(bytes(data), max(1, len(data)))
+        out = C.c_void_p()
+        w, h, d = C.c_int(), C.c_int(), C.c_int()
+        code = lib().icx_tiff_decode(self._p, buf, len(data), C.byref(out), C.byref(w), C.byref(h), C.byref(d))
+        if code == TIFF_INTERNAL_ERR:
+            raise ICXError("icx_tiff_decode: " + _err(self._p))
+        arr = None
+        if out.value:
+            n = w.value * h.value * d.value
+            arr = np.frombuffer(C.string_at(out.value, n), np.uint8).reshape(h.value, w.value, d.value).copy()
+            lib().icx_free(out)
+        return code, w.value, h.value, d.value, arr
 
     def tga_encode(self, px, rle: bool = False):
         """Image::writeTga (codecs.cpp:1410-1437) on the GPU: uint8 (h, w) or (h, w, d), d in 1, 3, 4,
@@ -847,6 +877,14 @@ def gif_probe(data: bytes):
     return code, w.value, h.value
 
 
+def tiff_probe(data: bytes):
+    """Host IFD walk of the TIFF read -> (code, width, height, channels)."""
+    w, h, d = C.c_int(), C.c_int(), C.c_int()
+    buf = C.create_string_buffer(bytes(data), max(1, len(data)))
+    code = lib().icx_tiff_probe(buf, len(data), C.byref(w), C.byref(h), C.byref(d))
+    return code, w.value, h.value, d.value
+
+
 def tga_encode_bound(width: int, height: int, d: int) -> int:
     """icx_tga_encode_bound: 18 + w*h*(d+1), or 0 for arguments the write refuses."""
     return int(lib().icx_tga_encode_bound(width, height, d))
@@ -959,6 +997,40 @@ class GifBatch:
         return {names[i].decode(): float(ms[i]) for i in range(k)}
 
 
+class TiffBatch:
+    """Device-resident batched TIFF decode (icx_tiff_batch_*): image i is
+    d_data[d_offsets[i] .. + d_sizes[i]); its bytes at d_out + i*out_stride
+    (out_stride >= 4 * max_width * max_height), status in
+    d_status[i], {width, height, channels} in d_dims[3i..]."""
+
+    def __init__(self, ctx: Context, max_images: int, max_width: int, max_height: int):
+        self.ctx = ctx
+        self._p = lib().icx_tiff_batch_create(ctx.ptr, max_images, max_width, max_height)
+        if not self._p:
+            raise ICXError("icx_tiff_batch_create failed: " + _err(ctx.ptr))
+        self.max_images, self.max_width, self.max_height = max_images, max_width, max_height
+
+    def close(self):
+        if getattr(self, "_p", None):
+            lib().icx_tiff_batch_destroy(self._p)
+            self._p = None
+
+    def __del__(self):
+        self.close()
+
+    def decode_device(self, n, d_data, d_offsets, d_sizes, d_out, out_stride, d_status, d_dims, stream=0):
+        rc = lib().icx_tiff_batch_decode(self._p, n, d_data, d_offsets, d_sizes, d_out, out_stride,
+                                        d_status, d_dims, stream or None)
+        if rc != TIFF_OK:
+            raise ICXError(f"icx_tiff_batch_decode -> {rc}: {_err(self.ctx.ptr)}")
+
+    def stage_times(self) -> dict:
+        names = (C.c_char_p * 8)()
+        ms = (C.c_float * 8)()
+        k = lib().icx_tiff_batch_stage_times(self._p, names, ms, 8)
+        return {names[i].decode(): float(ms[i]) for i in range(k)}
+
+
 class HdrBatch:
     """Device-resident batched Radiance .hdr decode (icx_hdr_batch_*): image i is
     d_data[d_offsets[i] .. + d_sizes[i]); 4 floats per pixel at d_out + i*out_stride floats."""
@@ -997,7 +1069,8 @@ class Image:
     read()/write() dispatch on the lower-cased extension like Image::read/write
     (codecs.cpp:53-122): read .jpg/.jpeg (readJpg), .png (readPng: d = 4, type UBYTE) and .hdr
     (readHdr: d = 4, type FLOAT, the floats' bytes in pixels_), .exr, .tga (readTga: d = 1, 3 or
-    4, type UBYTE) and .gif (readGif: the first frame, d = 3, type UBYTE), write .jpg/.jpeg, .png, .exr,
+    4, type UBYTE), .gif (readGif: the first frame, d = 3, type UBYTE) and .tif/.tiff (readTiff: d = 1,
+    3 or 4, type UBYTE), write .jpg/.jpeg, .png, .exr,
     .tga (uncompressed) and .hdr (flat RGBE; d = 4 only). Other extensions raise ValueError (the
     reference's std::invalid_argument for unknown types)."""
 
@@ -1031,6 +1104,9 @@ class Image:
             return
         if ext == ".gif":
             self._read_gif(filepath)
+            return
+        if ext in (".tif", ".tiff"):
+            self._read_tiff(filepath)
             return
         if ext not in (".jpg", ".jpeg"):
             raise ValueError("Cannot parse filetype")
@@ -1085,6 +1161,17 @@ class Image:
         if code != GIF_OK:
             raise RuntimeError("Could not read image data")
         self.w_, self.h_, self.d_ = w, h, 3
+        self.pixels_ = px.reshape(-1).copy()
+        self.type_ = Image.UBYTE
+
+    def _read_tiff(self, filepath: str):
+        """readTiff (codecs.cpp:1439-1484): the first IFD, d = 1, 3 or 4, type UBYTE, rows top-down.
+        Every failure is Image::read's RuntimeError("Could not read image data")."""
+        data = open(filepath, "rb").read()
+        code, w, h, d, px = self.context().tiff_decode(data)
+        if code != TIFF_OK:
+            raise RuntimeError("Could not read image data")
+        self.w_, self.h_, self.d_ = w, h, d
         self.pixels_ = px.reshape(-1).copy()
         self.type_ = Image.UBYTE
 

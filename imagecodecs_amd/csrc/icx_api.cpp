@@ -1723,4 +1723,124 @@ int icx_gif_decode(icx_ctx* ctx, const uint8_t* data, size_t size, uint8_t** out
     return rc;
 }
 
+// --------------------------------------------------------- TIFF (Image::readTiff)
+struct icx_tiff_batch {
+    icx_ctx* ctx = nullptr;
+    TiffWs ws;
+    Blocks mem;  // the device memory ws points into
+    std::unique_ptr<EventHook> hook;
+};
+
+int icx_tiff_probe(const uint8_t* data, size_t size, int* w, int* h, int* d) {
+    int ww = 0, hh = 0, dd = 0, pw = 0, ph = 0;
+    const int rc = data ? tiff_probe(data, (int64_t)size, &ww, &hh, &dd, &pw, &ph) : ICX_TIFF_NOT_TIFF;
+    if (w) *w = rc == ICX_TIFF_OK ? ww : 0;
+    if (h) *h = rc == ICX_TIFF_OK ? hh : 0;
+    if (d) *d = rc == ICX_TIFF_OK ? dd : 0;
+    return rc;
+}
+
+icx_tiff_batch* icx_tiff_batch_create(icx_ctx* ctx, int max_images, int max_w, int max_h) {
+    // (images are one grid dimension; byte positions inside a chunk are 32-bit)
+    if (!ctx || max_images <= 0 || max_images > 65535 || max_w <= 0 || max_h <= 0 ||
+        (int64_t)max_w * max_h > ((int64_t)1 << 30)) {
+        if (ctx) ctx->err = "icx_tiff_batch_create: bad arguments";
+        return nullptr;
+    }
+    ICX_HIP(ctx, hipSetDevice(ctx->device), nullptr);
+    auto* b = new icx_tiff_batch();
+    b->ctx = ctx;
+    b->hook = std::make_unique<EventHook>();
+    if (!tiff_ws_alloc(b->ws, b->mem, ctx->device, max_images, max_w, max_h)) {
+        ctx->err = std::string("icx_tiff_batch_create: out of device memory: ") + hipGetErrorString(hipGetLastError());
+        delete b;
+        return nullptr;
+    }
+    return b;
+}
+
+void icx_tiff_batch_destroy(icx_tiff_batch* b) {
+    if (!b) return;
+    (void)hipSetDevice(b->ctx->device);
+    delete b;
+}
+
+int icx_tiff_batch_decode(icx_tiff_batch* b, int n, const uint8_t* d_data, const uint64_t* d_off, const uint64_t* d_size,
+                         uint8_t* d_out, uint64_t out_stride, int32_t* d_status, int32_t* d_dims, void* stream) {
+    if (!b) return ICX_TIFF_INTERNAL_ERR;
+    icx_ctx* ctx = b->ctx;
+    if (n < 0 || n > b->ws.max_images) { ctx->err = "icx_tiff_batch_decode: n exceeds batch capacity"; return ICX_TIFF_INTERNAL_ERR; }
+    if (n == 0) return ICX_TIFF_OK;
+    if (!d_data || !d_off || !d_size || !d_out || !d_status || !d_dims) { ctx->err = "null pointer"; return ICX_TIFF_INTERNAL_ERR; }
+    if (out_stride < 4ull * b->ws.max_w * b->ws.max_h) { ctx->err = "icx_tiff_batch_decode: out_stride too small"; return ICX_TIFF_INTERNAL_ERR; }
+    ICX_HIP(ctx, hipSetDevice(ctx->device), ICX_TIFF_INTERNAL_ERR);
+    hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
+    const RoctxRange range("icx_tiff_batch_decode");
+    b->hook->reset();
+    launch_tiff_decode(b->ws, n, d_data, d_off, d_size, d_out, out_stride, d_status, d_dims, st, b->hook.get());
+    ICX_HIP(ctx, hipGetLastError(), ICX_TIFF_INTERNAL_ERR);
+    return ICX_TIFF_OK;
+}
+
+int icx_tiff_batch_stage_times(const icx_tiff_batch* b, const char** names, float* ms, int cap) {
+    if (!b) return 0;
+    static const Stage order[3] = {kStParse, kStEntropy, kStConvert};
+    static const char* const label[3] = {"parse", "unpack", "render"};
+    float acc[kStCount];
+    b->hook->sum(acc);
+    for (int k = 0; k < 3 && k < cap; ++k) {
+        if (names) names[k] = label[k];
+        if (ms) ms[k] = acc[order[k]];
+    }
+    return 3;
+}
+
+int icx_tiff_decode(icx_ctx* ctx, const uint8_t* data, size_t size, uint8_t** out, int* w, int* h, int* d) {
+    if (out) *out = nullptr;
+    if (w) *w = 0;
+    if (h) *h = 0;
+    if (d) *d = 0;
+    if (!ctx || !out) return ICX_TIFF_INTERNAL_ERR;
+    int ww = 0, hh = 0, dd = 0, pw = 0, ph = 0;
+    const int prc = data ? tiff_probe(data, (int64_t)size, &ww, &hh, &dd, &pw, &ph) : ICX_TIFF_NOT_TIFF;
+    if (prc != ICX_TIFF_OK) return prc;  // container errors need no device work
+    ICX_HIP(ctx, hipSetDevice(ctx->device), ICX_TIFF_INTERNAL_ERR);
+    // a workspace for the size padded to whole chunks: every file the walk accepts fits its scratch
+    // (declared before the buffers: they are freed first, then the batch)
+    std::unique_ptr<icx_tiff_batch, void (*)(icx_tiff_batch*)> b(icx_tiff_batch_create(ctx, 1, pw, ph), icx_tiff_batch_destroy);
+    if (!b) return ICX_TIFF_INTERNAL_ERR;
+    const uint64_t nout = (uint64_t)ww * hh * dd, stride = nout;
+    Buf<uint8_t> d_in, d_out;
+    Buf<uint64_t> d_meta;
+    Buf<int32_t> d_res;
+    int rc = ICX_TIFF_INTERNAL_ERR;
+    const uint64_t meta[2] = {0, (uint64_t)size};
+    int32_t res[4] = {0, 0, 0, 0};
+    hipStream_t st = ctx->stream;
+    if (d_in.reserve(size) && d_out.reserve(stride) && d_meta.reserve(16) && d_res.reserve(16) &&
+        hipMemcpyAsync(d_in.p, data, size, hipMemcpyHostToDevice, st) == hipSuccess &&
+        hipMemcpyAsync(d_meta.p, meta, 16, hipMemcpyHostToDevice, st) == hipSuccess &&
+        (launch_tiff_decode(b->ws, 1, d_in.p, d_meta.p, d_meta.p + 1, d_out.p, stride, d_res.p, d_res.p + 1, st, nullptr),
+         hipGetLastError() == hipSuccess) &&
+        hipMemcpyAsync(res, d_res.p, 16, hipMemcpyDeviceToHost, st) == hipSuccess && hipStreamSynchronize(st) == hipSuccess) {
+        rc = res[0];
+        if (rc == ICX_TIFF_OK) {
+            uint8_t* hostp = (uint8_t*)std::malloc(nout);
+            if (hostp && hipMemcpy(hostp, d_out.p, nout, hipMemcpyDeviceToHost) == hipSuccess) {
+                *out = hostp;
+                if (w) *w = res[1];
+                if (h) *h = res[2];
+                if (d) *d = res[3];
+            } else {
+                std::free(hostp);
+                ctx->err = "icx_tiff_decode: host allocation or copy failed";
+                rc = ICX_TIFF_INTERNAL_ERR;
+            }
+        }
+    } else if (ctx->err.empty()) {
+        ctx->err = "icx_tiff_decode: HIP failure";
+    }
+    return rc;
+}
+
 }  // extern "C"

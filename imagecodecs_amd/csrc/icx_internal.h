@@ -388,6 +388,26 @@ void launch_gif_decode(const GifWs& ws, int n, const uint8_t* d_data, const uint
                        uint8_t* d_out, uint64_t out_stride, int32_t* d_status, int32_t* d_dims, hipStream_t st,
                        StageHook* hook);
 
+// TIFF read (icx_tiff.hip; Image::readTiff, codecs.cpp:1439-1484). Status codes: icx_tiff_core.h
+// kTiff* = include/icx.h ICX_TIFF_*.
+struct TiffDesc;
+struct TiffWs {
+    int max_images = 0, max_w = 0, max_h = 0;
+    int64_t slot = 0;            // bytes per image of scratch (tiff_scratch_slot: a multiple of 16)
+    int unpack_grid = 0;         // workgroups of k_tiff_unpack (from the device's CU count)
+    TiffDesc* desc = nullptr;    // [max_images]
+    int32_t* count = nullptr;    // [max_images] chunks of each image that parsed
+    int32_t* first = nullptr;    // [max_images + 1] their exclusive scan: the work list
+    uint32_t* next = nullptr;    // the work list's next untaken item (k_tiff_unpack)
+    uint8_t* scratch = nullptr;  // [max_images][slot] decompressed chunks, each in a room of its own
+};
+// pw, ph: the size padded to whole chunks
+int tiff_probe(const uint8_t* data, int64_t size, int* w, int* h, int* d, int* pw, int* ph);
+bool tiff_ws_alloc(TiffWs& ws, Blocks& mem, int device, int max_images, int max_w, int max_h);
+void launch_tiff_decode(const TiffWs& ws, int n, const uint8_t* d_data, const uint64_t* d_off, const uint64_t* d_size,
+                        uint8_t* d_out, uint64_t out_stride, int32_t* d_status, int32_t* d_dims, hipStream_t st,
+                        StageHook* hook);
+
 // ---- OpenEXR read (icx_exr.hip) ----
 // tinyexr's LoadEXRFromMemory; returns its code (-100: HIP failure, err says which).
 struct ExrWs;

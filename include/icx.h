@@ -635,6 +635,91 @@ int icx_gif_batch_decode(icx_gif_batch* b, int n, const uint8_t* d_data, const u
  * synchronises). Returns the number of stages. */
 int icx_gif_batch_stage_times(const icx_gif_batch* b, const char** names, float* ms, int cap);
 
+/* ---- TIFF read (Image::readTiff, codecs.cpp:1439-1484: libtiff's TIFFReadRGBAImage) ----------------
+ * Output: Type::UBYTE, rows top-down, the first IFD only, d channels:
+ *   Photometric 0 (MinIsWhite: a stored v gives 255 - v) and 1           d = 1
+ *   Photometric 2 (RGB) with SamplesPerPixel 3                          d = 3
+ *   Photometric 2 with SamplesPerPixel 4                                d = 4: the fourth sample as
+ *       stored, whatever ExtraSamples says, no premultiply (a deviation from TIFFReadRGBAImage)
+ *   Photometric 3 (palette)                                             d = 3: ColorMap SHORT >> 8, as
+ *       libtiff and PIL do (the reference would report d = 1)
+ * Accepted: classic TIFF ("II*\0" or "MM\0*"); BitsPerSample all 8, one per sample;
+ * SamplesPerPixel 1, 3 or 4; PlanarConfiguration 1, or 2 when SamplesPerPixel is 1; FillOrder 1;
+ * Orientation 1 or absent; SampleFormat 1 or absent; Compression 1, 5 (LZW), 8 and 32946 (zlib),
+ * 32773 (PackBits); Predictor 1 or 2, where 2 is honoured only with compression 5 / 8 / 32946 (as
+ * libtiff, the tag is ignored for uncompressed and PackBits data); strips (RowsPerStrip absent or
+ * larger than the height: one strip) or tiles of any positive TileWidth / TileLength, clipped at
+ * the right and bottom edges. BitsPerSample, ColorMap and SampleFormat are SHORT; every other tag
+ * read here may be SHORT or LONG. Unknown tags are ignored, entries need not be sorted, of two
+ * entries with one tag the later counts.
+ * Chunks: a strip or tile must decompress to rows_in_chunk x row_bytes (a strip's last chunk has
+ * fewer rows, a tile is always full size). Fewer bytes, or an invalid code, is BAD_DATA. LZW and
+ * PackBits stop at that count and ignore what follows (a stream needs no EOI; a PackBits packet
+ * or an LZW string running past the count is cut there). A zlib stream that inflates to MORE than
+ * that count is refused as BAD_DATA (what the inflate shared with the PNG and EXR reads does; its
+ * Adler-32 is checked); bytes after the zlib trailer are ignored. Uncompressed chunks may be longer
+ * than needed. A PackBits header byte of -128 is a no-op; a packet that runs past the chunk's
+ * input is BAD_DATA. A chunk whose bytes reach past the file is TRUNCATED. An image fails as a
+ * whole, with the code of its lowest-numbered failing chunk; a failed image yields no pixels.
+ * LZW (compression 5): MSB first, Clear = 256, EOI = 257, first entry 258, "early change":
+ * counting codes after a Clear from 1, codes 1..254 are 9 bits, ..766 are 10, ..1790 are 11, then
+ * 12. BAD_DATA: a first code that is not Clear; a first code after a Clear that is not a literal;
+ * a code above the next free entry; a table that would grow past entry 4094 without a Clear (at
+ * most 3838 codes may follow a Clear before the next one); EOI or the end of
+ * the chunk before the last byte. Old-style LSB-first LZW (first byte 0, low bit of the second
+ * set) is UNSUPPORTED.
+ * The checks run in this order: the header; the IFD's entries in file order (type and count of a
+ * known tag -> MALFORMED, its array outside the file -> TRUNCATED); then BAD_HEADER, UNSUPPORTED,
+ * MALFORMED and TOO_LARGE as listed below; then the chunks. */
+enum icx_tiff_result {
+    ICX_TIFF_OK = 0,
+    ICX_TIFF_NOT_TIFF = 1,    /* bad magic, or fewer than 8 bytes                                     */
+    ICX_TIFF_BAD_HEADER = 2,  /* IFD offset or entry table outside the file; width or height zero or
+                                 missing; no chunk offsets                                            */
+    ICX_TIFF_UNSUPPORTED = 3, /* BigTIFF (magic 43); BitsPerSample not 8 (also absent: its default is
+                                 1) or not one per sample; other compression, photometric, planar,
+                                 orientation, fill order, sample format or predictor; SamplesPerPixel
+                                 2 or above 4; old-style LZW                                          */
+    ICX_TIFF_MALFORMED = 4,   /* a tag of the wrong type or count; offset and byte-count arrays of
+                                 different length or not the chunk count; missing byte counts, tile
+                                 size or a zero RowsPerStrip; a palette without a ColorMap of 768
+                                 SHORTs; strip (273, 279) and tile (322..325) tags both present       */
+    ICX_TIFF_BAD_DATA = 5,    /* as defined under Chunks and LZW                                      */
+    ICX_TIFF_TRUNCATED = 6,   /* a tag array, the ColorMap or a chunk reaches past the file           */
+    ICX_TIFF_TOO_LARGE = 7,   /* larger than the batch workspace; more than 4096 chunks; more than
+                                 2^30 pixels (also when padded to whole chunks); a chunk of 2^31
+                                 bytes or more                                                        */
+    ICX_TIFF_INTERNAL_ERR = -1 /* HIP failure (see icx_last_error)                                    */
+};
+/* The IFD walk (host only, no GPU touched): width, height and channels, or the code the walk gives
+ * (every code above except BAD_DATA and a chunk's TRUNCATED / UNSUPPORTED, which the decode finds). */
+int icx_tiff_probe(const uint8_t* data, size_t size, int* width, int* height, int* channels);
+/* One image, host in / host out: *out receives a malloc()'d width*height*channels byte buffer
+ * (free with icx_free), null unless ICX_TIFF_OK. A code the probe gives returns without touching
+ * the GPU. */
+int icx_tiff_decode(icx_ctx* ctx, const uint8_t* data, size_t size, uint8_t** out, int* width, int* height,
+                    int* channels);
+/* Device-resident batch: image i = d_data[d_offsets[i] .. + d_sizes[i]), output bytes at
+ * d_out + i*out_stride (out_stride >= 4*max_width*max_height), per-image status in d_status[i]
+ * and {width, height, channels} in d_dims[3i..] (zero for a failed image, whose slot is
+ * unspecified). Asynchronous on hip_stream (NULL = the context's stream), no host read-back.
+ * Returns ICX_TIFF_OK or ICX_TIFF_INTERNAL_ERR. max_images <= 65535, max_width * max_height <= 2^30.
+ * Scratch: decompressed chunks wait in a slot of S = round16(4*max_width*max_height) +
+ * 16*min(4096, max_width*max_height) bytes per image, each chunk in a room of its full size
+ * (TileWidth*TileLength*SamplesPerPixel, or RowsPerStrip*width*SamplesPerPixel with RowsPerStrip
+ * clamped to the height) rounded up to 16 bytes. Padded tiles can exceed width*height*channels: an
+ * image wider than max_width, higher than max_height, or whose rooms together exceed S is
+ * ICX_TIFF_TOO_LARGE (whatever its compression). */
+typedef struct icx_tiff_batch icx_tiff_batch;
+icx_tiff_batch* icx_tiff_batch_create(icx_ctx* ctx, int max_images, int max_width, int max_height);
+void icx_tiff_batch_destroy(icx_tiff_batch* b);
+int icx_tiff_batch_decode(icx_tiff_batch* b, int n, const uint8_t* d_data, const uint64_t* d_offsets,
+                          const uint64_t* d_sizes, uint8_t* d_out, uint64_t out_stride, int32_t* d_status,
+                          int32_t* d_dims, void* hip_stream);
+/* Milliseconds per stage of the last icx_tiff_batch_decode ("parse", "unpack", "render";
+ * synchronises). Returns the number of stages. */
+int icx_tiff_batch_stage_times(const icx_tiff_batch* b, const char** names, float* ms, int cap);
+
 #ifdef __cplusplus
 }
 #endif

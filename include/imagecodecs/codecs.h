@@ -23,6 +23,12 @@
  *               local palettes, transparency, interlace, frames smaller than or clipped by the
  *               canvas. A file the read refuses (codes in include/icx.h) leaves pixels_ null and
  *               read() throws "Could not read image data". write(".gif") stays outside this path.
+ *               ".tif"/".tiff" decode the first IFD of a TIFF, 8 bits per sample, rows top-down, on
+ *               the GPU (readTiff, codecs.cpp:1439-1484 -> icx_tiff_decode): strips or tiles,
+ *               uncompressed, LZW, zlib or PackBits, predictor 2, grey (either polarity), palette,
+ *               RGB and RGBA. channels() is 1, 3 or 4. A file the read refuses (codes in
+ *               include/icx.h) leaves pixels_ null and read() throws "Could not read image data".
+ *               write(".tif") stays outside this path.
  *   write(path) -- ".jpg"/".jpeg" encode with tiny_jpeg quality 3 semantics (writeJpg,
  *                  codecs.cpp:851-854 -> icx_tje_encode_to_file, byte-identical stream).
  *               ".png" encodes with png_encoder::saveToFile semantics (writePng,
@@ -87,6 +93,12 @@
  * extension is walked as a sub-block chain, the graphic control values coming from its first
  * sub-block when that has at least 4 bytes; a file that ends inside a header, table, extension or
  * data sub-block the decode still needs is refused (the reference ignores short reads).
+ * TIFF read (contract in include/icx.h): a palette file gives channels() == 3, the ColorMap's
+ * entries >> 8 as libtiff maps them (the reference would report 1 for its SamplesPerPixel over
+ * TIFFReadRGBAImage's packed pixels); a fourth sample passes through as stored, without
+ * TIFFReadRGBAImage's premultiply; and the bytes of a pixel are R, G, B, A in this order (the
+ * reference's (currPix >> j) & 0xff shifts by j bits where 8 * j was meant, codecs.cpp:1471-1477).
+ * Only 8-bit samples are read.
  *
  * Header-only; link with -L<repo>/imagecodecs_amd/lib -licx. One icx context per process
  * (device ICX_DEVICE, default 0), created on first use and serialised by a mutex -- the
@@ -373,6 +385,38 @@ class Image {
         type_ = Type::UBYTE;
     }
 
+    // readTiff (codecs.cpp:1439-1484): the first IFD, d = 1, 3 or 4, Type::UBYTE, rows top-down,
+    // decoded on the GPU (icx_tiff_decode). A failure leaves pixels_ null, and read() throws "Could
+    // not read image data" (:85-88).
+    void readTiff(const std::string& path) {
+        std::FILE* f = std::fopen(path.c_str(), "rb");
+        std::vector<uint8_t> buf;
+        if (f) {
+            uint8_t chunk[1 << 16];
+            size_t k;
+            while ((k = std::fread(chunk, 1, sizeof chunk, f)) > 0) buf.insert(buf.end(), chunk, chunk + k);
+            std::fclose(f);
+        }
+        auto& P = detail::icx_process();
+        std::lock_guard<std::mutex> lock(P.mu);
+        uint8_t* out = nullptr;
+        int w = 0, h = 0, d = 0;
+        const int rc = icx_tiff_decode(P.get(), buf.data(), buf.size(), &out, &w, &h, &d);
+        delete[] pixels_;
+        pixels_ = nullptr;
+        w_ = h_ = d_ = 0;
+        if (rc == ICX_TIFF_INTERNAL_ERR) throw std::runtime_error(std::string("icx_tiff_decode: ") + icx_last_error(P.get()));
+        if (rc != ICX_TIFF_OK) return;
+        const size_t n = (size_t)w * h * d;
+        pixels_ = new unsigned char[n ? n : 1];
+        if (n) std::memcpy(pixels_, out, n);
+        icx_free(out);
+        w_ = w;
+        h_ = h;
+        d_ = d;
+        type_ = Type::UBYTE;
+    }
+
     // writeTga (codecs.cpp:1410-1437): uncompressed, d = 1, 3, 4. As in the reference nothing is
     // thrown: a failure -- no usable GPU included -- only prints the message; the result stays
     // queryable.
@@ -476,6 +520,7 @@ public:
         else if (ext == ".exr") readExr(filepath);
         else if (ext == ".tga") readTga(filepath);
         else if (ext == ".gif") readGif(filepath);
+        else if (ext == ".tif" || ext == ".tiff") readTiff(filepath);
         else throw std::invalid_argument("Cannot parse filetype");
         if (pixels_ == nullptr) throw std::runtime_error("Could not read image data");
     }

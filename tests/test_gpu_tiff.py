@@ -1,0 +1,329 @@
+"""GPU TIFF read (Image::readTiff, codecs.cpp:1439-1484; contract in include/icx.h) against the
+serial restatement in tests/tiffutil.py: result code, size, channels and pixels of every file equal
+the restatement's exactly -- the reference's data/test.tif, PIL-written files, and the crafted
+corpus (strips and tiles, each compression with and without predictor, widths around the wave and
+the 16-byte store, chunk offsets at every residue, LZW width steps and clears, PackBits packet
+sizes, deflate block kinds, every status)."""
+import io
+import os
+import zlib
+
+import numpy as np
+import pytest
+
+import imagecodecs_amd as icx
+import tiffutil as T
+
+pytestmark = pytest.mark.gpu
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+FIXTURE = open(os.path.join(GOLDEN, "tiff", "test.tif"), "rb").read()
+KTIFF_WIN = 2048   # icx_tiff.hip kTiffWin: chunk bytes per window load of the LZW wave
+KTIFF_SEG = 1024   # kTiffSeg: pixels per row segment of k_tiff_render
+STAGES = {"parse", "unpack", "render"}
+ALL_COMPS = (1, 5, 8, 32773)
+
+
+@pytest.fixture(scope="module")
+def ctx():
+    c = icx.Context(0)
+    yield c
+    c.close()
+
+
+def _same(got, data, name="", **limits):
+    ref = T.decode(data, **limits)
+    assert got[0] == ref[0], (name, got[0], ref[0])
+    if ref[0] == T.OK:
+        assert got[1:4] == ref[1:4], name
+        np.testing.assert_array_equal(got[4], ref[4], err_msg=name)
+    else:
+        assert got[1:4] == (0, 0, 0) and got[4] is None, name
+
+
+def _batch(ctx, files, max_w, max_h, pad=0, shift=0):
+    """The files in one batch; the first file starts `shift` bytes into the data, slots are
+    4 * max_w * max_h + pad bytes apart."""
+    import torch
+    dev = torch.device("cuda", 0)
+    n = len(files)
+    sizes = np.array([len(f) for f in files], np.int64)
+    offs = np.zeros(n, np.int64)
+    offs[1:] = np.cumsum(sizes)[:-1]
+    offs += shift
+    blob = b"\xEE" * shift + b"".join(files) or b"\0"
+    data = torch.from_numpy(np.frombuffer(blob, np.uint8).copy()).to(dev)
+    d_off = torch.from_numpy(offs).to(dev)
+    d_sz = torch.from_numpy(sizes).to(dev)
+    stride = 4 * max_w * max_h + pad
+    guard = 256
+    out = torch.full((guard + n * stride + guard,), 0xA5, dtype=torch.uint8, device=dev)
+    st = torch.full((n,), -9, dtype=torch.int32, device=dev)
+    dims = torch.full((n, 3), -9, dtype=torch.int32, device=dev)
+    b = icx.TiffBatch(ctx, n, max_w, max_h)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    torch.cuda.synchronize(dev)  # (the fills above are done before another stream writes)
+    b.decode_device(n, data.data_ptr(), d_off.data_ptr(), d_sz.data_ptr(), out.data_ptr() + guard, stride,
+                    st.data_ptr(), dims.data_ptr(), stream)
+    torch.cuda.synchronize(dev)
+    times = b.stage_times()
+    b.close()
+    out, st, dims = out.cpu().numpy(), st.cpu().numpy(), dims.cpu().numpy()
+    assert (out[:guard] == 0xA5).all() and (out[-guard:] == 0xA5).all()
+    res = []
+    for i in range(n):
+        w, h, d = (int(v) for v in dims[i])
+        slot = out[guard + i * stride: guard + (i + 1) * stride]
+        arr = None
+        if st[i] == icx.TIFF_OK:
+            arr = slot[:w * h * d].reshape(h, w, d)
+            assert (slot[w * h * d:] == 0xA5).all(), f"image {i} wrote past its pixels"
+        else:
+            assert (w, h, d) == (0, 0, 0)
+            assert (slot == 0xA5).all(), f"failed image {i} wrote pixels"
+        res.append((int(st[i]), w, h, d, arr))
+    return res, times
+
+
+def _check_batch(ctx, files, max_w, max_h, **kw):
+    res, times = _batch(ctx, [f for _, f in files], max_w, max_h, **kw)
+    assert set(times) == STAGES
+    for (name, f), got in zip(files, res):
+        _same(got, f, name, max_w=max_w, max_h=max_h)
+    return res
+
+
+def _pil_files():
+    Image = pytest.importorskip("PIL.Image")
+    rng = np.random.default_rng(11)
+    out = []
+    for comp in ("raw", "packbits", "tiff_lzw", "tiff_adobe_deflate"):
+        for pred in (1, 2):
+            for mode in ("L", "P", "RGB", "RGBA"):
+                for strips in (False, True):
+                    ch = {"L": 1, "P": 1, "RGB": 3, "RGBA": 4}[mode]
+                    a = (T.smooth(ch + pred, 33, 29, ch) + rng.integers(0, 3, (33, 29, ch)[:2 if ch == 1 else 3], dtype=np.uint8)).astype(np.uint8)
+                    im = Image.fromarray(a, mode)
+                    if mode == "P":
+                        im.putpalette(rng.integers(0, 256, 768, dtype=np.uint8).tobytes())
+                    info = {317: 2} if pred == 2 else {}
+                    if strips:
+                        info[278] = 4
+                    b = io.BytesIO()
+                    im.save(b, "TIFF", compression=comp, tiffinfo=info)
+                    out.append((f"pil_{comp}_p{pred}_{mode}_{'s4' if strips else 'one'}", b.getvalue()))
+    return out
+
+
+def test_tiff_fixture(ctx):
+    got = ctx.tiff_decode(FIXTURE)
+    assert got[:4] == (icx.TIFF_OK, 499, 289, 3)
+    _same(got, FIXTURE, "fixture")
+
+
+def test_tiff_pil_written_files(ctx):
+    Image = pytest.importorskip("PIL.Image")
+    files = _pil_files()
+    assert len(files) == 64
+    res = _check_batch(ctx, files, 29, 33)
+    for (name, data), got in zip(files, res):
+        assert got[0] == T.OK, name
+        im = Image.open(io.BytesIO(data))
+        ref = np.asarray(im.convert("RGB") if im.mode == "P" else im)
+        np.testing.assert_array_equal(got[4].reshape(ref.shape), ref, err_msg=name)
+
+
+def test_tiff_corpus_in_one_batch(ctx):
+    files = [("fixture", FIXTURE)] + T.corpus()
+    assert len(files) > 70
+    res = _check_batch(ctx, files, 499, 289)
+    assert all(r[0] == T.OK for r in res)
+
+
+def test_tiff_corpus_single(ctx):
+    """The host in / host out entry on one file of each group."""
+    names = dict(T.corpus())
+    for name in ("raw_p1_s3_strips3", "lzw_p2_s4_strips3", "deflate_p2_tiles", "zip32946_p1_s1_strips3", "packbits_p1_tiles",
+                 "lzw_mm_long_shuffled", "deflate_miniswhite", "packbits_palette", "lzw_palette_mm_tiles", "rps_above_height",
+                 "raw_pred2_ignored", "lzw_no_eoi", "lzw_clear_every_10", "lzw_kwkwk", "zlib_trailing_bytes", "raw_longer_chunk"):
+        _same(ctx.tiff_decode(names[name]), names[name], name)
+
+
+@pytest.mark.parametrize("comp", ALL_COMPS)
+def test_tiff_widths_and_strips(ctx, comp):
+    """Widths 1, 5, 21, 22, 64, 65, 257 in 1- and 3-row strips over 7 rows (RowsPerStrip 3 does not
+    divide 7), grey and RGB, with the predictor where it is honoured."""
+    files = []
+    for w in (1, 5, 21, 22, 64, 65, 257):
+        for rps in (1, 3):
+            for spp in (1, 3):
+                a = T.smooth(w + rps, 7, w, spp) if (w + spp) & 1 else T.noise(w + rps, 7, w, spp)
+                files.append((f"w{w}_rps{rps}_s{spp}", T.make_tiff(a, comp=comp, pred=2, rps=rps)))
+    _check_batch(ctx, files, 257, 7)
+
+
+@pytest.mark.parametrize("comp", ALL_COMPS)
+def test_tiff_chunk_offsets_at_every_residue(ctx, comp):
+    """The first chunk at all 16 residues mod 16 (the later ones follow without padding), the batch
+    data itself shifted, slots an odd number of bytes apart."""
+    files = [(f"at{r}", T.make_tiff(T.smooth(r, 6, 37, 3), comp=comp, pred=2, rps=2, data_at=8 + r)) for r in range(16)]
+    files += [(f"tile_at{r}", T.make_tiff(T.smooth(r, 20, 37, 4), comp=comp, pred=2, tile=(16, 16), data_at=8 + r)) for r in (1, 7, 14)]
+    _check_batch(ctx, files, 37, 20, pad=3, shift=5)
+
+
+def test_tiff_lzw_noise_crosses_every_width_and_the_clear(ctx):
+    """97 x 131 noise in one strip: 9 -> 10 -> 11 -> 12 bits and libtiff's Clear at entry 4094; the
+    chunk is many staged windows long. With and without predictor, and cut short."""
+    a = T.noise(30, 131, 97)
+    for pred in (1, 2):
+        data = T.make_tiff(a, comp=5, pred=pred)
+        code, H = T.parse(data)
+        assert H["counts"][0] > 7 * KTIFF_WIN
+        got = ctx.tiff_decode(data)
+        assert got[0] == T.OK
+        _same(got, data, f"pred{pred}")
+    Image = pytest.importorskip("PIL.Image")
+    b = io.BytesIO()
+    Image.fromarray(a, "L").save(b, "TIFF", compression="tiff_lzw", tiffinfo={317: 2})
+    _same(ctx.tiff_decode(b.getvalue()), b.getvalue(), "libtiff's own stream")
+    np.testing.assert_array_equal(ctx.tiff_decode(b.getvalue())[4][:, :, 0], a)
+
+
+def test_tiff_lzw_crafted_streams(ctx):
+    raw = T.noise(50, 131, 97)
+    n = raw.size
+    flat = np.full((40, 300), 9, np.uint8)
+    files = [
+        ("no_eoi", T.make_tiff(raw, comp=5, lzw={"eoi": False}), T.OK),
+        ("clear_every_300", T.make_tiff(raw, comp=5, lzw={"clear_every": 300}), T.OK),
+        ("clear_every_64", T.make_tiff(raw, comp=5, lzw={"clear_every": 64}), T.OK),
+        ("clear_every_65", T.make_tiff(raw, comp=5, lzw={"clear_every": 65}), T.OK),
+        ("clear_every_1", T.make_tiff(raw[:20], comp=5, lzw={"clear_every": 1}), T.OK),
+        ("kwkwk_long_strings", T.make_tiff(flat, comp=5), T.OK),
+        ("kwkwk_pred2_rgb", T.make_tiff(np.stack([flat, flat + 1, flat + 2], axis=2), comp=5, pred=2), T.OK),
+        ("double_clear", T.make_tiff(raw[:1, :3], comp=5, chunks={0: T.lzw_from_codes([256, 256, int(raw[0, 0]), 256, 256,
+                                                                                     int(raw[0, 1]), int(raw[0, 2]), 257])}), T.OK),
+        ("string_cut_at_want", T.make_tiff(flat[:1, :7], comp=5, chunks={0: T.lzw_encode(bytes([9]) * 40)}), T.OK),
+        ("no_leading_clear", T.make_tiff(raw, comp=5, lzw={"lead_clear": False}), T.BAD_DATA),
+        ("first_after_clear_not_literal", T.make_tiff(raw[:1, :8], comp=5, chunks={0: T.lzw_from_codes([256, 7, 8, 256, 258, 1, 2, 3, 4, 5, 6])}),
+         T.BAD_DATA),
+        ("code_above_next", T.make_tiff(raw[:1, :8], comp=5, chunks={0: T.lzw_from_codes([256, 1, 2, 3, 261, 4, 5, 6, 7])}), T.BAD_DATA),
+        ("never_clear", T.lzw_never_clear_file(), T.BAD_DATA),
+        ("eoi_early", T.make_tiff(raw[:1, :8], comp=5, chunks={0: T.lzw_from_codes([256, 1, 2, 3, 257, 4, 5, 6, 7, 8])}), T.BAD_DATA),
+        ("old_style", T.make_tiff(raw[:1, :8], comp=5, chunks={0: b"\x00\x01\x02\x03"}), T.UNSUPPORTED),
+    ]
+    for name, data, want in files:
+        assert T.decode(data)[0] == want, name
+    res = _check_batch(ctx, [(n_, f) for n_, f, _ in files], 300, 131)
+    assert [r[0] for r in res] == [w for _, _, w in files]
+
+
+def test_tiff_packbits_packets(ctx):
+    """Literal runs of 1 and 128, repeat runs of 2 and 128, a -128 no-op; a last packet cut at the
+    chunk's size."""
+    s, out = T.packbits_packets([("lit", b"a"), ("rep", 2, 7), ("nop",), ("lit", bytes(range(128))), ("rep", 128, 9), ("nop",),
+                                 ("lit", b"xyz"), ("rep", 3, 1)])
+    assert len(out) == 265
+    a = np.frombuffer(out, np.uint8).reshape(5, 53)
+    files = [("packets", T.make_tiff(a, comp=32773, chunks={0: s})),
+             ("cut_in_last_packet", T.make_tiff(a[:, :52], comp=32773, chunks={0: s})),
+             ("photo_rows", T.make_tiff(T.smooth(1, 9, 300, 3), comp=32773, rps=4))]
+    res = _check_batch(ctx, files, 300, 9)
+    assert all(r[0] == T.OK for r in res)
+
+
+def test_tiff_deflate_block_kinds(ctx):
+    """Stored, fixed and dynamic blocks (zlib levels 0, 1 on a tiny chunk, 9), a chunk of several
+    flushes of the inflate's ring, Adobe and old-style compression numbers."""
+    a = T.smooth(3, 40, 300, 3)
+    files = []
+    for level in (0, 1, 9):
+        for comp in (8, 32946):
+            files.append((f"level{level}_{comp}", T.make_tiff(a, comp=comp, pred=2, rps=16, zlevel=level)))
+    tiny = T.noise(1, 1, 5)
+    files.append(("fixed_block", T.make_tiff(tiny, comp=8, zlevel=1)))
+    assert zlib.compress(tiny.tobytes(), 1)[2] & 6 == 2  # BTYPE 01
+    res = _check_batch(ctx, files, 300, 40)
+    assert all(r[0] == T.OK for r in res)
+
+
+def test_tiff_predictor_across_tile_edges(ctx):
+    """Predictor 2 on RGBA restarts at every tile: 16 x 16 tiles on 37 x 20, and a tile wider than a
+    render segment with more than three segments in a row."""
+    files = []
+    for comp in (5, 8):
+        files.append((f"rgba_tiles_{comp}", T.make_tiff(T.noise(comp, 20, 37, 4), comp=comp, pred=2, tile=(16, 16))))
+        files.append((f"wide_{comp}", T.make_tiff(T.smooth(comp, 3, 3 * KTIFF_SEG + 77, 4), comp=comp, pred=2, rps=2)))
+        files.append((f"wide_tiles_{comp}", T.make_tiff(T.smooth(comp, 3, 3 * KTIFF_SEG + 77, 3), comp=comp, pred=2, tile=(KTIFF_SEG + 16, 16))))
+    res = _check_batch(ctx, files, 3 * KTIFF_SEG + 77, 20)
+    assert all(r[0] == T.OK for r in res)
+
+
+def test_tiff_one_bad_chunk_fails_its_image_alone(ctx):
+    a = T.smooth(5, 12, 40, 3)
+    files = []
+    for comp, bad in ((1, b"\0" * 10), (5, T.lzw_from_codes([256, 1, 2, 257])), (8, zlib.compress(b"short")), (32773, b"\x05ab")):
+        files.append((f"good_{comp}", T.make_tiff(a, comp=comp, rps=2)))
+        files.append((f"bad_middle_{comp}", T.make_tiff(a, comp=comp, rps=2, chunks={3: bad})))
+        files.append((f"good_tiles_{comp}", T.make_tiff(a, comp=comp, tile=(16, 16))))
+    res = _check_batch(ctx, files, 40, 12)
+    assert [r[0] for r in res] == [T.OK, T.BAD_DATA, T.OK] * 4
+
+
+def test_tiff_every_status(ctx):
+    cases = T.status_cases()
+    assert {c for _, _, c in cases} == set(range(8))
+    for name, data, want in cases:
+        assert T.decode(data)[0] == want, name
+        _same(ctx.tiff_decode(data), data, name)
+    res = _check_batch(ctx, [(n, f) for n, f, _ in cases], 16, 16)
+    assert [r[0] for r in res] == [c for _, _, c in cases]
+
+
+def test_tiff_mixed_batch_with_refused_files(ctx):
+    """Every compression next to refused files, the fixture too large for the workspace."""
+    names = dict(T.corpus())
+    files = [(n, names[n]) for n in ("raw_p1_s3_strips3", "lzw_p2_s3_strips3", "deflate_p2_s4_strips3", "zip32946_p1_tiles",
+                                     "packbits_p1_s1_strips3", "lzw_palette_mm_tiles", "deflate_miniswhite", "lzw_kwkwk")]
+    files += [(n, f) for n, f, _ in T.status_cases()] + [("fixture", FIXTURE)]
+    res = _check_batch(ctx, files, 200, 33, pad=1, shift=3)
+    assert res[-1][0] == T.TOO_LARGE
+    assert sum(r[0] != T.OK for r in res) > 40 and sum(r[0] == T.OK for r in res) >= 9
+
+
+def test_tiff_prefixes_and_mutants(ctx):
+    """Every prefix of one file and 200 seeded bit flips of it, each followed by another file or at
+    the very end of the data: defined statuses equal to the restatement's."""
+    base = T.base_file()
+    files = [(f"prefix{k}", base[:k]) for k in range(0, len(base) + 1, 3)] + T.mutants(base)
+    seen = {T.decode(f)[0] for _, f in files}
+    assert seen >= {T.OK, T.NOT_TIFF, T.BAD_HEADER, T.MALFORMED, T.UNSUPPORTED, T.TRUNCATED}
+    _check_batch(ctx, files, 16, 16)
+
+
+def test_tiff_too_large(ctx):
+    data = T.make_tiff(T.noise(1, 9, 33), comp=5, rps=2)
+    for mw, mh, want in ((33, 9, T.OK), (32, 9, T.TOO_LARGE), (33, 8, T.TOO_LARGE)):
+        res, _ = _batch(ctx, [data, data], mw, mh)
+        assert [r[0] for r in res] == [want, want]
+    # padded tiles past the slot: the one 64 x 64 x 3 tile of a 33 x 9 image needs 12288 bytes of scratch
+    tiled = T.make_tiff(T.noise(2, 9, 33, 3), comp=8, tile=(64, 64))
+    assert T.decode(tiled, max_w=33, max_h=9)[0] == T.TOO_LARGE and T.decode(tiled, max_w=64, max_h=64)[0] == T.OK
+    _check_batch(ctx, [("tiled", tiled)], 33, 9)
+    _check_batch(ctx, [("tiled", tiled)], 64, 64)
+    _same(ctx.tiff_decode(tiled), tiled, "padded tiles, single")
+
+
+def test_tiff_image_read(ctx, tmp_path):
+    p = tmp_path / "a.TIF"
+    p.write_bytes(FIXTURE)
+    img = icx.Image()
+    img.read(str(p))
+    assert (img.cols(), img.rows(), img.channels(), img.type()) == (499, 289, 3, icx.Image.UBYTE)
+    np.testing.assert_array_equal(img.data().reshape(289, 499, 3), T.decode(FIXTURE)[4])
+    bad = tmp_path / "bad.tiff"
+    bad.write_bytes(FIXTURE[:2000])
+    with pytest.raises(RuntimeError, match="Could not read image data"):
+        icx.Image().read(str(bad))
+    img.load(np.zeros((4, 4, 3), np.uint8), 4, 4, 3)
+    with pytest.raises(ValueError):
+        img.write(str(tmp_path / "out.tif"))
