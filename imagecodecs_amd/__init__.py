@@ -94,6 +94,7 @@ _SIGS = {
     "icx_batch_group": (_i32, [_vp]),
     "icx_batch_groups": (_i32, [_vp, _i32]),
     "icx_batch_path_stats": (_i32, [_vp, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32)]),
+    "icx_batch_dri_stats": (_i32, [_vp, C.POINTER(_i32), C.POINTER(_i32)]),
     "icx_tje_encode_with_func": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp]),
     "icx_tje_encode_to_file_at_quality": (_i32, [_vp, C.c_char_p, _i32, _i32, _i32, _i32, _vp]),
     "icx_tje_encode_to_file": (_i32, [_vp, C.c_char_p, _i32, _i32, _i32, _vp]),
@@ -823,6 +824,13 @@ class Batch:
         a, b, c = C.c_int(), C.c_int(), C.c_int()
         lib().icx_batch_path_stats(self._p, C.byref(a), C.byref(b), C.byref(c))
         return {"parallel": a.value, "fallback": b.value, "sequential": c.value}
+
+    def dri_stats(self) -> dict:
+        """Restart-interval images of the last call planned onto the guess-write lanes: decided by
+        them ("gw"), sent back to one lane per interval ("gw_fallback")."""
+        a, b = C.c_int(), C.c_int()
+        lib().icx_batch_dri_stats(self._p, C.byref(a), C.byref(b))
+        return {"gw": a.value, "gw_fallback": b.value}
 
     @property
     def group(self) -> int:

@@ -289,7 +289,7 @@ static bool ws_alloc(icx_ctx* ctx, GroupWs& ws, Blocks& mem, int group, int max_
     ICX_ALLOC(ctx, mem.alloc(ws.rst, sizeof(int64_t) * ws.rst_cap * group), false);
     ICX_ALLOC(ctx, mem.alloc(ws.tile_rbase, sizeof(int32_t) * ws.tiles_cap), false);
     ICX_ALLOC(ctx, mem.alloc(ws.ent, sizeof(LaneEntry) * ws.lanes_cap), false);
-    ICX_ALLOC(ctx, mem.alloc(ws.stats, sizeof(int32_t) * 4), false);
+    ICX_ALLOC(ctx, mem.alloc(ws.stats, sizeof(int32_t) * kPathStats), false);
     ICX_ALLOC(ctx, mem.alloc(ws.Y, sizeof(uint64_t) * ws.lanes_cap), false);
     ICX_ALLOC(ctx, mem.alloc(ws.rec, sizeof(RecState) * kRec * ws.lanes_cap), false);
     ICX_ALLOC(ctx, mem.alloc(ws.nrec, sizeof(int32_t) * ws.lanes_cap), false);
@@ -408,7 +408,7 @@ int icx_jpeg_batch_decode(icx_batch* b, int n, const uint8_t* d_data, const uint
     const RoctxRange range("icx_jpeg_batch_decode");
     b->hook->reset();
     for (int p = 0; p < b->pipes; ++p)
-        ICX_HIP(ctx, hipMemsetAsync(b->ws[p].stats, 0, sizeof(int32_t) * 4, st), ICX_INTERNAL_ERR);
+        ICX_HIP(ctx, hipMemsetAsync(b->ws[p].stats, 0, sizeof(int32_t) * kPathStats, st), ICX_INTERNAL_ERR);
     // equal-sized groups (512 images on 361 slots -> 256 + 256, not 361 + 151): every kernel's
     // grid is sized by the work of its group, so a small tail group leaves the GPU half idle
     int per = 0;
@@ -479,21 +479,39 @@ int icx_jpeg_batch_decode(icx_batch* b, int n, const uint8_t* d_data, const uint
     return ICX_OK;
 }
 
-int icx_batch_path_stats(const icx_batch* b, int32_t* parallel, int32_t* fallback, int32_t* sequential) {
-    if (!b) return ICX_INTERNAL_ERR;
-    int32_t h[4] = {0, 0, 0, 0};
+// The batch's path counters summed over its pipelines (GroupWs::stats), once the last call's work is done.
+static int batch_stats(const icx_batch* b, int32_t (&h)[kPathStats]) {
+    for (int k = 0; k < kPathStats; ++k) h[k] = 0;
     // The decode ran on non-blocking streams, which the null stream does not order against:
     // wait for the batch's own event recorded after every pipe joined.
     ICX_HIP(b->ctx, hipSetDevice(b->ctx->device), ICX_INTERNAL_ERR);
     if (b->decoded) ICX_HIP(b->ctx, hipEventSynchronize(b->done), ICX_INTERNAL_ERR);
     for (int p = 0; p < b->pipes; ++p) {
-        int32_t q[4];
+        int32_t q[kPathStats];
         ICX_HIP(b->ctx, hipMemcpy(q, b->ws[p].stats, sizeof q, hipMemcpyDeviceToHost), ICX_INTERNAL_ERR);
-        for (int k = 0; k < 4; ++k) h[k] += q[k];
+        for (int k = 0; k < kPathStats; ++k) h[k] += q[k];
     }
+    return ICX_OK;
+}
+
+int icx_batch_path_stats(const icx_batch* b, int32_t* parallel, int32_t* fallback, int32_t* sequential) {
+    if (!b) return ICX_INTERNAL_ERR;
+    int32_t h[kPathStats];
+    const int rc = batch_stats(b, h);
+    if (rc != ICX_OK) return rc;
     if (parallel) *parallel = h[0];
     if (fallback) *fallback = h[1];
     if (sequential) *sequential = h[2];
+    return ICX_OK;
+}
+
+int icx_batch_dri_stats(const icx_batch* b, int32_t* gw, int32_t* gw_fallback) {
+    if (!b) return ICX_INTERNAL_ERR;
+    int32_t h[kPathStats];
+    const int rc = batch_stats(b, h);
+    if (rc != ICX_OK) return rc;
+    if (gw) *gw = h[3];
+    if (gw_fallback) *gw_fallback = h[4];
     return ICX_OK;
 }
 

@@ -110,6 +110,8 @@ __host__ __device__ inline int16_t dc_cell(int32_t dc) {
     return (dc > -32768 && dc <= 32767) ? (int16_t)dc : kDcEscape;
 }
 
+constexpr int kPathStats = 5;  // GroupWs::stats: parallel, fallback, sequential, DRI guess-write, its fallback
+
 struct GroupWs {
     int slots = 0;
     int max_w = 0, max_h = 0;
@@ -148,7 +150,7 @@ struct GroupWs {
     int32_t* tile_rbase = nullptr;  // [tiles_cap] restart markers before the tile (per image)
     LaneEntry* ent = nullptr;   // [lanes_cap]
     struct StepSet* steps = nullptr;  // [slots] step tables (icx_step.h), built per group
-    int32_t* stats = nullptr;   // [4] path counters, accumulated over a batch call
+    int32_t* stats = nullptr;   // [kPathStats] path counters (k_spec_finish), accumulated over a batch call
     // coefficient pool (Desc::acbase / mapped) and the guess-write path's records
     int64_t pool_cap = 0;              // pool blocks (+ kGwChunk scratch blocks allocated past it)
     uint2* map = nullptr;              // [pool_cap] block n of a mapped image: {pool block, DC offset} at acbase + n

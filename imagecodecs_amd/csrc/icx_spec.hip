@@ -104,10 +104,12 @@ __global__ __launch_bounds__(1024) void k_spec_plan(int n, const uint8_t* __rest
             nsub = d.restart == 0 ? (scan_len + sb - 1) / sb : (nmcu + d.restart - 1) / d.restart;
             // restart intervals on the guess-write path: long intervals, every MCU >= 8 bits
             // (lane_span), cut into kint lanes of at most kSubBytes
-            if (d.restart != 0 && gw && dri_min > 0 && scan_len / nsub >= dri_min && min_mcu_bits(d) >= 8) {
-                const int64_t avg = scan_len / nsub;
-                kint = (int)min<int64_t>(64, max<int64_t>(2, (avg + kSubBytes - 1) / kSubBytes));
-                sb = (avg + kint - 1) / kint;
+            if (d.restart != 0 && gw) {
+                const DriGwPlan p = dri_gw_plan(d, scan_len, dri_min);
+                if (p.kint) {
+                    kint = p.kint;
+                    sb = p.sb;
+                }
             }
             nlanes = kint ? nsub * kint : nsub;
             nw = (int)min<int64_t>((nlanes + kLanes - 1) / kLanes, INT32_MAX / 4);
@@ -1660,7 +1662,11 @@ __global__ void k_spec_finish(int n, Desc* __restrict__ desc, SpecImg* __restric
     if (s.mode != 1) desc[i].mapped = 0;  // the sequential kernel writes in place
     if (s.mode == 1 || s.mode == 3) desc[i].status = (s.err & kSpecSyntax) ? kSyntaxError : kOk;
     // path statistics: [0] parallel path (incl. DRI intervals), [1] parallel -> sequential
-    // fallback, [2] sequential only
+    // fallback, [2] sequential only; of [0], restart-interval images planned onto the guess-write
+    // lanes (kint > 0): [3] decided by them, [4] sent back to the interval lanes (dri_gw_fallback
+    // leaves kint set)
+    if (s.mode == 1 && s.kint > 0) atomicAdd(&stats[3], 1);
+    if (s.mode == 3 && s.kint > 0) atomicAdd(&stats[4], 1);
     if (s.mode == 1 || s.mode == 3) atomicAdd(&stats[0], 1);
     else if (s.mode == 2) atomicAdd(&stats[1], 1);
     else if (desc[i].status == kPending) atomicAdd(&stats[2], 1);

@@ -718,9 +718,13 @@ struct ErrBounds {
     }
 };
 
-// The fewest bits any MCU of the frame can take on a valid stream: per block the shortest DC code
-// plus its magnitude bits, plus the AC table's EOB code (a block without EOB holds 63 AC symbols).
-// Restart intervals go to the guess-write path only when this is at least 8 (lane_span's exit rule).
+// About the fewest bits an MCU of the frame takes on a valid stream: per block the shortest DC code
+// plus its magnitude bits, plus the AC table's EOB code. Restart intervals go to the guess-write path
+// only when this is at least 8, so that an interval's end is the only MCU start in [8 em - 7, 8 em]
+// (lane_span's exit rule). It is no true lower bound: a block without EOB can fill its 63 positions
+// with three ZRLs and one run-14 symbol, which odd tables (a long EOB code, a short ZRL) code in
+// fewer bits. An interval's last lane may then exit one MCU early; what keeps the result exact is
+// k_gw_scan's count check (cnt == iblk), which sends such an image to the interval lanes.
 ICX_HD int huff_count(const Huff& t, int L) { return (int)((t.bound[L] - t.bound[L - 1]) >> (16 - L)); }
 ICX_HD int min_mcu_bits(const Desc& d) {
     // (per Huffman table once: the shortest DC code + its category's bits, the EOB code's length)
@@ -749,6 +753,26 @@ ICX_HD int min_mcu_bits(const Desc& d) {
     return bits;
 }
 
+// k_spec_plan's decision for a restart-interval image when the group runs the guess-write path:
+// intervals averaging at least dri_min bytes of scan data (0: never), every MCU >= 8 bits
+// (lane_span), are cut into kint lanes of sb <= kSubBytes bytes each. kint = 0: the image keeps one
+// lane per interval (mode 3).
+struct DriGwPlan {
+    int kint;
+    int64_t sb;
+};
+ICX_HD DriGwPlan dri_gw_plan(const Desc& d, int64_t scan_len, int dri_min) {
+    DriGwPlan p{0, 0};
+    if (d.restart == 0 || dri_min <= 0) return p;
+    const int64_t nint = ((int64_t)d.mbw * d.mbh + d.restart - 1) / d.restart;
+    if (nint <= 0 || scan_len / nint < dri_min || min_mcu_bits(d) < 8) return p;
+    const int64_t avg = scan_len / nint;
+    const int64_t k = (avg + kSubBytes - 1) / kSubBytes;
+    p.kint = (int)(k > 64 ? 64 : (k < 2 ? 2 : k));
+    p.sb = (avg + p.kint - 1) / p.kint;
+    return p;
+}
+
 // Lane j's range in U bits and how it ends.
 //  * kint == 0 (no restart markers): lanes of sub_bytes, the last to the end of the data; a lane
 //    exits at its first block start at or after `end`.
@@ -760,8 +784,10 @@ ICX_HD int min_mcu_bits(const Desc& d) {
 //    (jpeg_dec.h:707-715 byte-aligns there), and an MCU takes at least 8 bits (k_spec_plan only sends
 //    such images here), so the true path's first MCU start at or past bit 8 em - 7 is the
 //    interval's end: the interval's last lane exits at the first block start at or after `end`
-//    whose block-in-MCU is at most `bmax` (0: an MCU start). Missing markers give degenerate but
-//    bounded ranges; k_gw_scan then sends the image to the interval lanes (mode 3).
+//    whose block-in-MCU is at most `bmax` (0: an MCU start). So does any earlier lane whose range
+//    reaches the interval's end (a short interval among long ones); the lanes after it are empty.
+//    Missing markers give degenerate but bounded ranges; k_gw_scan then sends the image to the
+//    interval lanes (mode 3).
 struct LaneSpan {
     int64_t start, end;  // bits
     int64_t floor;       // a lead starts no earlier
@@ -785,14 +811,20 @@ ICX_HD LaneSpan lane_span(int64_t j, int64_t nsub, int64_t sub_bytes, int64_t ul
     const int64_t em = m + 1 < nint ? (at(m) > sm ? at(m) : sm) : ulen;
     const int64_t len = em - sm, sub = (len + kint - 1) / kint > 0 ? (len + kint - 1) / kint : 1;
     const int64_t st = sm + ii * sub < em ? sm + ii * sub : em;
+    const int64_t eb = ii == kint - 1 || sm + (ii + 1) * sub > em ? em : sm + (ii + 1) * sub;
     L.start = st * 8;
     L.floor = sm * 8;
     L.first = ii == 0;
-    if (ii == kint - 1 && m + 1 < nint) {
-        L.end = em * 8 - 7 > L.start ? em * 8 - 7 : L.start;
+    if (eb == em && m + 1 < nint) {
+        // the interval-final rule, for every lane that reaches the interval's end: in a short
+        // interval ((kint - 1) sub >= len) that is an earlier lane than the last, and the lanes after
+        // it are empty, at that end (bit 8 em - 7, or the interval's start if it has no byte at all)
+        const int64_t fe = em * 8 - 7 > L.floor ? em * 8 - 7 : L.floor;
+        L.start = L.start < fe ? L.start : fe;
+        L.end = fe;
         L.bmax = 0;
     } else {
-        L.end = (ii == kint - 1 ? em : (sm + (ii + 1) * sub < em ? sm + (ii + 1) * sub : em)) * 8;
+        L.end = eb * 8;
         L.bmax = 255;
     }
     return L;

@@ -121,6 +121,11 @@ int icx_batch_stage_times(const icx_batch* b, const char** names, float* ms, int
  * (unverified chain), or the sequential decoder only (restart intervals, exotic sampling).
  * Synchronizes with the device. */
 int icx_batch_path_stats(const icx_batch* b, int32_t* parallel, int32_t* fallback, int32_t* sequential);
+/* Of the `parallel` images of the most recent batch call, the restart-interval images planned onto
+ * the interval-aligned guess-write lanes: those the lanes decided (gw), and those sent back to one
+ * lane per interval because the lanes could not decide them exactly (gw_fallback).
+ * Synchronizes with the device. */
+int icx_batch_dri_stats(const icx_batch* b, int32_t* gw, int32_t* gw_fallback);
 
 /* ---- per-image result records and multi-GPU decode ------------- */
 /* The record each device computes for every image it decoded; ranks (or devices) exchange

@@ -66,3 +66,23 @@ def elsewhere_case(seed=8300, w=512, h=512):
         if q > 0:
             return data[:k] + data[q:], j
     raise AssertionError("no stuffed FF 00 Dn in the stream")
+
+
+# The guess-write DRI batches of tests/test_gpu_decode.py (ICX_GW=1, ICX_DRI_GW=1), shared with the
+# CPU test that counts what the planner selects of them (tests/test_dri_gw_emu.py).
+DRI_GW_SPECS = [(1024, 768, "420", 64), (1000, 1000, "420", 1000), (640, 487, "444", 64), (800, 600, "422", 50),
+                (777, 555, "gray", 97), (1024, 1024, "420", 7), (512, 512, "420", 1), (1023, 999, "444", 300)]
+DRI_GW_CORRUPT_SPECS = [(640, 480, "420", 40), (640, 480, "444", 80), (640, 480, "gray", 40), (512, 512, "422", 64)]
+
+
+def dri_gw_jpegs():
+    return [S.synth_jpeg(4400 + k, w, h, smp, 60 + 5 * k, r) for k, (w, h, smp, r) in enumerate(DRI_GW_SPECS)]
+
+
+def dri_gw_corrupt_cases():
+    import numpy as np
+    rng = np.random.default_rng(43)
+    cases = []
+    for seed, (w, h, smp, r) in enumerate(DRI_GW_CORRUPT_SPECS):
+        cases += dri_corruptions(S.synth_jpeg(4500 + seed, w, h, smp, 85, r), rng, 24)
+    return cases

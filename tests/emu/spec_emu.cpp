@@ -347,10 +347,13 @@ struct EmuSink {
 // One guess-write lane (k_gw_lane's per-lane logic, scalar): decode [start - lead, end) from a
 // guessed block start; from the first block start at or after `start` (g0) store every block
 // started before the first block start at or after `end` (the exit), recording MCU starts.
+// `floor`: the lead starts no earlier (lane_span: a restart interval's first bit); `bmax`: the exit's
+// block-in-MCU is at most this (0 for an interval's last lane). Failures are noted per stretch between
+// records as k_gw_lane does (gw_guess_err).
 static uint64_t emu_gw_lane(const uint8_t* U, int64_t ulen, const WriteTab& TW, const Huff* H, const Sel& S, int64_t start,
                             int64_t end, int64_t lead, int64_t errbits, int64_t sbase, int32_t Sst, EmuPool& P,
-                            RecState* rec, GwOut& out) {
-    const int64_t s0 = start - lead > 0 ? start - lead : 0;
+                            RecState* rec, GwOut& out, int64_t floor = 0, int bmax = 255) {
+    const int64_t s0 = start - lead > floor ? start - lead : floor;
     Reader r;
     r.init(U, ulen, s0);
     ErrBounds eb;
@@ -363,6 +366,7 @@ static uint64_t emu_gw_lane(const uint8_t* U, int64_t ulen, const WriteTab& TW, 
     out.chunk0 = -1;
     out.nrec = 0;
     out.over = 0;
+    out.rerr = 0;
     int32_t chunk = -1;  // current overflow chunk
     int64_t addr = 0;    // pool block of the block in progress
     for (;;) {
@@ -372,11 +376,13 @@ static uint64_t emu_gw_lane(const uint8_t* U, int64_t ulen, const WriteTab& TW, 
                 phase = 1;
                 out.g0 = pack_state(s0 + u, b, 0);
             }
-            if (phase == 1 && u >= span) return pack_state(s0 + u, b, 0);
+            if (phase == 1 && u >= span && b <= bmax) return pack_state(s0 + u, b, 0);
             if (phase == 1 && b == 0 && out.nrec < kRecGw) {
                 RecState& e = rec[out.nrec++];
                 e.rel = u - pre;
-                e.b = 0;
+                e.b = out.err == INT32_MAX ? 0 : out.err + 1;  // (the first failure since the record before)
+                if (out.err != INT32_MAX) out.rerr = 1;
+                out.err = INT32_MAX;
                 e.cnt = out.k;
                 e.ds[0] = out.ds[0]; e.ds[1] = out.ds[1]; e.ds[2] = out.ds[2];
             }
@@ -416,6 +422,28 @@ static uint64_t emu_gw_lane(const uint8_t* U, int64_t ulen, const WriteTab& TW, 
             }
             if (o.w2) blk[o.c2 & 63] = (int16_t)o.v2;
             if (z == 0) ++out.k;
+        }
+    }
+}
+
+// k_gw_map for one lane: its nb blocks from image block G on, each to its pool block and DC offset
+// (Pd: the lane's entry predictors): the count lane's chain first, then the guess lane's slots from
+// the splice record on.
+static void emu_gw_map_lane(const Desc& d, const Sel& SL, int64_t G, int64_t nb, const int32_t* Pd, const GwOut& g,
+                            const GcRec& c, const RecState* rec, int64_t sbase, int32_t Sst, const EmuPool& P,
+                            std::vector<int64_t>& maddr, std::vector<int32_t>& moff) {
+    GwSlots sl{sbase, Sst, -1, 0};
+    const int32_t m0 = c.m >= 0 ? rec[c.m].cnt : 0;
+    for (int64_t n = G; n < G + nb; ++n) {
+        const int32_t t = (int32_t)(n - G);
+        const int ci = SL.comp((int)(n % d.bpm));
+        if (t < c.c && c.m != -2) {
+            GwSlots cs{0, 0, -1, 0};
+            maddr[n] = cs.addr(t, c.chunk0, P.chunk_next.data());
+            moff[n] = Pd[ci];
+        } else {
+            maddr[n] = sl.addr(t - (c.m == -2 ? 0 : c.c) + m0, g.chunk0, P.chunk_next.data());
+            moff[n] = c.m >= 0 ? wadd(Pd[ci], wsub(c.cds[ci], rec[c.m].ds[ci])) : Pd[ci];
         }
     }
 }
@@ -550,23 +578,9 @@ int emu_gw_decode(const uint8_t* file, int64_t size, int sub_bytes, int64_t lead
         }
         stats[7] += 1;
     }
-    for (int64_t j = 0; j < nsub && !bad; ++j) {
-        GwSlots sl{j * Sst, Sst, -1, 0};
-        const int32_t m0 = c[j].m >= 0 ? rec[j * kRec + c[j].m].cnt : 0;
-        for (int64_t n = G[j]; n < G[j + 1] && n < total; ++n) {
-            const int32_t t = (int32_t)(n - G[j]);
-            const int ci = SL.comp((int)(n % d.bpm));
-            if (t < c[j].c && c[j].m != -2) {
-                GwSlots cs{0, 0, -1, 0};
-                maddr[n] = cs.addr(t, c[j].chunk0, P.chunk_next.data());
-                moff[n] = Pd[3 * j + ci];
-            } else {
-                maddr[n] = sl.addr(t - (c[j].m == -2 ? 0 : c[j].c) + m0, g[j].chunk0, P.chunk_next.data());
-                moff[n] = c[j].m >= 0 ? wadd(Pd[3 * j + ci], wsub(c[j].cds[ci], rec[j * kRec + c[j].m].ds[ci]))
-                                      : Pd[3 * j + ci];
-            }
-        }
-    }
+    for (int64_t j = 0; j < nsub && !bad; ++j)
+        emu_gw_map_lane(d, SL, G[j], std::min(G[j + 1], total) - std::min(G[j], total), &Pd[3 * j], g[j], c[j], &rec[j * kRec],
+                        j * Sst, Sst, P, maddr, moff);
     std::memset(coef, 0, sizeof(int16_t) * 64 * total);
     for (int64_t n = 0; n < total && !bad; ++n) {
         const int16_t* blk = &P.coef[(size_t)maddr[n] * 64];
@@ -580,6 +594,199 @@ int emu_gw_decode(const uint8_t* file, int64_t size, int sub_bytes, int64_t lead
     stats[0] += nsub; stats[1] += synced; stats[2] += counted; stats[3] += spliced; stats[4] += repaired;
     stats[5] += (P.next - (nsub * Sst + kGwChunk - 1) / kGwChunk * kGwChunk) / kGwChunk;
     stats[6] += P.next;
+    return 0;
+}
+}
+
+// ---- restart intervals on the guess-write lanes (k_spec_plan's kint > 0) ----
+extern "C" {
+
+// lane_span as the kernels call it: out = {start, end, floor, bmax, first}.
+void emu_lane_span(int64_t j, int64_t nsub, int64_t sub_bytes, int64_t ulen, int kint, int64_t nint, const int64_t* RS,
+                   int64_t nrst, int64_t* out /*[5]*/) {
+    const LaneSpan L = lane_span(j, nsub, sub_bytes, ulen, kint, nint, RS, nrst);
+    out[0] = L.start; out[1] = L.end; out[2] = L.floor; out[3] = L.bmax; out[4] = L.first;
+}
+
+// k_spec_plan's decision for `file` in a guess-write group (dri_gw_plan): out = {kint, lane bytes,
+// intervals, min_mcu_bits}; returns 0, or 2 for a file that is no candidate of the parallel decoder.
+int emu_dri_gw_plan(const uint8_t* file, int64_t size, int dri_min, int64_t* out /*[4]*/) {
+    auto dp = std::make_unique<Desc>();
+    Desc& d = *dp;
+    parse_headers(file, size, d);
+    out[0] = out[1] = out[2] = out[3] = 0;
+    const int64_t scan_len = d.size - d.scan_off;
+    if (!(d.status == kPending && d.nc >= 1 && d.bpm <= kSpecMaxBpm && scan_len > 0 && scan_len < ((int64_t)1 << 40))) return 2;
+    const DriGwPlan p = dri_gw_plan(d, scan_len, dri_min);
+    out[0] = p.kint;
+    out[1] = p.sb;
+    out[2] = d.restart ? ((int64_t)d.mbw * d.mbh + d.restart - 1) / d.restart : 0;
+    out[3] = min_mcu_bits(d);
+    return 0;
+}
+
+// A restart-interval image on the guess-write path end to end (k_gw_lane / k_gw_check / k_gw_count /
+// k_gw_repair / k_gw_scan's interval branch / k_gw_map, each lane cut by lane_span with the kint and
+// lane bytes of dri_gw_plan), and dri_gw_fallback: whatever the lanes cannot decide exactly is
+// emu_dri_decode's. Returns like emu_dri_decode (0 parallel result, 1 sequential kernel, 2 not
+// eligible). *outcome: 0 decided by the guess-write lanes, 3 fell back to the interval lanes, 2 not
+// planned with kint. stats (accumulated): [0] lanes, [1] synchronised at their start, [2] count
+// lanes, [3] spliced, [4] lanes re-derived by repair walks, [5] walks stopped at an interval's first
+// lane, [6] count lanes that never spliced (m == -1), [7] of those, interval-final ones (gc_walk's
+// bmax exit), [8] the largest kint, [9] intervals, [10] lanes queued for repair, [11] lanes with an
+// empty range, [12..19] interval-final exits by bit residue 8 em - p.
+int emu_gw_dri_decode(const uint8_t* file, int64_t size, int dri_min, int16_t* coef, int32_t* dcout, int64_t cap_blocks,
+                      int64_t* nblocks, int32_t* status, int32_t* outcome, int64_t* stats /*[20]*/) {
+    auto fallback = [&](int oc) {
+        int32_t first;
+        *outcome = oc;
+        return emu_dri_decode(file, size, coef, dcout, cap_blocks, nblocks, status, &first);
+    };
+    auto dp = std::make_unique<Desc>();
+    Desc& d = *dp;
+    *status = parse_headers(file, size, d);
+    *nblocks = 0;
+    *outcome = 2;
+    const int64_t scan_len = d.size - d.scan_off;
+    if (!(d.status == kPending && d.restart > 0 && d.nc >= 1 && d.bpm <= kSpecMaxBpm && scan_len > 0)) return 2;
+    const int64_t total = (int64_t)d.mbw * d.mbh * d.bpm;
+    *nblocks = total;
+    if (total > cap_blocks) return 2;
+    const DriGwPlan plan = dri_gw_plan(d, scan_len, dri_min);
+    if (plan.kint == 0) return fallback(2);
+    const uint8_t* R = file + d.scan_off;
+    std::vector<uint8_t> U;
+    std::vector<int64_t> rst;
+    int64_t errpos;
+    int32_t giveup = 0;
+    const int64_t ulen = emu_unstuff(R, scan_len, ustf_align(R), U, errpos, giveup, &rst);
+    if (giveup) return fallback(3);
+    const int64_t errbits = errpos == INT64_MAX ? INT64_MAX : errpos * 8;
+    auto SSp = std::make_unique<StepSet>();
+    StepSet& SS = *SSp;
+    for (int k = 0; k < WriteTab::entries(); ++k) SS.write.fill(d.huff, k);
+    const Sel SL = make_sel(d);
+    set_block_sel(SS.write, d.huff, SL);
+    const Huff* H = d.huff;
+    const int64_t K = plan.kint, nint = ((int64_t)d.mbw * d.mbh + d.restart - 1) / d.restart, nsub = nint * K;
+    const int64_t sub_bytes = plan.sb, nrst = (int64_t)rst.size();
+    const int64_t* RS = rst.data();
+    auto span = [&](int64_t j) { return lane_span(j, nsub, sub_bytes, ulen, (int)K, nint, RS, nrst); };
+    const int32_t Sst = (int32_t)((total * 11 / 10 + nsub - 1) / nsub + 1);  // k_spec_plan's gw_S
+    EmuPool P;
+    P.init(nsub * Sst + 8 * total + 64 * nsub + 1024, nsub * Sst);
+    stats[0] += nsub;
+    stats[8] = std::max<int64_t>(stats[8], K);
+    stats[9] += nint;
+    // ---- k_gw_lane
+    std::vector<uint64_t> X(nsub), Y(nsub, 0);
+    std::vector<GwOut> g(nsub);
+    std::vector<RecState> rec(nsub * kRec);
+    bool give_up = false;  // SpecImg::err & kSpecGiveUp
+    for (int64_t j = 0; j < nsub; ++j) {
+        const LaneSpan ls = span(j);
+        const int64_t lead = ls.first ? 0 : std::min<int64_t>(kGuessLead, sub_bytes * 2);
+        stats[11] += ls.start == ls.end;
+        X[j] = emu_gw_lane(U.data(), ulen, SS.write, H, SL, ls.start, ls.end, lead, errbits, j * Sst, Sst, P, &rec[j * kRec],
+                           g[j], ls.floor, ls.bmax);
+        give_up |= g[j].over != 0;
+    }
+    // ---- k_gw_check + k_gw_count
+    std::vector<GcRec> c(nsub);
+    const GcRec kSynced{-1, 0, 0, -2, {0, 0, 0}, INT32_MAX};
+    auto count_lane = [&](int64_t j, uint64_t entry) {  // false: the pool ran out
+        const LaneSpan ls = span(j);
+        GcRec& q = c[j];
+        uint64_t ex = 0;
+        EmuSink sk{&P};
+        q.pad_ = 0;
+        q.c = gc_walk(U.data(), ulen, SS.write, H, SL, entry, ls.start, ls.end, &rec[j * kRec], g[j].nrec, errbits, sk, q.cds,
+                      &q.m, &ex, &q.err, ls.bmax);
+        q.chunk0 = sk.chunk0;
+        Y[j] = ex;
+        stats[3] += q.m >= 0;
+        stats[6] += q.m == -1;
+        stats[7] += q.m == -1 && ls.bmax == 0;
+        return q.m != -3;
+    };
+    std::vector<int64_t> queue;
+    for (int64_t j = 0; j < nsub; ++j) c[j] = kSynced;
+    for (int64_t j = 0; j < nsub; ++j) {
+        const LaneSpan ls = span(j);
+        const uint64_t entry = ls.first ? pack_state(ls.start, 0, 0) : X[j - 1];
+        if (g[j].g0 == entry) continue;
+        if (ls.first) return -1;  // (k_gw_count reads X[f - 1]: an interval's first lane is never queued)
+        ++stats[2];
+        if (!count_lane(j, entry)) give_up = true;  // (k_gw_count goes on; k_gw_scan sends the image back)
+        if (c[j].m < 0 && j + 1 < nsub && Y[j] != X[j] && (j + 1) % K != 0) queue.push_back(j);
+    }
+    stats[10] += (int64_t)queue.size();
+    // ---- k_gw_repair
+    if ((int64_t)queue.size() > kMaxRepair) return fallback(3);
+    int64_t done = -1;
+    for (int64_t j : queue) {
+        if (j <= done) continue;
+        X[j] = Y[j];
+        int64_t k = j + 1;
+        for (int steps = 0; k < nsub; ++k, ++steps) {
+            if (k % K == 0) { ++stats[5]; break; }  // a restart interval's first lane: synchronised
+            if (steps >= kGwMaxWalk) return fallback(3);
+            if (g[k].g0 == X[k - 1]) { c[k] = kSynced; break; }
+            ++stats[4];
+            if (!count_lane(k, X[k - 1])) return fallback(3);
+            if (c[k].m >= 0 || k + 1 == nsub || Y[k] == X[k]) break;
+            X[k] = Y[k];
+        }
+        done = k;
+    }
+    for (int64_t j = 0; j < nsub; ++j) stats[1] += c[j].m == -2;
+    // ---- k_gw_scan, the interval branch
+    bool bad = give_up || nrst < nint - 1;
+    const int64_t iblk = (int64_t)d.restart * d.bpm;
+    std::vector<LaneEntry> ent(nsub);
+    int64_t res[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    for (int64_t m = 0; m < nint && !bad; ++m) {
+        const int64_t G0 = m * iblk;
+        int32_t cnt = 0, p[3] = {0, 0, 0};
+        for (int64_t ii = 0; ii < K; ++ii) {
+            const int64_t f = m * K + ii;
+            int32_t ds[3];
+            const int32_t nb = gw_lane_total(g[f], c[f], &rec[f * kRec], ds);
+            const int32_t e = gw_lane_err(g[f], c[f], &rec[f * kRec]);
+            ent[f] = LaneEntry{G0 + cnt, p[0], p[1], p[2], nb};
+            if (e != INT32_MAX && ent[f].G + e < total) bad = true;
+            cnt += nb;
+            for (int q = 0; q < 3; ++q) p[q] = wadd(p[q], ds[q]);
+            if (ii == K - 1 && m + 1 < nint) {  // the interval's end, where NanoJPEG reads marker m
+                const uint64_t ex = c[f].m == -1 ? Y[f] : X[f];
+                const int64_t em = RS[m] >> 3, pp = st_pos(ex);
+                if (st_b(ex) != 0 || pp < em * 8 - 7 || pp > em * 8) bad = true;
+                else ++res[em * 8 - pp];
+                if (dri_end_kind(U.data(), ulen, errpos, em, m, RS[m]) != kDriExact) bad = true;
+            }
+        }
+        if (m + 1 < nint ? cnt != iblk : cnt < total - G0) bad = true;
+    }
+    if (bad) return fallback(3);
+    for (int q = 0; q < 8; ++q) stats[12 + q] += res[q];
+    // ---- k_gw_map, then the blocks as the IDCT reads them
+    std::vector<int64_t> maddr(total, -1);
+    std::vector<int32_t> moff(total, 0);
+    for (int64_t j = 0; j < nsub; ++j) {
+        const int64_t nb = std::min<int64_t>(ent[j].pad, total - ent[j].G);
+        const int32_t Pd[3] = {ent[j].p0, ent[j].p1, ent[j].p2};
+        if (nb > 0) emu_gw_map_lane(d, SL, ent[j].G, nb, Pd, g[j], c[j], &rec[j * kRec], j * Sst, Sst, P, maddr, moff);
+    }
+    std::memset(coef, 0, sizeof(int16_t) * 64 * total);
+    for (int64_t n = 0; n < total; ++n) {
+        if (maddr[n] < 0) return -2;  // (a block no lane owns: the interval checks above rule it out)
+        const int16_t* blk = &P.coef[(size_t)maddr[n] * 64];
+        const int32_t dl = blk[0] == kDcEscape ? P.dc[(size_t)maddr[n]] : blk[0];
+        dcout[n] = wadd(dl, moff[n]);
+        for (int zz = 1; zz < 64; ++zz) coef[n * 64 + nat_of_zig(zz)] = blk[zz];
+    }
+    *status = kOk;
+    *outcome = 0;
     return 0;
 }
 }

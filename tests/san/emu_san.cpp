@@ -2,7 +2,9 @@
 // (imagecodecs_amd/csrc/icx_spec_core.h through tests/emu/spec_emu.cpp, host-only build) under
 // -fsanitize=address,undefined, run over every JPEG named on the command line with the sequential-
 // chain emulator (emu_spec_decode) and the guess-write emulator (emu_gw_decode) at several lane
-// sizes, leads and static-slot fractions. Exit status 0 = no sanitizer report.
+// sizes, leads and static-slot fractions, and the restart-interval guess-write emulator
+// (emu_gw_dri_decode) with intervals planned from 1 and from 512 bytes. Exit status 0 = no sanitizer
+// report.
 #include <cstdio>
 #include <cstdlib>
 #include <vector>
@@ -27,6 +29,11 @@ int main(int argc, char** argv) {
             emu_spec_decode(d.data(), (int64_t)d.size(), sub, coef.data(), dc.data(), cap, &nb, &status, st4);
             emu_gw_decode(d.data(), (int64_t)d.size(), sub, sub == 64 ? 0 : 4096, sub == 512 ? 0.05 : 1.1, coef.data(),
                           dc.data(), cap, &nb, &status, st8);
+        }
+        for (int dri_min : {1, 512}) {
+            int64_t st20[20] = {0};
+            int32_t outcome = 0;
+            emu_gw_dri_decode(d.data(), (int64_t)d.size(), dri_min, coef.data(), dc.data(), cap, &nb, &status, &outcome, st20);
         }
         ++files;
     }

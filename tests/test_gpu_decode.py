@@ -11,7 +11,8 @@ from conftest import GOLDEN
 import imagecodecs_amd as icx
 from oracle import pyoracle as O
 from tools import synthpy as S
-from driutil import dri_corruptions, elsewhere_case, rst_markers
+from driutil import dri_corruptions, dri_gw_corrupt_cases, dri_gw_jpegs, elsewhere_case, rst_markers
+from test_dri_gw_emu import plan as dri_gw_plan, run as dri_gw_emu
 
 pytestmark = pytest.mark.gpu
 
@@ -293,13 +294,15 @@ def test_dri_guess_write_lanes_bit_exact(ctx, monkeypatch, gw_env):
     ICX_DRI_GW=0 runs the same batch on the interval lanes alone."""
     monkeypatch.setenv("ICX_GW", "1")
     monkeypatch.setenv("ICX_DRI_GW", gw_env)
-    specs = [(1024, 768, "420", 64), (1000, 1000, "420", 1000), (640, 487, "444", 64), (800, 600, "422", 50),
-             (777, 555, "gray", 97), (1024, 1024, "420", 7), (512, 512, "420", 1), (1023, 999, "444", 300)]
-    jpegs = [S.synth_jpeg(4400 + k, w, h, smp, 60 + 5 * k, r) for k, (w, h, smp, r) in enumerate(specs)]
+    jpegs = dri_gw_jpegs()
     b = icx.Batch(ctx, len(jpegs), 1024, 1024)
     res = b.decode_host(jpegs)
     stats = b.path_stats()
     assert stats == {"parallel": len(jpegs), "fallback": 0, "sequential": 0}, stats
+    # and the images k_spec_plan cut into interval-aligned lanes (dri_gw_plan, run on the CPU: at
+    # least 5 of the 8, tests/test_dri_gw_emu.py) were decided by those lanes, none sent back
+    planned = sum(dri_gw_plan(j)["kint"] > 0 for j in jpegs)
+    assert b.dri_stats() == ({"gw": planned, "gw_fallback": 0} if gw_env == "1" else {"gw": 0, "gw_fallback": 0})
     for j, (code, w, h, n, pix) in zip(jpegs, res):
         ocode, ow, oh, on, opix = O.decode(j)
         assert code == ocode == 0 and (w, h, n) == (ow, oh, on)
@@ -314,15 +317,20 @@ def test_dri_guess_write_corrupt_markers(ctx, monkeypatch):
     sequential kernel."""
     monkeypatch.setenv("ICX_GW", "1")
     monkeypatch.setenv("ICX_DRI_GW", "1")
-    rng = np.random.default_rng(43)
-    cases = []
-    for seed, (w, h, smp, r) in enumerate([(640, 480, "420", 40), (640, 480, "444", 80), (640, 480, "gray", 40),
-                                           (512, 512, "422", 64)]):
-        cases += dri_corruptions(S.synth_jpeg(4500 + seed, w, h, smp, 85, r), rng, 24)
+    cases = dri_gw_corrupt_cases()
     b = icx.Batch(ctx, len(cases), 640, 512)
     res = b.decode_host(cases)
     stats = b.path_stats()
     assert stats["sequential"] == 0, stats
+    # every planned image is counted once, and the ones sent back are the ones the CPU emulator sends back
+    emu = [dri_gw_emu(j) for j in cases]
+    planned = sum(dri_gw_plan(j)["kint"] > 0 for j in cases)
+    # (three of the four base images qualify -- the gray one has 6-bit MCUs -- and of their 24 variants
+    # each only the 3 truncated ones can drop under 512 bytes an interval)
+    assert planned >= 63 and all(r.ret == 0 for r in emu)
+    dri = b.dri_stats()
+    assert dri["gw"] + dri["gw_fallback"] == planned, (dri, planned)
+    assert dri["gw_fallback"] == sum(r.outcome == 3 for r in emu), dri
     for j, (code, w, h, n, pix) in zip(cases, res):
         ocode, _, _, _, opix = O.decode(j)
         assert code == ocode
