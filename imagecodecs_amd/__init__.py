@@ -22,7 +22,10 @@ callers (tests, bench): it binds the C ABI with ctypes and offers
   * ``GifBatch``                  -- device-resident batched .gif decode
   * ``Context.tiff_decode``       -- Image::readTiff (codecs.cpp:1439-1484): strips / tiles, one wave per chunk
   * ``TiffBatch``                 -- device-resident batched .tif decode
+  * ``Context.pnm_decode`` / ``pnm_encode`` -- Image::readPbm / writePbm (codecs.cpp:1034-1167): P1-P6, Pf, PF
+  * ``PnmBatch``                  -- device-resident batched Netpbm decode
   * ``Image``                     -- ImageCodecs::Image (codecs.h:16-103) for .jpg/.jpeg/.png/.hdr/.exr/.tga/.gif/.tif
+                                     and .pbm/.pgm/.ppm/.pnm/.pfm
 
 There is deliberately no CPU fallback: if libicx.so is missing or no GPU is visible every
 entry point raises ``ICXError``.
@@ -46,7 +49,10 @@ __all__ = ["ICXError", "Context", "Batch", "HdrBatch", "Image", "lib", "build", 
            "TGA_INTERNAL_ERR", "GifBatch", "gif_probe", "GIF_OK", "GIF_NOT_GIF", "GIF_BAD_HEADER", "GIF_MALFORMED",
            "GIF_BAD_DATA", "GIF_TRUNCATED", "GIF_TOO_LARGE", "GIF_INTERNAL_ERR", "TiffBatch", "tiff_probe", "TIFF_OK",
            "TIFF_NOT_TIFF", "TIFF_BAD_HEADER", "TIFF_UNSUPPORTED", "TIFF_MALFORMED", "TIFF_BAD_DATA", "TIFF_TRUNCATED",
-           "TIFF_TOO_LARGE", "TIFF_INTERNAL_ERR"]
+           "TIFF_TOO_LARGE", "TIFF_INTERNAL_ERR", "PnmBatch", "pnm_probe", "pnm_encode_bound", "PNM_OK", "PNM_NOT_PNM",
+           "PNM_BAD_HEADER", "PNM_UNSUPPORTED", "PNM_BAD_DATA", "PNM_TRUNCATED", "PNM_TOO_LARGE", "PNM_INVALID_ARGUMENT",
+           "PNM_INTERNAL_ERR", "PNM_UBYTE", "PNM_USHORT", "PNM_FLOAT", "PNM_P4", "PNM_P5", "PNM_P6", "PNM_PF",
+           "PNM_ASCII_TILE"]
 
 OK, NO_JPEG, UNSUPPORTED, OUT_OF_MEM, INTERNAL_ERR, SYNTAX_ERROR = range(6)  # nj_result_t
 RESULT_NAMES = ["NJ_OK", "NJ_NO_JPEG", "NJ_UNSUPPORTED", "NJ_OUT_OF_MEM", "NJ_INTERNAL_ERR", "NJ_SYNTAX_ERROR"]
@@ -168,6 +174,16 @@ _SIGS = {
     "icx_tga_save_to_memory": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, C.POINTER(_vp), C.POINTER(_sz)]),
     "icx_tga_save_to_file": (_i32, [_vp, C.c_char_p, _vp, _i32, _i32, _i32, _i32]),
     "icx_tga_encode_device_batch": (_i32, [_vp, _i32, _vp, _vp, _vp, _i32, _i32, _vp, _u64, _vp, _vp, _vp]),
+    "icx_pnm_probe": (_i32, [_vp, _sz] + [C.POINTER(_i32)] * 5),
+    "icx_pnm_decode": (_i32, [_vp, _vp, _sz, C.POINTER(_vp)] + [C.POINTER(_i32)] * 5),
+    "icx_pnm_batch_create": (_vp, [_vp, _i32, _i32, _i32]),
+    "icx_pnm_batch_destroy": (None, [_vp]),
+    "icx_pnm_batch_decode": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _vp]),
+    "icx_pnm_batch_stage_times": (_i32, [_vp, _vp, _vp, _i32]),
+    "icx_pnm_encode_bound": (_sz, [_i32, _i32, _i32, _i32, _i32]),
+    "icx_pnm_save_to_memory": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, C.POINTER(_vp), C.POINTER(_sz)]),
+    "icx_pnm_save_to_file": (_i32, [_vp, C.c_char_p, _vp, _i32, _i32, _i32, _i32, _i32]),
+    "icx_pnm_encode_device_batch": (_i32, [_vp, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _u64, _vp, _vp, _vp]),
 }
 
 # icx_record (include/icx.h): per-image result record gathered across devices / ranks
@@ -198,6 +214,14 @@ GIF_INTERNAL_ERR = -1
 (TIFF_OK, TIFF_NOT_TIFF, TIFF_BAD_HEADER, TIFF_UNSUPPORTED, TIFF_MALFORMED, TIFF_BAD_DATA, TIFF_TRUNCATED,
  TIFF_TOO_LARGE) = range(8)
 TIFF_INTERNAL_ERR = -1
+# icx_pnm_result (include/icx.h): Image::readPbm / writePbm outcomes
+(PNM_OK, PNM_NOT_PNM, PNM_BAD_HEADER, PNM_UNSUPPORTED, PNM_BAD_DATA, PNM_TRUNCATED, PNM_TOO_LARGE,
+ PNM_INVALID_ARGUMENT) = range(8)
+PNM_INTERNAL_ERR = -1
+PNM_UBYTE, PNM_USHORT, PNM_FLOAT = range(3)  # icx_pnm_type = ImageCodecs::Type
+PNM_P4, PNM_P5, PNM_P6, PNM_PF = 4, 5, 6, 8  # icx_pnm_format
+PNM_ASCII_TILE = 4096  # icx_pnm_core.h kPnmTile: bytes of raster text per tile of the P1 / P2 / P3 read
+_PNM_DTYPES = (np.uint8, np.uint16, np.float32)
 
 WRITE_FUNC = C.CFUNCTYPE(None, C.c_void_p, C.c_void_p, C.c_int)
 
@@ -570,6 +594,61 @@ class Context:
             raise ICXError("icx_tga_encode_device_batch: " + _err(self._p))
         return rc
 
+    def pnm_decode(self, data: bytes):
+        """Image::readPbm (codecs.cpp:1034-1100; contract in include/icx.h) on the GPU -> (code, w, h,
+        channels, type, maxval, array (h, w, channels) of uint8 / uint16 / float32 or None); code is an
+        icx_pnm_result."""
+        buf = C.create_string_buffer(bytes(data), max(1, len(data)))
+        out = C.c_void_p()
+        v = [C.c_int() for _ in range(5)]
+        code = lib().icx_pnm_decode(self._p, buf, len(data), C.byref(out), *[C.byref(x) for x in v])
+        if code == PNM_INTERNAL_ERR:
+            raise ICXError("icx_pnm_decode: " + _err(self._p))
+        w, h, d, t, mv = (x.value for x in v)
+        arr = None
+        if out.value:
+            dt = np.dtype(_PNM_DTYPES[t])
+            arr = np.frombuffer(C.string_at(out.value, w * h * d * dt.itemsize), dt).reshape(h, w, d).copy()
+            lib().icx_free(out)
+        return code, w, h, d, t, mv, arr
+
+    def pnm_encode(self, px, fmt: int):
+        """Image::writePbm (codecs.cpp:1102-1167) on the GPU: (h, w) or (h, w, d) of uint8, uint16 or
+        float32, rows top-down; fmt is PNM_P4 / P5 / P6 / PF -> (code, the file's bytes or None)."""
+        a = np.ascontiguousarray(px)
+        if a.dtype not in (np.uint8, np.uint16, np.float32):
+            return PNM_INVALID_ARGUMENT, None
+        if a.ndim == 2:
+            a = a[:, :, None]
+        if a.ndim != 3:
+            return PNM_INVALID_ARGUMENT, None
+        h, w, d = a.shape
+        t = (np.dtype(np.uint8), np.dtype(np.uint16), np.dtype(np.float32)).index(a.dtype)
+        out, size = C.c_void_p(), C.c_size_t()
+        code = lib().icx_pnm_save_to_memory(self._p, a.ctypes.data if a.size else None, w, h, d, t, fmt,
+                                            C.byref(out), C.byref(size))
+        if code == PNM_INTERNAL_ERR:
+            raise ICXError("icx_pnm_save_to_memory: " + _err(self._p))
+        if code != PNM_OK:
+            return code, None
+        data = C.string_at(out.value, size.value)
+        lib().icx_free(out)
+        return code, data
+
+    def pnm_encode_device_batch(self, d_srcs, widths, heights, d: int, type_: int, fmt: int, d_out: int, out_stride: int,
+                                d_sizes: int, d_status: int, stream=0) -> int:
+        """icx_pnm_encode_device_batch: image i's pixels at device address d_srcs[i], its file to
+        d_out + i*out_stride, size (uint64) and status (int32) to the device arrays -> the call's code."""
+        n = len(d_srcs)
+        sp = (C.c_void_p * max(1, n))(*d_srcs)
+        ws = np.ascontiguousarray(widths, np.int32)
+        hs = np.ascontiguousarray(heights, np.int32)
+        rc = lib().icx_pnm_encode_device_batch(self._p, n, sp, ws.ctypes.data, hs.ctypes.data, d, type_, fmt, d_out,
+                                               out_stride, d_sizes, d_status, stream or None)
+        if rc == PNM_INTERNAL_ERR:
+            raise ICXError("icx_pnm_encode_device_batch: " + _err(self._p))
+        return rc
+
     def png_encode(self, width: int, height: int, d: int, src: bytes):
         """PNG bytes of an RGB8 (d=3) / RGBA8 (d=4) image (png_encoder::saveToFile), or None."""
         chunks = []
@@ -898,6 +977,55 @@ def tga_encode_bound(width: int, height: int, d: int) -> int:
     return int(lib().icx_tga_encode_bound(width, height, d))
 
 
+def pnm_probe(data: bytes):
+    """Host header walk of the Netpbm read -> (code, width, height, channels, type, maxval)."""
+    v = [C.c_int() for _ in range(5)]
+    buf = C.create_string_buffer(bytes(data), max(1, len(data)))
+    code = lib().icx_pnm_probe(buf, len(data), *[C.byref(x) for x in v])
+    return (code, *(x.value for x in v))
+
+
+def pnm_encode_bound(width: int, height: int, d: int, type_: int, fmt: int) -> int:
+    """icx_pnm_encode_bound: the file's length, or 0 for arguments the write refuses."""
+    return int(lib().icx_pnm_encode_bound(width, height, d, type_, fmt))
+
+
+class PnmBatch:
+    """Device-resident batched Netpbm decode (icx_pnm_batch_*): image i is
+    d_data[d_offsets[i] .. + d_sizes[i]); its elements at d_out + i*out_stride (d_out 16-byte aligned,
+    out_stride a multiple of 16), status in d_status[i], {width, height, channels, type, maxval} in
+    d_dims[5i..]."""
+
+    def __init__(self, ctx: Context, max_images: int, max_width: int, max_height: int):
+        self.ctx = ctx
+        self._p = lib().icx_pnm_batch_create(ctx.ptr, max_images, max_width, max_height)
+        if not self._p:
+            raise ICXError("icx_pnm_batch_create failed: " + _err(ctx.ptr))
+        self.max_images, self.max_width, self.max_height = max_images, max_width, max_height
+
+    def close(self):
+        if getattr(self, "_p", None):
+            lib().icx_pnm_batch_destroy(self._p)
+            self._p = None
+
+    def __del__(self):
+        self.close()
+
+    def decode_device(self, n, d_data, d_offsets, d_sizes, d_out, out_stride, d_status, d_dims, stream=0) -> int:
+        """-> PNM_OK, or PNM_INVALID_ARGUMENT for a d_out or out_stride that is not 16-byte aligned."""
+        rc = lib().icx_pnm_batch_decode(self._p, n, d_data, d_offsets, d_sizes, d_out, out_stride,
+                                        d_status, d_dims, stream or None)
+        if rc not in (PNM_OK, PNM_INVALID_ARGUMENT):
+            raise ICXError(f"icx_pnm_batch_decode -> {rc}: {_err(self.ctx.ptr)}")
+        return rc
+
+    def stage_times(self) -> dict:
+        names = (C.c_char_p * 8)()
+        ms = (C.c_float * 8)()
+        k = lib().icx_pnm_batch_stage_times(self._p, names, ms, 8)
+        return {names[i].decode(): float(ms[i]) for i in range(k)}
+
+
 def png_probe(data: bytes):
     """Host chunk walk of the PNG read (signature, IHDR, PLTE / tRNS, IDAT present) -> (code, width, height)."""
     w, h = C.c_int(), C.c_int()
@@ -1079,8 +1207,12 @@ class Image:
     (readHdr: d = 4, type FLOAT, the floats' bytes in pixels_), .exr, .tga (readTga: d = 1, 3 or
     4, type UBYTE), .gif (readGif: the first frame, d = 3, type UBYTE) and .tif/.tiff (readTiff: d = 1,
     3 or 4, type UBYTE), write .jpg/.jpeg, .png, .exr,
-    .tga (uncompressed) and .hdr (flat RGBE; d = 4 only). Other extensions raise ValueError (the
-    reference's std::invalid_argument for unknown types)."""
+    .tga (uncompressed) and .hdr (flat RGBE; d = 4 only). .pbm/.pgm/.ppm/.pnm/.pfm are read by
+    their magic (readPbm: d = 1 or 3; UBYTE, USHORT or FLOAT) and written as P4 / P5 / P6 / P5 or P6
+    by d / PF or Pf (writePbm). Other extensions raise ValueError (the reference's
+    std::invalid_argument for unknown types)."""
+
+    _PNM_EXT = (".pbm", ".pgm", ".ppm", ".pnm", ".pfm")
 
     UBYTE, USHORT, FLOAT = range(3)  # ImageCodecs::Type (codecs.h:14)
     _ctx = None
@@ -1115,6 +1247,9 @@ class Image:
             return
         if ext in (".tif", ".tiff"):
             self._read_tiff(filepath)
+            return
+        if ext in Image._PNM_EXT:
+            self._read_pnm(filepath)
             return
         if ext not in (".jpg", ".jpeg"):
             raise ValueError("Cannot parse filetype")
@@ -1183,6 +1318,18 @@ class Image:
         self.pixels_ = px.reshape(-1).copy()
         self.type_ = Image.UBYTE
 
+    def _read_pnm(self, filepath: str):
+        """readPbm (codecs.cpp:1034-1100): the type is the magic's, whatever the name; d = 1 or 3, type
+        UBYTE, USHORT or FLOAT, rows top-down. Every failure is Image::read's RuntimeError("Could not
+        read image data")."""
+        data = open(filepath, "rb").read()
+        code, w, h, d, t, _, px = self.context().pnm_decode(data)
+        if code != PNM_OK:
+            raise RuntimeError("Could not read image data")
+        self.w_, self.h_, self.d_ = w, h, d
+        self.pixels_ = px.reshape(-1).view(np.uint8).copy()
+        self.type_ = t
+
     def _read_exr(self, filepath: str):
         """readExr (codecs.cpp:464-493): LoadEXRFromMemory -> d = 4, type FLOAT, the floats' bytes in
         pixels_; a failure raises RuntimeError("Could not load .exr") (:489). (The reference reads
@@ -1226,16 +1373,33 @@ class Image:
                 return
             if code != HDR_OK:
                 return
+        elif ext in Image._PNM_EXT:  # writePbm (codecs.cpp:1102-1167)
+            if ext == ".pfm" and self.type_ != Image.FLOAT:
+                raise RuntimeError("Cannot write non-float data to .pfm")  # :1149-1152
+            fmt = {".pbm": PNM_P4, ".pgm": PNM_P5, ".ppm": PNM_P6, ".pfm": PNM_PF}.get(ext, PNM_P5 if self.d_ == 1 else PNM_P6)
+            try:  # (every other failure: nothing is thrown, no file appears)
+                px = np.frombuffer(self.pixels_.tobytes(), _PNM_DTYPES[self.type_], self.w_ * self.h_ * self.d_)
+                code, out = self.context().pnm_encode(px.reshape(self.h_, self.w_, self.d_), fmt)
+            except (ICXError, ValueError, AttributeError):
+                return
+            if code != PNM_OK:
+                return
         else:
             raise ValueError("Cannot parse filetype")
         with open(filepath, "wb") as f:
             if out is not None:
                 f.write(out)
 
-    def load(self, pixels, w: int, h: int, channels: int):
-        self.pixels_ = np.ascontiguousarray(pixels, np.uint8).reshape(-1)
+    def load(self, pixels, w: int, h: int, channels: int, type_: int = None):
+        """load(pixels, w, h, channels): UBYTE, as the reference's. With a fifth argument the pixels
+        are w*h*channels elements of that type (uint8, uint16 or float32), kept as their bytes."""
+        if type_ is None:
+            self.pixels_ = np.ascontiguousarray(pixels, np.uint8).reshape(-1)
+            type_ = Image.UBYTE
+        else:
+            self.pixels_ = np.ascontiguousarray(pixels, _PNM_DTYPES[type_]).reshape(-1).view(np.uint8)
         self.w_, self.h_, self.d_ = w, h, channels
-        self.type_ = Image.UBYTE
+        self.type_ = type_
 
     def rows(self):
         return self.h_

@@ -20,6 +20,7 @@
 #include "icx_mem.h"
 #include "icx_step.h"
 #include "icx_tga_core.h"
+#include "icx_pnm_core.h"
 #include "icx_hdrw_core.h"
 #include "icx_gif_core.h"
 
@@ -37,6 +38,7 @@ struct icx_ctx {
     ExrwWs* exrw = nullptr;  // grow-only EXR write buffers (icx_exrw.hip)
     TgawWs* tgaw = nullptr;  // grow-only Targa write buffers (icx_tga.hip)
     HdrwWs* hdrw = nullptr;  // grow-only Radiance write buffers (icx_hdrw.hip)
+    PnmwWs* pnmw = nullptr;  // grow-only Netpbm write buffers (icx_pnm.hip)
 };
 
 struct EventHook;
@@ -179,6 +181,7 @@ void icx_destroy(icx_ctx* c) {
     if (c->exrw) exrw_ws_destroy(c->exrw);
     if (c->tgaw) tgaw_ws_destroy(c->tgaw);
     if (c->hdrw) hdrw_ws_destroy(c->hdrw);
+    if (c->pnmw) pnmw_ws_destroy(c->pnmw);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
 }
@@ -1536,6 +1539,234 @@ int icx_tga_save_to_file(icx_ctx* ctx, const char* path, const uint8_t* pixels, 
         return ICX_TGA_INTERNAL_ERR;
     }
     return ICX_TGA_OK;
+}
+
+// --------------------------------------------------------- Netpbm (Image::readPbm / writePbm)
+struct icx_pnm_batch {
+    icx_ctx* ctx = nullptr;
+    PnmWs ws;
+    Blocks mem;  // the device memory ws points into
+    std::unique_ptr<EventHook> hook;
+};
+
+static int pnm_probe_at(const uint8_t* data, size_t size, int* w, int* h, int* d, int* type, int* maxval, int64_t* raster_at) {
+    int v[5] = {0, 0, 0, 0, 0};
+    int64_t at = -1;
+    const int rc = data ? pnm_probe(data, (int64_t)size, &v[0], &v[1], &v[2], &v[3], &v[4], &at) : ICX_PNM_NOT_PNM;
+    int* const dst[5] = {w, h, d, type, maxval};
+    for (int k = 0; k < 5; ++k)
+        if (dst[k]) *dst[k] = rc == ICX_PNM_OK ? v[k] : 0;
+    if (raster_at) *raster_at = at;
+    return rc;
+}
+
+int icx_pnm_probe(const uint8_t* data, size_t size, int* w, int* h, int* channels, int* type, int* maxval) {
+    return pnm_probe_at(data, size, w, h, channels, type, maxval, nullptr);
+}
+
+// tiles_cap: tiles of raster text per image (0: a workspace for binary files only).
+static icx_pnm_batch* pnm_batch_new(icx_ctx* ctx, int max_images, int max_w, int max_h, int64_t tiles_cap) {
+    // (images are one grid dimension)
+    if (!ctx || max_images <= 0 || max_images > 65535 || max_w <= 0 || max_h <= 0 ||
+        (int64_t)max_w * max_h > ((int64_t)1 << 30)) {
+        if (ctx) ctx->err = "icx_pnm_batch_create: bad arguments";
+        return nullptr;
+    }
+    ICX_HIP(ctx, hipSetDevice(ctx->device), nullptr);
+    auto* b = new icx_pnm_batch();
+    b->ctx = ctx;
+    b->hook = std::make_unique<EventHook>();
+    if (!pnm_ws_alloc(b->ws, b->mem, max_images, max_w, max_h, tiles_cap)) {
+        ctx->err = std::string("icx_pnm_batch_create: out of device memory: ") + hipGetErrorString(hipGetLastError());
+        delete b;
+        return nullptr;
+    }
+    return b;
+}
+
+icx_pnm_batch* icx_pnm_batch_create(icx_ctx* ctx, int max_images, int max_w, int max_h) {
+    if (max_w <= 0 || max_h <= 0) return pnm_batch_new(ctx, max_images, max_w, max_h, 0);  // (refused there)
+    return pnm_batch_new(ctx, max_images, max_w, max_h, pnm_default_tiles(max_w, max_h));
+}
+
+void icx_pnm_batch_destroy(icx_pnm_batch* b) {
+    if (!b) return;
+    (void)hipSetDevice(b->ctx->device);
+    delete b;
+}
+
+int icx_pnm_batch_decode(icx_pnm_batch* b, int n, const uint8_t* d_data, const uint64_t* d_off, const uint64_t* d_size,
+                         void* d_out, uint64_t out_stride, int32_t* d_status, int32_t* d_dims, void* stream) {
+    if (!b) return ICX_PNM_INTERNAL_ERR;
+    icx_ctx* ctx = b->ctx;
+    if (n < 0 || n > b->ws.max_images) { ctx->err = "icx_pnm_batch_decode: n exceeds batch capacity"; return ICX_PNM_INTERNAL_ERR; }
+    if (n == 0) return ICX_PNM_OK;
+    if (!d_data || !d_off || !d_size || !d_out || !d_status || !d_dims) { ctx->err = "null pointer"; return ICX_PNM_INTERNAL_ERR; }
+    if ((reinterpret_cast<uintptr_t>(d_out) & 15) || (out_stride & 15)) return ICX_PNM_INVALID_ARGUMENT;
+    ICX_HIP(ctx, hipSetDevice(ctx->device), ICX_PNM_INTERNAL_ERR);
+    hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
+    const RoctxRange range("icx_pnm_batch_decode");
+    b->hook->reset();
+    launch_pnm_decode(b->ws, n, d_data, d_off, d_size, static_cast<uint8_t*>(d_out), out_stride, d_status, d_dims, st,
+                      b->hook.get());
+    ICX_HIP(ctx, hipGetLastError(), ICX_PNM_INTERNAL_ERR);
+    return ICX_PNM_OK;
+}
+
+int icx_pnm_batch_stage_times(const icx_pnm_batch* b, const char** names, float* ms, int cap) {
+    if (!b) return 0;
+    static const Stage order[4] = {kStParse, kStUnstuff, kStEntropy, kStConvert};
+    static const char* const label[4] = {"parse", "locate", "text", "stream"};
+    float acc[kStCount];
+    b->hook->sum(acc);
+    for (int k = 0; k < 4 && k < cap; ++k) {
+        if (names) names[k] = label[k];
+        if (ms) ms[k] = acc[order[k]];
+    }
+    return 4;
+}
+
+int icx_pnm_decode(icx_ctx* ctx, const uint8_t* data, size_t size, void** out, int* w, int* h, int* channels, int* type,
+                   int* maxval) {
+    if (out) *out = nullptr;
+    int* const res_out[5] = {w, h, channels, type, maxval};
+    for (int* p : res_out)
+        if (p) *p = 0;
+    if (!ctx || !out) return ICX_PNM_INTERNAL_ERR;
+    int ww = 0, hh = 0, dd = 0, tt = 0, mv = 0;
+    int64_t raster_at = -1;
+    const int prc = pnm_probe_at(data, size, &ww, &hh, &dd, &tt, &mv, &raster_at);
+    if (prc != ICX_PNM_OK) return prc;  // header errors and a short binary raster need no device work
+    ICX_HIP(ctx, hipSetDevice(ctx->device), ICX_PNM_INTERNAL_ERR);
+    // (declared before the buffers: they are freed first, then the batch)
+    // (a text file gets a tile for every kPnmTile bytes of its text: nothing is TOO_LARGE here)
+    const int64_t tiles = raster_at >= 0 ? ((int64_t)size - raster_at + kPnmTile - 1) / kPnmTile + 1 : 0;
+    std::unique_ptr<icx_pnm_batch, void (*)(icx_pnm_batch*)> b(pnm_batch_new(ctx, 1, ww, hh, tiles), icx_pnm_batch_destroy);
+    if (!b) return ICX_PNM_INTERNAL_ERR;
+    const uint64_t nout = (uint64_t)ww * hh * dd * pnm_elem_bytes(tt), stride = (nout + 15) & ~(uint64_t)15;
+    Buf<uint8_t> d_in, d_out;
+    Buf<uint64_t> d_meta;
+    Buf<int32_t> d_res;
+    int rc = ICX_PNM_INTERNAL_ERR;
+    const uint64_t meta[2] = {0, (uint64_t)size};
+    int32_t res[6] = {0, 0, 0, 0, 0, 0};
+    hipStream_t st = ctx->stream;
+    if (d_in.reserve(size) && d_out.reserve(stride) && d_meta.reserve(16) && d_res.reserve(sizeof res) &&
+        hipMemcpyAsync(d_in.p, data, size, hipMemcpyHostToDevice, st) == hipSuccess &&
+        hipMemcpyAsync(d_meta.p, meta, 16, hipMemcpyHostToDevice, st) == hipSuccess &&
+        (launch_pnm_decode(b->ws, 1, d_in.p, d_meta.p, d_meta.p + 1, d_out.p, stride, d_res.p, d_res.p + 1, st, nullptr),
+         hipGetLastError() == hipSuccess) &&
+        hipMemcpyAsync(res, d_res.p, sizeof res, hipMemcpyDeviceToHost, st) == hipSuccess && hipStreamSynchronize(st) == hipSuccess) {
+        rc = res[0];
+        if (rc == ICX_PNM_OK) {
+            uint8_t* hostp = (uint8_t*)std::malloc(nout);
+            if (hostp && hipMemcpy(hostp, d_out.p, nout, hipMemcpyDeviceToHost) == hipSuccess) {
+                *out = hostp;
+                for (int k = 0; k < 5; ++k)
+                    if (res_out[k]) *res_out[k] = res[1 + k];
+            } else {
+                std::free(hostp);
+                ctx->err = "icx_pnm_decode: host allocation or copy failed";
+                rc = ICX_PNM_INTERNAL_ERR;
+            }
+        } else if (rc == ICX_PNM_INTERNAL_ERR) {
+            ctx->err = "icx_pnm_decode: the text kernels left no verdict";
+        }
+    } else {
+        const hipError_t e = hipGetLastError();
+        ctx->err = std::string("icx_pnm_decode: HIP failure: ") + hipGetErrorString(e);
+    }
+    return rc;
+}
+
+size_t icx_pnm_encode_bound(int width, int height, int d, int type, int format) {
+    return (size_t)pnm_encode_bound(width, height, d, type, format);
+}
+
+int icx_pnm_encode_device_batch(icx_ctx* ctx, int n, const void* const* d_src, const int32_t* widths,
+                                const int32_t* heights, int d, int type, int format, uint8_t* d_out, uint64_t out_stride,
+                                uint64_t* d_sizes, int32_t* d_status, void* stream) {
+    if (!ctx) return ICX_PNM_INTERNAL_ERR;
+    // (1, 1: whether this d, type and format go together at all)
+    if (n < 0 || n > 65535 || !pnm_write_args_ok(1, 1, d, type, format) ||
+        (n > 0 && (!d_src || !widths || !heights || !d_out || !d_sizes || !d_status)))
+        return ICX_PNM_INVALID_ARGUMENT;
+    if (n == 0) return ICX_PNM_OK;
+    ICX_HIP(ctx, hipSetDevice(ctx->device), ICX_PNM_INTERNAL_ERR);
+    const RoctxRange range("icx_pnm_encode_device_batch");
+    std::string err;
+    int rc;
+    try {  // (nothing may cross the C ABI: a host allocation failure is an internal error)
+        if (!ctx->pnmw) ctx->pnmw = pnmw_ws_create();
+        rc = pnm_encode_batch(stream ? (hipStream_t)stream : ctx->stream, *ctx->pnmw, n,
+                              reinterpret_cast<const uint8_t* const*>(d_src), widths, heights, d, type, format, d_out,
+                              out_stride, d_sizes, d_status, err);
+    } catch (const std::exception& e) {
+        err = std::string("icx_pnm_encode_device_batch: ") + e.what();
+        rc = -1;
+    }
+    if (rc != 0) {
+        ctx->err = err.empty() ? "icx_pnm_encode_device_batch: HIP failure" : err;
+        return ICX_PNM_INTERNAL_ERR;
+    }
+    return ICX_PNM_OK;
+}
+
+int icx_pnm_save_to_memory(icx_ctx* ctx, const void* pixels, int width, int height, int d, int type, int format,
+                           uint8_t** out, size_t* size) {
+    if (out) *out = nullptr;
+    if (size) *size = 0;
+    if (!ctx) return ICX_PNM_INTERNAL_ERR;
+    const uint64_t bound = pnm_encode_bound(width, height, d, type, format);
+    if (!pixels || !out || !size || bound == 0) return ICX_PNM_INVALID_ARGUMENT;
+    ICX_HIP(ctx, hipSetDevice(ctx->device), ICX_PNM_INTERNAL_ERR);
+    const uint64_t npx = (uint64_t)width * height * d * pnm_elem_bytes(type);
+    Buf<uint8_t> d_px, d_file;
+    Buf<uint64_t> d_res;  // the file's size, then its status
+    uint64_t res[2] = {0, 0};
+    hipStream_t st = ctx->stream;
+    if (!(d_px.reserve(npx) && d_file.reserve(bound) && d_res.reserve(16) &&
+          hipMemcpyAsync(d_px.p, pixels, npx, hipMemcpyHostToDevice, st) == hipSuccess)) {
+        ctx->err = std::string("icx_pnm_save_to_memory: ") + hipGetErrorString(hipGetLastError());
+        return ICX_PNM_INTERNAL_ERR;
+    }
+    const void* src = d_px.p;
+    const int32_t w = width, h = height;
+    const int rc = icx_pnm_encode_device_batch(ctx, 1, &src, &w, &h, d, type, format, d_file.p, bound, d_res.p,
+                                               reinterpret_cast<int32_t*>(d_res.p + 1), st);
+    if (rc != ICX_PNM_OK) return rc;
+    ICX_HIP(ctx, hipMemcpy(res, d_res.p, 16, hipMemcpyDeviceToHost), ICX_PNM_INTERNAL_ERR);
+    const int code = (int32_t)(res[1] & 0xFFFFFFFFu);
+    if (code != ICX_PNM_OK) return code;
+    uint8_t* hostp = (uint8_t*)std::malloc(res[0]);
+    if (!hostp || hipMemcpy(hostp, d_file.p, res[0], hipMemcpyDeviceToHost) != hipSuccess) {
+        std::free(hostp);
+        (void)hipGetLastError();
+        ctx->err = "icx_pnm_save_to_memory: host allocation or copy failed";
+        return ICX_PNM_INTERNAL_ERR;
+    }
+    *out = hostp;
+    *size = (size_t)res[0];
+    return ICX_PNM_OK;
+}
+
+int icx_pnm_save_to_file(icx_ctx* ctx, const char* path, const void* pixels, int width, int height, int d, int type,
+                         int format) {
+    if (!ctx) return ICX_PNM_INTERNAL_ERR;
+    if (!path) return ICX_PNM_INVALID_ARGUMENT;
+    uint8_t* mem = nullptr;
+    size_t size = 0;
+    const int rc = icx_pnm_save_to_memory(ctx, pixels, width, height, d, type, format, &mem, &size);
+    if (rc != ICX_PNM_OK) return rc;
+    std::FILE* f = std::fopen(path, "wb");
+    const bool ok = f && std::fwrite(mem, 1, size, f) == size;
+    const bool closed = f && std::fclose(f) == 0;
+    std::free(mem);
+    if (!ok || !closed) {
+        ctx->err = std::string("icx_pnm_save_to_file: cannot write ") + path;
+        return ICX_PNM_INTERNAL_ERR;
+    }
+    return ICX_PNM_OK;
 }
 
 // --------------------------------------------------------- Radiance .hdr write (Image::writeHdr)

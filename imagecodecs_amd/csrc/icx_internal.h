@@ -358,6 +358,33 @@ bool tga_ws_alloc(TgaWs& ws, Blocks& mem, int max_images, int max_w, int max_h, 
 void launch_tga_decode(const TgaWs& ws, int n, const uint8_t* d_data, const uint64_t* d_off, const uint64_t* d_size,
                        uint8_t* d_out, uint64_t out_stride, int32_t* d_status, int32_t* d_dims, hipStream_t st,
                        StageHook* hook);
+// Netpbm read and write (icx_pnm.hip; Image::readPbm / writePbm, codecs.cpp:1034-1167). Status
+// codes: icx_pnm_core.h kPnm* = include/icx.h ICX_PNM_*.
+struct PnmDesc;
+struct PnmWs {
+    int max_images = 0, max_w = 0, max_h = 0;
+    int64_t tiles_cap = 0;       // tiles of raster text per image; 0: a workspace for binary files only
+                                 // (an ASCII file is TOO_LARGE there)
+    PnmDesc* desc = nullptr;     // [max_images]
+    int4* summary = nullptr;     // [max_images][tiles_cap] token starts, carried comment bit, first illegal byte (k_pnm_tiles)
+    int64_t* tbase = nullptr;    // [max_images][tiles_cap] the tile's first sample index << 1 | starts in a comment (k_pnm_chain)
+};
+// The probe's code; for kPnmOk the header's values, and *raster_at = where the text of an ASCII
+// file starts (-1 for a binary file).
+int pnm_probe(const uint8_t* data, int64_t size, int* w, int* h, int* d, int* type, int* maxval, int64_t* raster_at);
+int64_t pnm_default_tiles(int max_w, int max_h);
+bool pnm_ws_alloc(PnmWs& ws, Blocks& mem, int max_images, int max_w, int max_h, int64_t tiles_cap);
+void launch_pnm_decode(const PnmWs& ws, int n, const uint8_t* d_data, const uint64_t* d_off, const uint64_t* d_size,
+                       uint8_t* d_out, uint64_t out_stride, int32_t* d_status, int32_t* d_dims, hipStream_t st,
+                       StageHook* hook);
+struct PnmwWs;  // grow-only buffers of the write
+PnmwWs* pnmw_ws_create();
+void pnmw_ws_destroy(PnmwWs* w);
+// 0, or -1 for a HIP failure (err says which). Synchronises with `st`.
+int pnm_encode_batch(hipStream_t st, PnmwWs& ws, int n, const uint8_t* const* d_src, const int32_t* widths,
+                     const int32_t* heights, int d, int type, int format, uint8_t* d_out, uint64_t out_stride,
+                     uint64_t* d_sizes, int32_t* d_status, std::string& err);
+
 struct TgawWs;  // grow-only buffers of the write
 TgawWs* tgaw_ws_create();
 void tgaw_ws_destroy(TgawWs* w);

@@ -570,6 +570,118 @@ int icx_tga_encode_device_batch(icx_ctx* ctx, int n, const uint8_t* const* d_src
                                 const int32_t* heights, int d, int rle, uint8_t* d_out, uint64_t out_stride,
                                 uint64_t* d_sizes, int32_t* d_status, void* hip_stream);
 
+/* ---- Netpbm read (Image::readPbm, codecs.cpp:1034-1100; PNM::load, pnm.h) ---------------------------
+ * PBM, PGM, PPM and PFM. The type comes from the magic, never from a file name:
+ *     P1, P4   channels 1, UBYTE: bit 0 -> 255, bit 1 -> 0 (codecs.cpp:1078-1079); maxval reads 255
+ *     P2, P5   channels 1; UBYTE when maxval <= 255, USHORT (host byte order) when 256 <= maxval <= 65535
+ *     P3, P6   channels 3; the same types
+ *     Pf, PF   channels 1 / 3, FLOAT; maxval reads 0
+ * Rows are top-down in the output. Samples are passed as stored, not rescaled to the type's range;
+ * maxval is returned. Binary 16-bit samples are big-endian in the file. P4 rows are padded to whole
+ * bytes. PFM rows are bottom-to-top in the file (codecs.cpp:1096-1099); a negative scale means
+ * little-endian floats, a positive one big-endian floats, which are byte-swapped; the scale's
+ * magnitude is not applied and the bits are otherwise copied (NaN payloads survive).
+ * Header: the two magic bytes, then width, height and -- P2, P3, P5, P6 -- maxval or -- PF, Pf -- the
+ * scale. A token is a run of bytes other than whitespace (space, TAB, LF, VT, FF, CR) and '#';
+ * tokens are separated by any run of whitespace and comments, a comment being a '#' and everything
+ * up to and including the next LF or CR (nothing need stand between the magic and the width). For
+ * P4, P5, P6, PF, Pf exactly one whitespace byte follows the last token and the raster starts at
+ * the next byte; for P1, P2, P3 the text starts right after the last token. Only the first image
+ * is read; bytes after its raster are ignored.
+ * Text rasters: outside comments a byte is a digit, whitespace, '#' or illegal. In P2 / P3 a sample
+ * is a maximal run of digits (leading zeros allowed, any length); a value above maxval is
+ * BAD_DATA. In P1 every '0' or '1' is one sample, separated or not, and any other digit is
+ * illegal. With E the end of the last needed sample's token, or the end of the file if there are
+ * too few: an illegal byte or an oversize value before E gives BAD_DATA; otherwise fewer samples
+ * than width*height*channels give TRUNCATED; nothing after E is examined. A binary raster shorter
+ * than it must be is TRUNCATED. A failed image yields no pixels. (Speed, not contract: a token is
+ * walked by one GPU lane, a byte at a time, so a file with a very long run of leading zeros in one
+ * sample decodes correctly but slowly.)
+ * Deliberate deviations: the reference picks the conversion by filepath.find(".pbm") / (".pfm")
+ * (a P4 file named .pnm comes back as packed bits, a P5 file named .pbm throws); it ignores maxval
+ * (a 16-bit file makes it read half the raster, and an ASCII value above 255 is truncated to a
+ * byte); it reads the digits "0101" of a P1 file as the number 101. */
+enum icx_pnm_result {
+    ICX_PNM_OK = 0,
+    ICX_PNM_NOT_PNM = 1,           /* fewer than 2 bytes, or not 'P' followed by '1'-'7', 'F' or 'f' */
+    ICX_PNM_BAD_HEADER = 2,        /* a missing or non-numeric token or one of more than 10 digits; zero
+                                      width or height; maxval 0 or above 65535; a scale that is zero
+                                      (no mantissa digit other than '0'), not finite as a float, or not of
+                                      the form [+-]digits[.digits][e[+-]digits]; no whitespace byte after
+                                      the last token of a binary type; the file ends inside the header */
+    ICX_PNM_UNSUPPORTED = 3,       /* P7 (PAM)                                                      */
+    ICX_PNM_BAD_DATA = 4,          /* text rasters: see above                                       */
+    ICX_PNM_TRUNCATED = 5,         /* the raster ends first                                         */
+    ICX_PNM_TOO_LARGE = 6,         /* more than 2^30 pixels; larger than the batch workspace / the output slot */
+    ICX_PNM_INVALID_ARGUMENT = 7,  /* write: see below; batch read: d_out or out_stride not 16-byte aligned */
+    ICX_PNM_INTERNAL_ERR = -1      /* HIP failure (see icx_last_error)                              */
+};
+/* `type` values: ImageCodecs::Type. */
+enum icx_pnm_type { ICX_PNM_UBYTE = 0, ICX_PNM_USHORT = 1, ICX_PNM_FLOAT = 2 };
+/* Header only (host): the header's values, or the code it gives (in the order NOT_PNM, UNSUPPORTED,
+ * BAD_HEADER, TOO_LARGE for more than 2^30 pixels); for a binary type also TRUNCATED. The text of
+ * an ASCII file is checked by the decode. Outputs are zero unless ICX_PNM_OK. */
+int icx_pnm_probe(const uint8_t* data, size_t size, int* width, int* height, int* channels, int* type, int* maxval);
+/* One image, host in / host out: *out receives a malloc()'d buffer of width*height*channels
+ * elements of 1, 2 or 4 bytes (free with icx_free), null unless ICX_PNM_OK. A code the probe gives
+ * returns without touching the GPU. */
+int icx_pnm_decode(icx_ctx* ctx, const uint8_t* data, size_t size, void** out, int* width, int* height, int* channels,
+                   int* type, int* maxval);
+/* Device-resident batch: image i = d_data[d_offsets[i] .. + d_sizes[i]), output at
+ * d_out + i*out_stride, per-image status in d_status[i] and {width, height, channels, type,
+ * maxval} in d_dims[5i..] (all zero for a failed image, whose slot is unspecified; nothing is
+ * written outside the slots). d_out must be 16-byte aligned and out_stride a multiple of 16, else
+ * the call returns ICX_PNM_INVALID_ARGUMENT. An image whose output is longer than out_stride, wider
+ * than max_width or higher than max_height is TOO_LARGE; so is a text file whose needed samples do
+ * not end within the workspace's 8 bytes of text per sample of a max_width x max_height RGB image.
+ * Asynchronous on hip_stream (NULL = the context's stream), no host read-back. Returns ICX_PNM_OK,
+ * ICX_PNM_INVALID_ARGUMENT or ICX_PNM_INTERNAL_ERR. */
+typedef struct icx_pnm_batch icx_pnm_batch;
+icx_pnm_batch* icx_pnm_batch_create(icx_ctx* ctx, int max_images, int max_width, int max_height);
+void icx_pnm_batch_destroy(icx_pnm_batch* b);
+int icx_pnm_batch_decode(icx_pnm_batch* b, int n, const uint8_t* d_data, const uint64_t* d_offsets,
+                         const uint64_t* d_sizes, void* d_out, uint64_t out_stride, int32_t* d_status, int32_t* d_dims,
+                         void* hip_stream);
+/* Milliseconds per stage of the last icx_pnm_batch_decode ("parse", "locate", "text", "stream";
+ * synchronises). Returns the number of stages. */
+int icx_pnm_batch_stage_times(const icx_pnm_batch* b, const char** names, float* ms, int cap);
+
+/* ---- Netpbm write (Image::writePbm, codecs.cpp:1102-1167) -----------------------------------------
+ * `pixels`: width*height*d elements of `type`, rows top-down, host byte order. The headers are the
+ * reference's bytes (codecs.cpp:1112, 1154, 1160):
+ *     ICX_PNM_P4   "P4\n<w> <h>\n"            UBYTE, d = 1: rows packed MSB first and padded to a byte,
+ *                                             bit = 1 exactly where the pixel byte is 0 (:1139)
+ *     ICX_PNM_P5   "P5\n<w> <h>\n<maxval>\n"  UBYTE / USHORT, d = 1: as stored; maxval 255 / 65535
+ *     ICX_PNM_P6   "P6\n<w> <h>\n<maxval>\n"  UBYTE / USHORT, d = 3 or 4: R,G,B; with d = 4 the fourth
+ *                                             sample is dropped
+ *     ICX_PNM_PF   "PF\n<w> <h>\n-1.0\n" (d = 3) or "Pf..." (d = 1), FLOAT: little-endian floats, rows
+ *                                             bottom-to-top
+ * Extensions: USHORT (written big-endian, as the format demands) and d = 4 (what read(".png")
+ * returns can be written). Deviation, by evident intent: the reference writes the rows of a PFM
+ * unflipped but flips on read, so its own round trip turns the picture over; here decode(encode(x))
+ * is x. Any other combination of format, type and d, a width or height below 1, more than 2^30
+ * pixels or a null pointer -> ICX_PNM_INVALID_ARGUMENT. Plain (ASCII) files are not written. */
+enum icx_pnm_format { ICX_PNM_P4 = 4, ICX_PNM_P5 = 5, ICX_PNM_P6 = 6, ICX_PNM_PF = 8 };
+/* The file's length; 0 for arguments the writes refuse. Host only. */
+size_t icx_pnm_encode_bound(int width, int height, int d, int type, int format);
+/* Host pixels in, *out receives the malloc()'d file (free with icx_free). Returns an icx_pnm_result. */
+int icx_pnm_save_to_memory(icx_ctx* ctx, const void* pixels, int width, int height, int d, int type, int format,
+                           uint8_t** out, size_t* size);
+/* The same file written to `path` (ICX_PNM_INTERNAL_ERR when it cannot be written). */
+int icx_pnm_save_to_file(icx_ctx* ctx, const char* path, const void* pixels, int width, int height, int d, int type,
+                         int format);
+/* n writes with pixels and files resident on the device: image i's pixels at d_src[i] (a host
+ * array of device pointers, any alignment; widths / heights are host arrays), its file to
+ * d_out + i*out_stride (any alignment), the file's length to d_sizes[i] and an icx_pnm_result to
+ * d_status[i] (device arrays): INVALID_ARGUMENT for a bad size or null source (length 0),
+ * TOO_LARGE (nothing of the file written, d_sizes[i] says what it needs) when it is longer than
+ * out_stride. A d, type and format that do not go together, n < 0, n > 65535 (one call's limit:
+ * split larger batches) or a null array with n > 0 -> the call returns ICX_PNM_INVALID_ARGUMENT.
+ * Runs on hip_stream (NULL = the context's stream) and synchronises with it. */
+int icx_pnm_encode_device_batch(icx_ctx* ctx, int n, const void* const* d_src, const int32_t* widths,
+                                const int32_t* heights, int d, int type, int format, uint8_t* d_out, uint64_t out_stride,
+                                uint64_t* d_sizes, int32_t* d_status, void* hip_stream);
+
 /* ---- GIF read (Image::readGif, codecs.cpp:507-542; gd_open_gif / gd_get_frame / gd_render_frame,
  * gif.cpp:43-524) -----------------------------------------------------------------------------------
  * Output as readGif returns it for a well-formed file: Type::UBYTE, 3 channels, the logical

@@ -29,6 +29,13 @@
  *               RGB and RGBA. channels() is 1, 3 or 4. A file the read refuses (codes in
  *               include/icx.h) leaves pixels_ null and read() throws "Could not read image data".
  *               write(".tif") stays outside this path.
+ *               ".pbm"/".pgm"/".ppm"/".pnm"/".pfm" decode Netpbm on the GPU (readPbm, codecs.cpp:1034-1100
+ *               -> icx_pnm_decode): P1 .. P6, Pf and PF, told apart by the magic, not by the name.
+ *               channels() is 1 or 3; type() is UBYTE (bitmaps: 0 -> 255, 1 -> 0; maxval <= 255),
+ *               USHORT (maxval 256 .. 65535, host byte order) or FLOAT (PFM: rows turned top-down,
+ *               big-endian files byte-swapped, bits otherwise untouched). Samples are not rescaled.
+ *               A file the read refuses (codes in include/icx.h) leaves pixels_ null and read()
+ *               throws "Could not read image data".
  *   write(path) -- ".jpg"/".jpeg" encode with tiny_jpeg quality 3 semantics (writeJpg,
  *                  codecs.cpp:851-854 -> icx_tje_encode_to_file, byte-identical stream).
  *               ".png" encodes with png_encoder::saveToFile semantics (writePng,
@@ -46,7 +53,16 @@
  *               -> icx_hdr_save_to_file, rle = 0); writing what was read reproduces every RGBE
  *               byte. d != 4 throws std::runtime_error("HDR data must contain a 4th channel of
  *               exposure values") (:781-784); any other failure throws nothing (lastWriteOk() tells).
- *   pixels_ is new[]-owned and delete[]-d by ~Image (codecs.h:102); load() adopts a buffer.
+ *               ".pbm" writes P4 (UBYTE, d = 1: bit 1 where the byte is 0), ".pgm" P5 (d = 1), ".ppm" P6
+ *               (d = 3, or 4 with the fourth sample dropped), ".pnm" P5 for d = 1 and P6 otherwise,
+ *               ".pfm" PF (d = 3) or Pf (d = 1), with the reference's header bytes (writePbm,
+ *               codecs.cpp:1102-1167 -> icx_pnm_save_to_file). P5 / P6 take UBYTE (maxval 255) and
+ *               USHORT (maxval 65535, big-endian). ".pfm" of non-float data throws
+ *               std::runtime_error("Cannot write non-float data to .pfm") (:1149-1152); any other
+ *               failure -- a d or type the format does not take included -- throws nothing
+ *               (lastWriteOk() tells).
+ *   pixels_ is new[]-owned and delete[]-d by ~Image (codecs.h:102); load() adopts a buffer;
+ *   load(pixels, w, h, channels, Type) is an extension that also states the element type.
  * Every other extension is outside this path: it throws std::invalid_argument exactly like the
  * reference's unknown-extension branch (codecs.cpp:80-83), so a build that needs those codecs
  * keeps the reference's codecs.cpp for them.
@@ -99,6 +115,16 @@
  * TIFFReadRGBAImage's premultiply; and the bytes of a pixel are R, G, B, A in this order (the
  * reference's (currPix >> j) & 0xff shifts by j bits where 8 * j was meant, codecs.cpp:1471-1477).
  * Only 8-bit samples are read.
+ * Netpbm read (contract in include/icx.h): the type is the magic's (the reference decides by
+ * filepath.find(".pbm") / (".pfm"): a P4 file named .pnm comes back as packed bits, and its
+ * ".pbm" branch throws for any other magic); maxval decides between UBYTE and USHORT and bounds the
+ * ASCII samples (the reference ignores it: it reads half of a 16-bit raster and truncates larger
+ * ASCII values to a byte); in a P1 file every '0' / '1' is a sample, as the specification says (the
+ * reference reads "0101" as the number 101); a PFM's positive scale means big-endian floats, which
+ * are byte-swapped (the reference copies them as they are). Netpbm write, by evident intent: a PFM's
+ * rows are written bottom-to-top (the reference writes them unflipped but flips on read, so its own
+ * round trip turns the picture over); ".pnm" of a d = 1 image is P5 (the reference writes "P6" over
+ * one sample per pixel); USHORT and d = 4 are accepted as described above.
  *
  * Header-only; link with -L<repo>/imagecodecs_amd/lib -licx. One icx context per process
  * (device ICX_DEVICE, default 0), created on first use and serialised by a mutex -- the
@@ -146,6 +172,9 @@ inline std::string lower_ext(const std::string& path) {
     std::string e = std::filesystem::path(path).extension().string();
     for (auto& c : e) c = (char)std::tolower((unsigned char)c);
     return e;
+}
+inline bool is_pnm_ext(const std::string& e) {
+    return e == ".pbm" || e == ".pgm" || e == ".ppm" || e == ".pnm" || e == ".pfm";
 }
 }  // namespace detail
 
@@ -436,6 +465,63 @@ class Image {
         if (!last_write_ok_) std::fprintf(stderr, "icx_tga_save_to_file -> %d %s\n", rc, icx_last_error(c));
     }
 
+    // readPbm (codecs.cpp:1034-1100): P1 .. P6, Pf and PF by the file's magic, whatever its name;
+    // d = 1 or 3, Type::UBYTE, USHORT or FLOAT, rows top-down, decoded on the GPU (icx_pnm_decode). A
+    // failure leaves pixels_ null, and read() throws "Could not read image data" (:85-88).
+    void readPnm(const std::string& path) {
+        std::FILE* f = std::fopen(path.c_str(), "rb");
+        std::vector<uint8_t> buf;
+        if (f) {
+            uint8_t chunk[1 << 16];
+            size_t k;
+            while ((k = std::fread(chunk, 1, sizeof chunk, f)) > 0) buf.insert(buf.end(), chunk, chunk + k);
+            std::fclose(f);
+        }
+        auto& P = detail::icx_process();
+        std::lock_guard<std::mutex> lock(P.mu);
+        void* out = nullptr;
+        int w = 0, h = 0, d = 0, type = 0, maxval = 0;
+        const int rc = icx_pnm_decode(P.get(), buf.data(), buf.size(), &out, &w, &h, &d, &type, &maxval);
+        delete[] pixels_;
+        pixels_ = nullptr;
+        w_ = h_ = d_ = 0;
+        if (rc == ICX_PNM_INTERNAL_ERR) throw std::runtime_error(std::string("icx_pnm_decode: ") + icx_last_error(P.get()));
+        if (rc != ICX_PNM_OK) return;
+        const Type t = type == ICX_PNM_FLOAT ? Type::FLOAT : type == ICX_PNM_USHORT ? Type::USHORT : Type::UBYTE;
+        const size_t n = (size_t)w * h * d * byteSize(t);
+        pixels_ = new unsigned char[n ? n : 1];
+        if (n) std::memcpy(pixels_, out, n);
+        icx_free(out);
+        w_ = w;
+        h_ = h;
+        d_ = d;
+        type_ = t;
+    }
+
+    // writePbm (codecs.cpp:1102-1167): ".pbm" P4, ".pgm" P5, ".ppm" P6, ".pnm" P5 for d = 1 and P6
+    // otherwise, ".pfm" PF / Pf. ".pfm" of non-float data throws (:1149-1152); as for the other
+    // writers any other failure -- no usable GPU included -- only prints the message; the result
+    // stays queryable.
+    void writePnm(const std::string& path, const std::string& ext) {
+        last_write_ok_ = false;
+        if (ext == ".pfm" && type_ != Type::FLOAT) throw std::runtime_error("Cannot write non-float data to .pfm");
+        auto& P = detail::icx_process();
+        std::lock_guard<std::mutex> lock(P.mu);
+        icx_ctx* c = nullptr;
+        try {
+            c = P.get();
+        } catch (const std::runtime_error& e) {
+            std::fprintf(stderr, "%s\n", e.what());
+            return;
+        }
+        const int format = ext == ".pbm" ? ICX_PNM_P4 : ext == ".pgm" ? ICX_PNM_P5 : ext == ".ppm" ? ICX_PNM_P6
+                         : ext == ".pfm" ? ICX_PNM_PF : d_ == 1 ? ICX_PNM_P5 : ICX_PNM_P6;
+        const int type = type_ == Type::FLOAT ? ICX_PNM_FLOAT : type_ == Type::USHORT ? ICX_PNM_USHORT : ICX_PNM_UBYTE;
+        const int rc = icx_pnm_save_to_file(c, path.c_str(), pixels_, w_, h_, d_, type, format);
+        last_write_ok_ = rc == ICX_PNM_OK;
+        if (!last_write_ok_) std::fprintf(stderr, "icx_pnm_save_to_file -> %d %s\n", rc, icx_last_error(c));
+    }
+
     // writeHdr (codecs.cpp:779-818): the reference's header and four RGBE bytes per pixel. As in the
     // reference d != 4 throws (:781-784) and type_ is not consulted (pixels_ is read as w*h*4
     // floats). Any other failure -- no usable GPU included -- only prints the message; the result
@@ -511,6 +597,12 @@ public:
         h_ = h;
         pixels_ = pixels;
     }
+    // Extension: the same with the element type stated (the reference's load cannot say that a
+    // buffer holds USHORT or FLOAT elements, which write(".pgm") / write(".pfm") need to know).
+    void load(unsigned char* pixels, int w, int h, int channels, Type type) {
+        load(pixels, w, h, channels);
+        type_ = type;
+    }
 
     void read(const std::string& filepath) {
         const std::string ext = detail::lower_ext(filepath);
@@ -521,6 +613,7 @@ public:
         else if (ext == ".tga") readTga(filepath);
         else if (ext == ".gif") readGif(filepath);
         else if (ext == ".tif" || ext == ".tiff") readTiff(filepath);
+        else if (detail::is_pnm_ext(ext)) readPnm(filepath);
         else throw std::invalid_argument("Cannot parse filetype");
         if (pixels_ == nullptr) throw std::runtime_error("Could not read image data");
     }
@@ -532,6 +625,7 @@ public:
         else if (ext == ".exr") writeExr(filepath);
         else if (ext == ".tga") writeTga(filepath);
         else if (ext == ".hdr") writeHdr(filepath);
+        else if (detail::is_pnm_ext(ext)) writePnm(filepath, ext);
         else throw std::invalid_argument("Cannot parse filetype");
     }
 };

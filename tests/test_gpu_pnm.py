@@ -1,0 +1,436 @@
+"""GPU Netpbm read and write (Image::readPbm / writePbm, codecs.cpp:1034-1167; contract in
+include/icx.h) through the C ABI, against the restatement in tests/pnmutil.py, the reference's
+fixtures and PIL.
+
+Read: status, size, type, maxval and every output byte equal the restatement's. Write: the files
+equal the restatement's byte for byte, and decode(encode(x)) == x."""
+import io
+import os
+
+import numpy as np
+import pytest
+
+import imagecodecs_amd as icx
+import pnmutil as U
+
+pytestmark = pytest.mark.gpu
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "pnm")
+FIXTURES = {n: open(os.path.join(GOLDEN, n), "rb").read() for n in ("test.pbm", "test.pgm", "test.ppm", "test.pnm", "test_48rows.pfm")}
+TILE = icx.PNM_ASCII_TILE
+STAGES = {"parse", "locate", "text", "stream"}
+FAILED = (0, 0, 0, 0, 0)
+
+
+@pytest.fixture(scope="module")
+def ctx():
+    c = icx.Context(0)
+    yield c
+    c.close()
+
+
+def _same(got, data, name=""):
+    ref = U.decode(data)
+    assert got[0] == ref[0], (name, got[0], ref[0])
+    if ref[0] == U.OK:
+        assert got[1:6] == ref[1:6], name
+        assert got[6].dtype == ref[6].dtype and got[6].shape == ref[6].shape, name
+        assert got[6].tobytes() == ref[6].tobytes(), name  # (bytes: NaN payloads count)
+    else:
+        assert got[1:6] == FAILED and got[6] is None, name
+
+
+def _batch(ctx, files, max_w, max_h, stride=None, misalign=0):
+    """One icx_pnm_batch_decode over `files` -> ([(code, w, h, d, type, maxval, array or None)], stage
+    times). The slots sit between guard bytes; whatever an OK image does not own must stay 0xA5."""
+    import torch
+    dev = torch.device("cuda", 0)
+    n = len(files)
+    sizes = np.array([len(f) for f in files], np.int64)
+    offs = np.zeros(n, np.int64)
+    offs[1:] = np.cumsum(sizes)[:-1]
+    blob = b"".join(files) or b"\0"
+    data = torch.from_numpy(np.frombuffer(blob, np.uint8).copy()).to(dev)
+    d_off = torch.from_numpy(offs).to(dev)
+    d_sz = torch.from_numpy(sizes).to(dev)
+    if stride is None:
+        stride = (12 * max_w * max_h + 15) & ~15
+    guard = 256
+    out = torch.full((guard + n * stride + guard,), 0xA5, dtype=torch.uint8, device=dev)
+    assert out.data_ptr() % 16 == 0
+    st = torch.full((n,), -9, dtype=torch.int32, device=dev)
+    dims = torch.full((n, 5), -9, dtype=torch.int32, device=dev)
+    b = icx.PnmBatch(ctx, n, max_w, max_h)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    torch.cuda.synchronize(dev)  # (the fills above are done before another stream writes)
+    rc = b.decode_device(n, data.data_ptr(), d_off.data_ptr(), d_sz.data_ptr(), out.data_ptr() + guard + misalign, stride,
+                         st.data_ptr(), dims.data_ptr(), stream)
+    torch.cuda.synchronize(dev)
+    if rc != icx.PNM_OK:
+        b.close()
+        assert (out.cpu().numpy() == 0xA5).all() and (st.cpu().numpy() == -9).all()
+        return rc, None
+    times = b.stage_times()
+    b.close()
+    out, st, dims = out.cpu().numpy(), st.cpu().numpy(), dims.cpu().numpy()
+    assert (out[:guard] == 0xA5).all() and (out[-guard:] == 0xA5).all()
+    res = []
+    for i in range(n):
+        w, h, d, t, mv = (int(v) for v in dims[i])
+        slot = out[guard + i * stride: guard + (i + 1) * stride]
+        arr = None
+        if st[i] == icx.PNM_OK:
+            nb = w * h * d * (1, 2, 4)[t]
+            arr = slot[:nb].view(U.DTYPES[t]).reshape(h, w, d).copy()
+            assert (slot[nb:] == 0xA5).all(), f"image {i} wrote past its pixels"
+        res.append((int(st[i]), w, h, d, t, mv, arr))
+    return res, times
+
+
+# ------------------------------------------------------------------------------------ read
+@pytest.mark.parametrize("name", sorted(FIXTURES))
+def test_pnm_fixtures(ctx, name):
+    got = ctx.pnm_decode(FIXTURES[name])
+    assert got[0] == icx.PNM_OK and got[1:3] == (499, 48 if name.endswith("pfm") else 289)
+    _same(got, FIXTURES[name], name)
+
+
+@pytest.mark.parametrize("kind", U.BINARY_KINDS)
+def test_pnm_binary_sizes(ctx, kind):
+    """w in 1, 7, 8, 9, 63, 64, 65, 499 x h in 1, 2, 3, 17: one batch call, and each file alone."""
+    cases = U.binary_cases(kind)
+    res, times = _batch(ctx, [f for _, f, _ in cases], 499, 17)
+    assert set(times) == STAGES
+    for (name, f, px), got in zip(cases, res):
+        assert got[0] == icx.PNM_OK and got[6].tobytes() == px.tobytes(), name
+        _same(got, f, name)
+        _same(ctx.pnm_decode(f), f, name)
+
+
+def test_pnm_raster_at_every_alignment(ctx):
+    cases = U.align_cases()
+    assert {U.parse(f)[1]["rs"] % 16 for n, f in cases if n.startswith("P6")} == set(range(16))
+    for name, f in cases:
+        _same(ctx.pnm_decode(f), f, name)
+    res, _ = _batch(ctx, [f for _, f in cases], 37, 5)
+    for (name, f), got in zip(cases, res):
+        _same(got, f, name)
+
+
+def test_pnm_maxval_and_float_payloads(ctx):
+    cases = U.maxval_cases() + U.float_cases()
+    assert {U.decode(f)[0] for _, f in cases} == {U.OK, U.BAD_DATA}
+    assert {U.decode(f)[5] for _, f in cases} >= {1, 254, 255, 256, 65535, 0}
+    for name, f in cases:
+        _same(ctx.pnm_decode(f), f, name)
+    special = [f for n, f in cases if n.startswith("special")]
+    assert all(np.isnan(U.decode(f)[6]).any() for f in special)
+    res, _ = _batch(ctx, [f for _, f in cases], 13, 3)
+    for (name, f), got in zip(cases, res):
+        _same(got, f, name)
+
+
+@pytest.mark.parametrize("case", U.text_general_cases(TILE), ids=lambda c: c[0])
+def test_pnm_text_over_three_tiles(ctx, case):
+    name, f = case
+    assert len(f) - U.parse(f)[1]["rs"] >= 3 * TILE and U.decode(f)[0] == U.OK
+    _same(ctx.pnm_decode(f), f, name)
+    cut = f[:U.parse(f)[1]["rs"] + 2 * TILE + 1]  # the text ends one byte into the third tile
+    assert U.decode(cut)[0] == U.TRUNCATED
+    _same(ctx.pnm_decode(cut), cut, name + "_cut")
+
+
+def test_pnm_text_tokens_at_tile_edges(ctx):
+    """A 5-digit token with k = 0 .. 5 of its digits before each of the first two tile edges."""
+    cases = U.text_edge_cases(TILE)
+    assert len(cases) == 24
+    for name, f in cases:
+        _same(ctx.pnm_decode(f), f, name)
+    res, _ = _batch(ctx, [f for _, f in cases], 1500, 1)
+    for (name, f), got in zip(cases, res):
+        _same(got, f, name)
+
+
+def test_pnm_text_p1(ctx):
+    for name, (f, px) in U.p1_cases(TILE):
+        got = ctx.pnm_decode(f)
+        assert got[0] == icx.PNM_OK and (got[6] == px).all(), name
+        _same(got, f, name)
+
+
+def test_pnm_text_error_positions(ctx):
+    cases = U.text_error_cases()
+    for name, f, code in cases:
+        got = ctx.pnm_decode(f)
+        assert got[0] == code, name
+        _same(got, f, name)
+    res, _ = _batch(ctx, [f for _, f, _ in cases], 4, 2)
+    for (name, f, code), got in zip(cases, res):
+        _same(got, f, name)
+
+
+def test_pnm_every_prefix_and_bit_flips(ctx):
+    """Every prefix of a small P6 and a small P3 file and 200 bit flips of each: every result code."""
+    cases = U.prefix_and_flip_cases()
+    files = [f if f else b"" for _, f in cases]
+    res, _ = _batch(ctx, files, 64, 64)
+    seen = set()
+    for (name, f), got in zip(cases, res):
+        ref = U.decode(f)
+        if ref[0] == U.OK and (ref[1] > 64 or ref[2] > 64):
+            assert got[0] == icx.PNM_TOO_LARGE, name
+            continue
+        _same(got, f, name)
+        seen.add(got[0])
+    assert seen >= {U.OK, U.NOT_PNM, U.BAD_HEADER, U.BAD_DATA, U.TRUNCATED}
+    for name, f in cases[::7]:
+        _same(ctx.pnm_decode(f), f, name)
+
+
+def test_pnm_header_codes_single(ctx):
+    for name, f, code in U.header_cases():
+        got = ctx.pnm_decode(f)
+        if code == U.OK:  # (the header is fine; the raster decides)
+            _same(got, f, name)
+        else:
+            assert got[0] == code and got[1:6] == FAILED and got[6] is None, name
+
+
+# ------------------------------------------------------------------------------------ batches
+def _mixed_files():
+    files = []
+    for k in range(8):
+        w, h = 5 + 7 * k, 3 + k
+        files.append(U.binary_case("P4", k, w, h)[0])
+        files.append(U.binary_case("P5" if k & 1 else "P5_16", k, w, h, b"#" + b"c" * k + b"\n")[0])
+        files.append(U.binary_case("P6_16" if k & 1 else "P6", k, w, h)[0])
+        files.append(U.binary_case("Pf_be" if k & 1 else "Pf_le", k, w, h)[0])
+        files.append(U.binary_case("PF_le" if k & 1 else "PF_be", k, w, h)[0])
+        files.append(U.text_file(b"1", w, h, 0, [b"1" if v else b"0" for v in U.bitmap(k, w, h).reshape(-1)], [b"", b" ", b"\n"]))
+        mv = 65535 if k & 1 else 255
+        files.append(U.text_file(b"2", w, h, mv, U.text_of(U.synth(k, w, h, 1, U.USHORT if k & 1 else U.UBYTE)), U.SEPARATORS))
+        files.append(U.text_file(b"3", w, h, 255, U.text_of(U.synth(k, w, h, 3), (1, 3, 4), k), [b" ", b"\r\n"]))
+    return files
+
+
+def test_pnm_batch_64_mixed(ctx):
+    files = _mixed_files()
+    assert len(files) == 64
+    refs = [U.decode(f) for f in files]
+    assert all(r[0] == U.OK for r in refs) and {r[4] for r in refs} == {U.UBYTE, U.USHORT, U.FLOAT}
+    assert {f[:2] for f in files} == {b"P1", b"P2", b"P3", b"P4", b"P5", b"P6", b"Pf", b"PF"}
+    res, times = _batch(ctx, files, 54, 10)
+    assert set(times) == STAGES
+    for k, (f, got) in enumerate(zip(files, res)):
+        _same(got, f, f"mixed{k}")
+
+
+def test_pnm_batch_failed_file_between_good_ones(ctx):
+    good = _mixed_files()[:8]
+    bad = [b"P6 2 2 255\n" + bytes(11), b"P2 2 2 9 1 2 3 x", b"GIF89a", b"P5 2 2 0\n" + bytes(4)]
+    files = [good[0], bad[0], good[1], bad[1], good[5], bad[2], good[7], bad[3], good[4]]
+    res, _ = _batch(ctx, files, 54, 10)
+    assert [r[0] for r in res] == [0, U.TRUNCATED, 0, U.BAD_DATA, 0, U.NOT_PNM, 0, U.BAD_HEADER, 0]
+    for k, (f, got) in enumerate(zip(files, res)):
+        _same(got, f, f"between{k}")
+
+
+def test_pnm_batch_slot_too_small(ctx):
+    """An image longer than out_stride, wider or higher than the workspace is TOO_LARGE; its
+    neighbours are intact and nothing outside the slots is written (checked by _batch)."""
+    ok8 = U.binary_case("P6", 1, 8, 4)[0]  # 96 bytes: fits 96
+    big = U.binary_case("P6_16", 2, 8, 4)[0]  # 192 bytes
+    flt = U.binary_case("Pf_le", 3, 8, 4)[0]  # 128 bytes
+    txt = U.text_file(b"3", 8, 4, 65535, U.text_of(U.synth(4, 8, 4, 3, U.USHORT)), [b" "])  # 192 bytes
+    wide = U.binary_case("P4", 5, 9, 1)[0]
+    tall = U.binary_case("P5", 6, 1, 5)[0]
+    files = [ok8, big, ok8, flt, txt, wide, tall, ok8]
+    res, _ = _batch(ctx, files, 8, 4, stride=96)
+    assert [r[0] for r in res] == [0, U.TOO_LARGE, 0, U.TOO_LARGE, U.TOO_LARGE, U.TOO_LARGE, U.TOO_LARGE, 0]
+    for k in (0, 2, 7):
+        _same(res[k], ok8, f"slot{k}")
+    assert all(r[1:6] == FAILED for r in res if r[0] != 0)
+
+
+def test_pnm_batch_alignment_is_demanded(ctx):
+    files = [U.binary_case("P5", 1, 8, 4)[0]]
+    assert _batch(ctx, files, 8, 4, stride=40)[0] == icx.PNM_INVALID_ARGUMENT
+    assert _batch(ctx, files, 8, 4, stride=48, misalign=8)[0] == icx.PNM_INVALID_ARGUMENT
+
+
+def test_pnm_batch_text_longer_than_the_workspace(ctx):
+    """The workspace holds 8 bytes of text per sample of a max_w x max_h RGB image (plus a tile): a
+    file whose samples end within it decodes whatever follows; one that needs more is TOO_LARGE."""
+    px = U.synth(9, 4, 4, 1)
+    short = U.text_file(b"2", 4, 4, 255, U.text_of(px), [b" "])
+    cap = ((4 * 4 * 3 * 8 + TILE - 1) // TILE + 1) * TILE
+    trailer = short + b"# " + b"x" * (2 * cap) + b"\n"
+    late = U.text_file(b"2", 4, 4, 255, U.text_of(px), [b" "], lead=b"\n#" + b"y" * cap + b"\n")
+    res, _ = _batch(ctx, [short, trailer, late, short], 4, 4)
+    _same(res[0], short)
+    _same(res[1], trailer)
+    _same(res[3], short)
+    assert res[2][0] == icx.PNM_TOO_LARGE and res[2][1:6] == FAILED
+    _same(ctx.pnm_decode(late), late, "late_single")  # (alone, the workspace is sized by the file)
+
+
+# ------------------------------------------------------------------------------------ write
+WRITE_KINDS = [("P4", U.P4, 1, U.UBYTE), ("P5", U.P5, 1, U.UBYTE), ("P5_16", U.P5, 1, U.USHORT), ("P6", U.P6, 3, U.UBYTE),
+               ("P6_16", U.P6, 3, U.USHORT), ("P6_rgba", U.P6, 4, U.UBYTE), ("P6_16_rgba", U.P6, 4, U.USHORT),
+               ("Pf", U.PF, 1, U.FLOAT), ("PF", U.PF, 3, U.FLOAT)]
+
+
+@pytest.mark.parametrize("kind", WRITE_KINDS, ids=lambda k: k[0])
+def test_pnm_encode_bytes_and_round_trip(ctx, kind):
+    name, fmt, d, typ = kind
+    for w in U.WIDTHS:
+        for h in U.HEIGHTS:
+            px = U.bitmap(w + h, w, h) if fmt == U.P4 else U.synth(3 * w + h, w, h, d, typ)
+            code, data = ctx.pnm_encode(px, fmt)
+            assert code == icx.PNM_OK and data == U.encode(px, fmt), (name, w, h)
+            assert len(data) == icx.pnm_encode_bound(w, h, d, typ, fmt)
+            got = ctx.pnm_decode(data)
+            _same(got, data, f"{name}_{w}x{h}")
+            assert got[6].tobytes() == np.ascontiguousarray(px[:, :, :3]).tobytes(), (name, w, h)
+            if d == 4:
+                assert data == ctx.pnm_encode(np.ascontiguousarray(px[:, :, :3]), fmt)[1], (name, w, h)
+
+
+def test_pnm_encode_unaligned_source(ctx):
+    """Pixels at an odd device address and files at an odd stride."""
+    import torch
+    dev = torch.device("cuda", 0)
+    for fmt, d, typ, off in ((U.P6, 4, U.UBYTE, 3), (U.P4, 1, U.UBYTE, 5), (U.P5, 1, U.USHORT, 2), (U.PF, 3, U.FLOAT, 4)):
+        imgs = [U.bitmap(k, 70 + k, 9) if fmt == U.P4 else U.synth(k, 70 + k, 9, d, typ) for k in range(3)]
+        bufs = [torch.from_numpy(np.frombuffer(bytes(off) + p.tobytes(), np.uint8).copy()).to(dev) for p in imgs]
+        stride = max(len(U.encode(p, fmt)) for p in imgs) + 5
+        out = torch.full((3 * stride,), 0xA5, dtype=torch.uint8, device=dev)
+        sizes = torch.zeros((3,), dtype=torch.int64, device=dev)
+        status = torch.full((3,), -9, dtype=torch.int32, device=dev)
+        torch.cuda.synchronize(dev)
+        rc = ctx.pnm_encode_device_batch([b.data_ptr() + off for b in bufs], [p.shape[1] for p in imgs], [9] * 3, d, typ, fmt,
+                                         out.data_ptr(), stride, sizes.data_ptr(), status.data_ptr())
+        assert rc == icx.PNM_OK and list(status.cpu().numpy()) == [0, 0, 0]
+        o = out.cpu().numpy()
+        for i, p in enumerate(imgs):
+            want = U.encode(p, fmt)
+            assert o[i * stride:i * stride + len(want)].tobytes() == want and (o[i * stride + len(want):(i + 1) * stride] == 0xA5).all(), (fmt, i)
+
+
+def test_pnm_fixture_ppm_written_back(ctx):
+    f = FIXTURES["test.ppm"]
+    got = ctx.pnm_decode(f)
+    code, data = ctx.pnm_encode(got[6], icx.PNM_P6)
+    rs = U.parse(f)[1]["rs"]
+    assert code == icx.PNM_OK and data[:15] == b"P6\n499 289\n255\n" and data[15:] == f[rs:rs + 499 * 289 * 3]
+
+
+def test_pnm_written_files_read_by_pil(ctx):
+    from PIL import Image
+    grey, rgb = U.synth(1, 67, 9, 1), U.synth(2, 67, 9, 3)
+    mono = U.bitmap(3, 67, 9)
+    flt = np.random.default_rng(4).standard_normal((9, 67, 1)).astype(np.float32)
+    for px, fmt in ((mono, U.P4), (grey, U.P5), (rgb, U.P6), (flt, U.PF)):
+        code, data = ctx.pnm_encode(px, fmt)
+        assert code == icx.PNM_OK
+        im = Image.open(io.BytesIO(data))
+        im.load()
+        got = np.asarray(im.convert("L") if im.mode == "1" else im)
+        assert (got.reshape(px.shape) == px).all(), fmt
+
+
+def test_pnm_encode_bad_arguments(ctx):
+    z = lambda shape, dt=np.uint8: np.zeros(shape, dt)  # noqa: E731
+    for px, fmt in ((z((4, 4, 3)), U.P5), (z((4, 4, 1)), U.P6), (z((4, 4, 2)), U.P6), (z((4, 4, 1), np.float32), U.P5),
+                    (z((4, 4, 3), np.uint16), U.P4), (z((4, 4, 3)), U.P4), (z((4, 4, 4), np.float32), U.PF),
+                    (z((4, 4, 3)), U.PF), (z((4, 4, 3)), 7), (z((4, 4, 3)), 1), (z((0, 4, 3)), U.P6), (z((4, 0, 3)), U.P6),
+                    (z((2, 2, 2, 3)), U.P6)):
+        assert ctx.pnm_encode(px, fmt) == (icx.PNM_INVALID_ARGUMENT, None), (px.shape, px.dtype, fmt)
+    assert ctx.pnm_encode_device_batch([1], [4], [4], 2, U.UBYTE, U.P6, 1, 100, 1, 1) == icx.PNM_INVALID_ARGUMENT
+    assert ctx.pnm_encode_device_batch([1], [4], [4], 3, U.FLOAT, U.P6, 1, 100, 1, 1) == icx.PNM_INVALID_ARGUMENT
+
+
+def test_pnm_encode_device_batch(ctx):
+    """Three images in one call, a fourth with a bad width, a null source and one whose file does not
+    fit: each gets its own status; TOO_LARGE reports the needed size and writes nothing."""
+    import torch
+    dev = torch.device("cuda", 0)
+    imgs = [U.synth(80 + k, w, h, 3) for k, (w, h) in enumerate([(129, 7), (40, 33), (257, 5)])]
+    big = U.synth(1, 60, 40, 3)
+    srcs = [torch.from_numpy(p.copy()).to(dev) for p in imgs + [imgs[0], imgs[0], big]]
+    ptrs = [s.data_ptr() for s in srcs]
+    ptrs[4] = 0
+    widths = [p.shape[1] for p in imgs] + [0, 129, 60]
+    heights = [p.shape[0] for p in imgs] + [7, 7, 40]
+    stride = max(len(U.encode(p, U.P6)) for p in imgs) + 3
+    assert stride < len(U.encode(big, U.P6))
+    n = len(srcs)
+    out = torch.full((n * stride + 64,), 0xA5, dtype=torch.uint8, device=dev)
+    sizes = torch.full((n,), -1, dtype=torch.int64, device=dev)
+    status = torch.full((n,), -9, dtype=torch.int32, device=dev)
+    torch.cuda.synchronize(dev)  # (the fills above are done before the context's stream writes)
+    rc = ctx.pnm_encode_device_batch(ptrs, widths, heights, 3, U.UBYTE, U.P6, out.data_ptr(), stride, sizes.data_ptr(),
+                                     status.data_ptr())
+    assert rc == icx.PNM_OK
+    out, sizes, status = out.cpu().numpy(), sizes.cpu().numpy(), status.cpu().numpy()
+    assert list(status) == [0, 0, 0, icx.PNM_INVALID_ARGUMENT, icx.PNM_INVALID_ARGUMENT, icx.PNM_TOO_LARGE]
+    assert sizes[3] == 0 and sizes[4] == 0 and sizes[5] == len(U.encode(big, U.P6))
+    for i, px in enumerate(imgs):
+        want = U.encode(px, U.P6)
+        slot = out[i * stride:(i + 1) * stride]
+        assert sizes[i] == len(want) and slot[:len(want)].tobytes() == want, i
+        assert (slot[len(want):] == 0xA5).all(), i
+    assert (out[3 * stride:] == 0xA5).all()
+
+
+# ------------------------------------------------------------------------------------ icx.Image
+def test_image_reads_fixtures_by_magic(tmp_path):
+    for name, data in sorted(FIXTURES.items()):
+        ref = U.decode(data)
+        p = tmp_path / name.upper()
+        p.write_bytes(data)
+        img = icx.Image()
+        img.read(str(p))
+        assert (img.cols(), img.rows(), img.channels(), img.type()) == (ref[1], ref[2], ref[3], ref[4]), name
+        assert img.totalBytes() == ref[6].nbytes and img.data().tobytes() == ref[6].tobytes(), name
+    p = tmp_path / "grey.pnm"  # the magic decides, not the name
+    p.write_bytes(FIXTURES["test.pgm"])
+    img = icx.Image()
+    img.read(str(p))
+    assert img.channels() == 1
+    bad = tmp_path / "bad.ppm"
+    bad.write_bytes(FIXTURES["test.ppm"][:1000])
+    with pytest.raises(RuntimeError, match="Could not read image data"):
+        icx.Image().read(str(bad))
+
+
+@pytest.mark.parametrize("ext", [".pbm", ".pgm", ".ppm", ".pnm", ".pfm"])
+def test_image_round_trip(tmp_path, ext):
+    src = {".pbm": "test.pbm", ".pgm": "test.pgm", ".ppm": "test.ppm", ".pnm": "test.pnm", ".pfm": "test_48rows.pfm"}[ext]
+    a = tmp_path / ("a" + ext)
+    a.write_bytes(FIXTURES[src])
+    img = icx.Image()
+    img.read(str(a))
+    b = tmp_path / ("b" + ext)
+    img.write(str(b))
+    back = icx.Image()
+    back.read(str(b))
+    assert (back.cols(), back.rows(), back.channels(), back.type()) == (img.cols(), img.rows(), img.channels(), img.type())
+    assert back.data().tobytes() == img.data().tobytes()
+    assert b.read_bytes()[:2] == {".pbm": b"P4", ".pgm": b"P5", ".ppm": b"P6", ".pnm": b"P6", ".pfm": b"PF"}[ext]
+
+
+def test_image_write_rules(tmp_path):
+    img = icx.Image()
+    img.load(U.synth(1, 6, 5, 3), 6, 5, 3)
+    with pytest.raises(RuntimeError, match="Cannot write non-float data to .pfm"):
+        img.write(str(tmp_path / "x.pfm"))
+    img.write(str(tmp_path / "x.pgm"))  # d = 3 is not a PGM: nothing thrown, nothing written
+    assert not (tmp_path / "x.pgm").exists() or (tmp_path / "x.pgm").read_bytes() == b""
+    g = icx.Image()
+    g.load(U.synth(2, 6, 5, 1, U.USHORT), 6, 5, 1, icx.Image.USHORT)
+    g.write(str(tmp_path / "g.pnm"))
+    assert (tmp_path / "g.pnm").read_bytes() == U.encode(U.synth(2, 6, 5, 1, U.USHORT), U.P5)
+    f = icx.Image()
+    f.load(U.synth(3, 6, 5, 1, U.FLOAT), 6, 5, 1, icx.Image.FLOAT)
+    f.write(str(tmp_path / "f.pfm"))
+    assert (tmp_path / "f.pfm").read_bytes() == U.encode(U.synth(3, 6, 5, 1, U.FLOAT), U.PF)
