@@ -18,13 +18,15 @@ callers (tests, bench): it binds the C ABI with ctypes and offers
   * ``Context.exr_encode``        -- Image::writeExr's float pixels -> OpenEXR (tinyexr SaveEXR)
   * ``Context.tga_decode`` / ``tga_encode`` -- Image::readTga / writeTga (codecs.cpp:1304-1437), RLE included
   * ``TgaBatch``                  -- device-resident batched .tga decode
+  * ``Context.bmp_decode`` / ``bmp_save_to_memory`` -- Image::readBmp / writeBmp (codecs.cpp:255-375), RLE4/RLE8 and bitfields read
+  * ``BmpBatch``                  -- device-resident batched .bmp decode
   * ``Context.gif_decode``        -- Image::readGif (codecs.cpp:507-542): first frame, wave LZW decode
   * ``GifBatch``                  -- device-resident batched .gif decode
   * ``Context.tiff_decode``       -- Image::readTiff (codecs.cpp:1439-1484): strips / tiles, one wave per chunk
   * ``TiffBatch``                 -- device-resident batched .tif decode
   * ``Context.pnm_decode`` / ``pnm_encode`` -- Image::readPbm / writePbm (codecs.cpp:1034-1167): P1-P6, Pf, PF
   * ``PnmBatch``                  -- device-resident batched Netpbm decode
-  * ``Image``                     -- ImageCodecs::Image (codecs.h:16-103) for .jpg/.jpeg/.png/.hdr/.exr/.tga/.gif/.tif
+  * ``Image``                     -- ImageCodecs::Image (codecs.h:16-103) for .jpg/.jpeg/.png/.hdr/.exr/.tga/.bmp/.gif/.tif
                                      and .pbm/.pgm/.ppm/.pnm/.pfm
 
 There is deliberately no CPU fallback: if libicx.so is missing or no GPU is visible every
@@ -46,7 +48,8 @@ __all__ = ["ICXError", "Context", "Batch", "HdrBatch", "Image", "lib", "build", 
            "PNGR_BAD_DATA", "PNGR_TOO_LARGE", "PNGR_INTERNAL_ERR", "EXR_SUCCESS", "EXR_INVALID_DATA", "Multi", "RECORD_DTYPE", "records_device",
            "checksum64", "multi_shard", "TgaBatch", "tga_probe", "tga_encode_bound", "TGA_OK", "TGA_BAD_HEADER",
            "TGA_UNSUPPORTED", "TGA_NO_IMAGE", "TGA_MALFORMED", "TGA_TRUNCATED", "TGA_TOO_LARGE", "TGA_INVALID_ARGUMENT",
-           "TGA_INTERNAL_ERR", "GifBatch", "gif_probe", "GIF_OK", "GIF_NOT_GIF", "GIF_BAD_HEADER", "GIF_MALFORMED",
+           "TGA_INTERNAL_ERR", "BmpBatch", "bmp_probe", "bmp_encode_bound", "BMP_OK", "BMP_NOT_BMP", "BMP_BAD_HEADER",
+           "BMP_UNSUPPORTED", "BMP_TRUNCATED", "BMP_TOO_LARGE", "BMP_INVALID_ARGUMENT", "BMP_INTERNAL_ERR", "GifBatch", "gif_probe", "GIF_OK", "GIF_NOT_GIF", "GIF_BAD_HEADER", "GIF_MALFORMED",
            "GIF_BAD_DATA", "GIF_TRUNCATED", "GIF_TOO_LARGE", "GIF_INTERNAL_ERR", "TiffBatch", "tiff_probe", "TIFF_OK",
            "TIFF_NOT_TIFF", "TIFF_BAD_HEADER", "TIFF_UNSUPPORTED", "TIFF_MALFORMED", "TIFF_BAD_DATA", "TIFF_TRUNCATED",
            "TIFF_TOO_LARGE", "TIFF_INTERNAL_ERR", "PnmBatch", "pnm_probe", "pnm_encode_bound", "PNM_OK", "PNM_NOT_PNM",
@@ -174,6 +177,16 @@ _SIGS = {
     "icx_tga_save_to_memory": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, C.POINTER(_vp), C.POINTER(_sz)]),
     "icx_tga_save_to_file": (_i32, [_vp, C.c_char_p, _vp, _i32, _i32, _i32, _i32]),
     "icx_tga_encode_device_batch": (_i32, [_vp, _i32, _vp, _vp, _vp, _i32, _i32, _vp, _u64, _vp, _vp, _vp]),
+    "icx_bmp_probe": (_i32, [_vp, _sz, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32)]),
+    "icx_bmp_decode": (_i32, [_vp, _vp, _sz, C.POINTER(_vp), C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32)]),
+    "icx_bmp_batch_create": (_vp, [_vp, _i32, _i32, _i32]),
+    "icx_bmp_batch_destroy": (None, [_vp]),
+    "icx_bmp_batch_decode": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _vp]),
+    "icx_bmp_batch_stage_times": (_i32, [_vp, _vp, _vp, _i32]),
+    "icx_bmp_encode_bound": (_sz, [_i32, _i32, _i32]),
+    "icx_bmp_save_to_memory": (_i32, [_vp, _vp, _i32, _i32, _i32, C.POINTER(_vp), C.POINTER(_sz)]),
+    "icx_bmp_save_to_file": (_i32, [_vp, C.c_char_p, _vp, _i32, _i32, _i32]),
+    "icx_bmp_encode_device_batch": (_i32, [_vp, _i32, _vp, _vp, _vp, _i32, _vp, _u64, _vp, _vp, _vp]),
     "icx_pnm_probe": (_i32, [_vp, _sz] + [C.POINTER(_i32)] * 5),
     "icx_pnm_decode": (_i32, [_vp, _vp, _sz, C.POINTER(_vp)] + [C.POINTER(_i32)] * 5),
     "icx_pnm_batch_create": (_vp, [_vp, _i32, _i32, _i32]),
@@ -207,6 +220,9 @@ EXR_UNSUPPORTED_FORMAT, EXR_INVALID_HEADER, EXR_UNSUPPORTED_FEATURE, EXR_INTERNA
 (TGA_OK, TGA_BAD_HEADER, TGA_UNSUPPORTED, TGA_NO_IMAGE, TGA_MALFORMED, TGA_TRUNCATED, TGA_TOO_LARGE,
  TGA_INVALID_ARGUMENT) = range(8)
 TGA_INTERNAL_ERR = -1
+# icx_bmp_result (include/icx.h): Image::readBmp / writeBmp outcomes
+(BMP_OK, BMP_NOT_BMP, BMP_BAD_HEADER, BMP_UNSUPPORTED, BMP_TRUNCATED, BMP_TOO_LARGE, BMP_INVALID_ARGUMENT) = range(7)
+BMP_INTERNAL_ERR = -1
 # icx_gif_result (include/icx.h): Image::readGif outcomes
 GIF_OK, GIF_NOT_GIF, GIF_BAD_HEADER, GIF_MALFORMED, GIF_BAD_DATA, GIF_TRUNCATED, GIF_TOO_LARGE = range(7)
 GIF_INTERNAL_ERR = -1
@@ -594,6 +610,55 @@ class Context:
             raise ICXError("icx_tga_encode_device_batch: " + _err(self._p))
         return rc
 
+    def bmp_decode(self, data: bytes):
+        """Image::readBmp (codecs.cpp:255-320; contract in include/icx.h) on the GPU -> (code, w, h,
+        channels, uint8 (h, w, channels) or None); code is an icx_bmp_result."""
+        buf = C.create_string_buffer(bytes(data), max(1, len(data)))
+        out = C.c_void_p()
+        w, h, d = C.c_int(), C.c_int(), C.c_int()
+        code = lib().icx_bmp_decode(self._p, buf, len(data), C.byref(out), C.byref(w), C.byref(h), C.byref(d))
+        if code == BMP_INTERNAL_ERR:
+            raise ICXError("icx_bmp_decode: " + _err(self._p))
+        arr = None
+        if out.value:
+            n = w.value * h.value * d.value
+            arr = np.frombuffer(C.string_at(out.value, n), np.uint8).reshape(h.value, w.value, d.value).copy()
+            lib().icx_free(out)
+        return code, w.value, h.value, d.value, arr
+
+    def bmp_save_to_memory(self, px):
+        """Image::writeBmp (codecs.cpp:324-375) on the GPU: uint8 (h, w) or (h, w, d), d in 1, 3, 4,
+        rows top-down -> (code, the file's bytes or None)."""
+        a = np.ascontiguousarray(px, np.uint8)
+        if a.ndim == 2:
+            a = a[:, :, None]
+        if a.ndim != 3:
+            return BMP_INVALID_ARGUMENT, None
+        h, w, d = a.shape
+        out, size = C.c_void_p(), C.c_size_t()
+        code = lib().icx_bmp_save_to_memory(self._p, a.ctypes.data if a.size else None, w, h, d, C.byref(out), C.byref(size))
+        if code == BMP_INTERNAL_ERR:
+            raise ICXError("icx_bmp_save_to_memory: " + _err(self._p))
+        if code != BMP_OK:
+            return code, None
+        data = C.string_at(out.value, size.value)
+        lib().icx_free(out)
+        return code, data
+
+    def bmp_encode_device_batch(self, d_srcs, widths, heights, d: int, d_out: int, out_stride: int, d_sizes: int,
+                                d_status: int, stream=0) -> int:
+        """icx_bmp_encode_device_batch: image i's pixels at device address d_srcs[i], its file to
+        d_out + i*out_stride, size (uint64) and status (int32) to the device arrays -> the call's code."""
+        n = len(d_srcs)
+        sp = (C.c_void_p * max(1, n))(*d_srcs)
+        ws = np.ascontiguousarray(widths, np.int32)
+        hs = np.ascontiguousarray(heights, np.int32)
+        rc = lib().icx_bmp_encode_device_batch(self._p, n, sp, ws.ctypes.data, hs.ctypes.data, d, d_out, out_stride,
+                                               d_sizes, d_status, stream or None)
+        if rc == BMP_INTERNAL_ERR:
+            raise ICXError("icx_bmp_encode_device_batch: " + _err(self._p))
+        return rc
+
     def pnm_decode(self, data: bytes):
         """Image::readPbm (codecs.cpp:1034-1100; contract in include/icx.h) on the GPU -> (code, w, h,
         channels, type, maxval, array (h, w, channels) of uint8 / uint16 / float32 or None); code is an
@@ -956,6 +1021,19 @@ def tga_probe(data: bytes):
     return code, w.value, h.value, d.value
 
 
+def bmp_probe(data: bytes):
+    """Host header walk of the BMP read -> (code, width, height, channels)."""
+    w, h, d = C.c_int(), C.c_int(), C.c_int()
+    buf = C.create_string_buffer(bytes(data), max(1, len(data)))
+    code = lib().icx_bmp_probe(buf, len(data), C.byref(w), C.byref(h), C.byref(d))
+    return code, w.value, h.value, d.value
+
+
+def bmp_encode_bound(width: int, height: int, d: int) -> int:
+    """icx_bmp_encode_bound: the written file's size, or 0 for arguments the write refuses."""
+    return int(lib().icx_bmp_encode_bound(width, height, d))
+
+
 def gif_probe(data: bytes):
     """Host container walk of the GIF read, up to the first image descriptor -> (code, width, height)."""
     w, h = C.c_int(), C.c_int()
@@ -1100,6 +1178,39 @@ class TgaBatch:
         return {names[i].decode(): float(ms[i]) for i in range(k)}
 
 
+class BmpBatch:
+    """Device-resident batched BMP decode (icx_bmp_batch_*): image i is
+    d_data[d_offsets[i] .. + d_sizes[i]); its bytes at d_out + i*out_stride, status in d_status[i],
+    {width, height, channels} in d_dims[3i..]."""
+
+    def __init__(self, ctx: Context, max_images: int, max_width: int, max_height: int):
+        self.ctx = ctx
+        self._p = lib().icx_bmp_batch_create(ctx.ptr, max_images, max_width, max_height)
+        if not self._p:
+            raise ICXError("icx_bmp_batch_create failed: " + _err(ctx.ptr))
+        self.max_images, self.max_width, self.max_height = max_images, max_width, max_height
+
+    def close(self):
+        if getattr(self, "_p", None):
+            lib().icx_bmp_batch_destroy(self._p)
+            self._p = None
+
+    def __del__(self):
+        self.close()
+
+    def decode_device(self, n, d_data, d_offsets, d_sizes, d_out, out_stride, d_status, d_dims, stream=0):
+        rc = lib().icx_bmp_batch_decode(self._p, n, d_data, d_offsets, d_sizes, d_out, out_stride,
+                                        d_status, d_dims, stream or None)
+        if rc != BMP_OK:
+            raise ICXError(f"icx_bmp_batch_decode -> {rc}: {_err(self.ctx.ptr)}")
+
+    def stage_times(self) -> dict:
+        names = (C.c_char_p * 8)()
+        ms = (C.c_float * 8)()
+        k = lib().icx_bmp_batch_stage_times(self._p, names, ms, 8)
+        return {names[i].decode(): float(ms[i]) for i in range(k)}
+
+
 class GifBatch:
     """Device-resident batched GIF decode (icx_gif_batch_*): image i is
     d_data[d_offsets[i] .. + d_sizes[i]); its R,G,B bytes at d_out + i*out_stride, status in
@@ -1207,7 +1318,8 @@ class Image:
     (readHdr: d = 4, type FLOAT, the floats' bytes in pixels_), .exr, .tga (readTga: d = 1, 3 or
     4, type UBYTE), .gif (readGif: the first frame, d = 3, type UBYTE) and .tif/.tiff (readTiff: d = 1,
     3 or 4, type UBYTE), write .jpg/.jpeg, .png, .exr,
-    .tga (uncompressed) and .hdr (flat RGBE; d = 4 only). .pbm/.pgm/.ppm/.pnm/.pfm are read by
+    .tga (uncompressed) and .hdr (flat RGBE; d = 4 only). .bmp is read (readBmp: d = 1, 3 or 4, type
+    UBYTE; raw, RLE4 / RLE8 and bitfields files) and written (writeBmp: 8-bit grey, 24-bit or 32-bit). .pbm/.pgm/.ppm/.pnm/.pfm are read by
     their magic (readPbm: d = 1 or 3; UBYTE, USHORT or FLOAT) and written as P4 / P5 / P6 / P5 or P6
     by d / PF or Pf (writePbm). Other extensions raise ValueError (the reference's
     std::invalid_argument for unknown types)."""
@@ -1241,6 +1353,9 @@ class Image:
             return
         if ext == ".tga":
             self._read_tga(filepath)
+            return
+        if ext == ".bmp":
+            self._read_bmp(filepath)
             return
         if ext == ".gif":
             self._read_gif(filepath)
@@ -1291,6 +1406,17 @@ class Image:
         data = open(filepath, "rb").read()
         code, w, h, d, px = self.context().tga_decode(data)
         if code != TGA_OK:
+            raise RuntimeError("Could not read image data")
+        self.w_, self.h_, self.d_ = w, h, d
+        self.pixels_ = px.reshape(-1).copy()
+        self.type_ = Image.UBYTE
+
+    def _read_bmp(self, filepath: str):
+        """readBmp (codecs.cpp:255-320): d = 1, 3 or 4, type UBYTE, rows top-down. Every failure is
+        Image::read's RuntimeError("Could not read image data") (:85-88: pixels_ stays null)."""
+        data = open(filepath, "rb").read()
+        code, w, h, d, px = self.context().bmp_decode(data)
+        if code != BMP_OK:
             raise RuntimeError("Could not read image data")
         self.w_, self.h_, self.d_ = w, h, d
         self.pixels_ = px.reshape(-1).copy()
@@ -1362,6 +1488,14 @@ class Image:
             except (ICXError, ValueError, AttributeError):
                 return
             if code != TGA_OK:
+                return
+        elif ext == ".bmp":  # writeBmp (codecs.cpp:324-375): nothing is thrown on failure
+            try:
+                px = np.frombuffer(self.pixels_.tobytes(), np.uint8, self.w_ * self.h_ * self.d_)
+                code, out = self.context().bmp_save_to_memory(px.reshape(self.h_, self.w_, self.d_))
+            except (ICXError, ValueError, AttributeError):
+                return
+            if code != BMP_OK:
                 return
         elif ext == ".hdr":  # writeHdr (codecs.cpp:779-818): flat RGBE; d != 4 throws (:781-784)
             if self.d_ != 4:

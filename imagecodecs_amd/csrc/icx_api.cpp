@@ -20,6 +20,7 @@
 #include "icx_mem.h"
 #include "icx_step.h"
 #include "icx_tga_core.h"
+#include "icx_bmp_core.h"
 #include "icx_pnm_core.h"
 #include "icx_hdrw_core.h"
 #include "icx_gif_core.h"
@@ -37,6 +38,7 @@ struct icx_ctx {
     ExrWs* exr = nullptr;  // grow-only EXR read buffers (icx_exr.hip)
     ExrwWs* exrw = nullptr;  // grow-only EXR write buffers (icx_exrw.hip)
     TgawWs* tgaw = nullptr;  // grow-only Targa write buffers (icx_tga.hip)
+    BmpwWs* bmpw = nullptr;  // grow-only BMP write buffers (icx_bmp.hip)
     HdrwWs* hdrw = nullptr;  // grow-only Radiance write buffers (icx_hdrw.hip)
     PnmwWs* pnmw = nullptr;  // grow-only Netpbm write buffers (icx_pnm.hip)
 };
@@ -180,6 +182,7 @@ void icx_destroy(icx_ctx* c) {
     if (c->exr) exr_ws_destroy(c->exr);
     if (c->exrw) exrw_ws_destroy(c->exrw);
     if (c->tgaw) tgaw_ws_destroy(c->tgaw);
+    if (c->bmpw) bmpw_ws_destroy(c->bmpw);
     if (c->hdrw) hdrw_ws_destroy(c->hdrw);
     if (c->pnmw) pnmw_ws_destroy(c->pnmw);
     if (c->stream) (void)hipStreamDestroy(c->stream);
@@ -1539,6 +1542,221 @@ int icx_tga_save_to_file(icx_ctx* ctx, const char* path, const uint8_t* pixels, 
         return ICX_TGA_INTERNAL_ERR;
     }
     return ICX_TGA_OK;
+}
+
+// --------------------------------------------------------- BMP (Image::readBmp / writeBmp)
+struct icx_bmp_batch {
+    icx_ctx* ctx = nullptr;
+    BmpWs ws;
+    Blocks mem;  // the device memory ws points into
+    std::unique_ptr<EventHook> hook;
+};
+
+int icx_bmp_probe(const uint8_t* data, size_t size, int* w, int* h, int* channels) {
+    int ww = 0, hh = 0, dd = 0;
+    const int rc = data ? bmp_probe(data, (int64_t)size, &ww, &hh, &dd, nullptr) : ICX_BMP_NOT_BMP;
+    if (w) *w = rc == ICX_BMP_OK ? ww : 0;
+    if (h) *h = rc == ICX_BMP_OK ? hh : 0;
+    if (channels) *channels = rc == ICX_BMP_OK ? dd : 0;
+    return rc;
+}
+
+// stream_cap: the run-length stream bytes per image the tile tables cover; 0: a workspace for raw
+// files only (no tile tables, no RLE kernels launched).
+static icx_bmp_batch* bmp_batch_new(icx_ctx* ctx, int max_images, int max_w, int max_h, int64_t stream_cap) {
+    // (images are one grid dimension, a stream's tiles another)
+    if (!ctx || max_images <= 0 || max_images > 65535 || max_w <= 0 || max_h <= 0 ||
+        (int64_t)max_w * max_h > ((int64_t)1 << 30) || stream_cap < 0 || stream_cap > ((int64_t)1 << 42)) {
+        if (ctx) ctx->err = "icx_bmp_batch_create: bad arguments";
+        return nullptr;
+    }
+    ICX_HIP(ctx, hipSetDevice(ctx->device), nullptr);
+    auto* b = new icx_bmp_batch();
+    b->ctx = ctx;
+    b->hook = std::make_unique<EventHook>();
+    if (!bmp_ws_alloc(b->ws, b->mem, max_images, max_w, max_h, stream_cap)) {
+        ctx->err = std::string("icx_bmp_batch_create: out of device memory: ") + hipGetErrorString(hipGetLastError());
+        delete b;
+        return nullptr;
+    }
+    return b;
+}
+
+icx_bmp_batch* icx_bmp_batch_create(icx_ctx* ctx, int max_images, int max_w, int max_h) {
+    // (sizes bmp_batch_new refuses have no bound to speak of)
+    const bool sized = max_w > 0 && max_h > 0 && (int64_t)max_w * max_h <= ((int64_t)1 << 30);
+    return bmp_batch_new(ctx, max_images, max_w, max_h, sized ? bmp_stream_bound(max_w, max_h) : 0);
+}
+
+void icx_bmp_batch_destroy(icx_bmp_batch* b) {
+    if (!b) return;
+    (void)hipSetDevice(b->ctx->device);
+    delete b;
+}
+
+int icx_bmp_batch_decode(icx_bmp_batch* b, int n, const uint8_t* d_data, const uint64_t* d_off, const uint64_t* d_size,
+                         uint8_t* d_out, uint64_t out_stride, int32_t* d_status, int32_t* d_dims, void* stream) {
+    if (!b) return ICX_BMP_INTERNAL_ERR;
+    icx_ctx* ctx = b->ctx;
+    if (n < 0 || n > b->ws.max_images) { ctx->err = "icx_bmp_batch_decode: n exceeds batch capacity"; return ICX_BMP_INTERNAL_ERR; }
+    if (n == 0) return ICX_BMP_OK;
+    if (!d_data || !d_off || !d_size || !d_out || !d_status || !d_dims) { ctx->err = "null pointer"; return ICX_BMP_INTERNAL_ERR; }
+    if (out_stride < 4ull * b->ws.max_w * b->ws.max_h) { ctx->err = "icx_bmp_batch_decode: out_stride too small"; return ICX_BMP_INTERNAL_ERR; }
+    ICX_HIP(ctx, hipSetDevice(ctx->device), ICX_BMP_INTERNAL_ERR);
+    hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
+    const RoctxRange range("icx_bmp_batch_decode");
+    b->hook->reset();
+    launch_bmp_decode(b->ws, n, d_data, d_off, d_size, d_out, out_stride, d_status, d_dims, st, b->hook.get());
+    ICX_HIP(ctx, hipGetLastError(), ICX_BMP_INTERNAL_ERR);
+    return ICX_BMP_OK;
+}
+
+int icx_bmp_batch_stage_times(const icx_bmp_batch* b, const char** names, float* ms, int cap) {
+    if (!b) return 0;
+    static const Stage order[5] = {kStParse, kStUnstuff, kStWrite, kStEntropy, kStConvert};
+    static const char* const label[5] = {"parse", "locate", "fill", "expand", "raw"};
+    float acc[kStCount];
+    b->hook->sum(acc);
+    for (int k = 0; k < 5 && k < cap; ++k) {
+        if (names) names[k] = label[k];
+        if (ms) ms[k] = acc[order[k]];
+    }
+    return 5;
+}
+
+int icx_bmp_decode(icx_ctx* ctx, const uint8_t* data, size_t size, uint8_t** out, int* w, int* h, int* channels) {
+    if (out) *out = nullptr;
+    if (w) *w = 0;
+    if (h) *h = 0;
+    if (channels) *channels = 0;
+    if (!ctx || !out) return ICX_BMP_INTERNAL_ERR;
+    int ww = 0, hh = 0, dd = 0;
+    int64_t stream = 0;
+    const int prc = data ? bmp_probe(data, (int64_t)size, &ww, &hh, &dd, &stream) : ICX_BMP_NOT_BMP;
+    if (prc != ICX_BMP_OK) return prc;  // header errors (more than 2^30 pixels among them) need no device work
+    ICX_HIP(ctx, hipSetDevice(ctx->device), ICX_BMP_INTERNAL_ERR);
+    // (declared before the buffers: they are freed first, then the batch)
+    // (the tile tables cover this file's own stream, whatever its length; a raw file needs none,
+    // and the one slot holds just the image's w*h*d bytes)
+    std::unique_ptr<icx_bmp_batch, void (*)(icx_bmp_batch*)> b(bmp_batch_new(ctx, 1, ww, hh, stream), icx_bmp_batch_destroy);
+    if (!b) return ICX_BMP_INTERNAL_ERR;
+    const uint64_t nout = (uint64_t)ww * hh * dd, stride = nout;
+    Buf<uint8_t> d_in, d_out;
+    Buf<uint64_t> d_meta;
+    Buf<int32_t> d_res;
+    int rc = ICX_BMP_INTERNAL_ERR;
+    const uint64_t meta[2] = {0, (uint64_t)size};
+    int32_t res[4] = {0, 0, 0, 0};
+    hipStream_t st = ctx->stream;
+    if (d_in.reserve(size) && d_out.reserve(stride) && d_meta.reserve(16) && d_res.reserve(16) &&
+        hipMemcpyAsync(d_in.p, data, size, hipMemcpyHostToDevice, st) == hipSuccess &&
+        hipMemcpyAsync(d_meta.p, meta, 16, hipMemcpyHostToDevice, st) == hipSuccess &&
+        (launch_bmp_decode(b->ws, 1, d_in.p, d_meta.p, d_meta.p + 1, d_out.p, stride, d_res.p, d_res.p + 1, st, nullptr),
+         hipGetLastError() == hipSuccess) &&
+        hipMemcpyAsync(res, d_res.p, 16, hipMemcpyDeviceToHost, st) == hipSuccess && hipStreamSynchronize(st) == hipSuccess) {
+        rc = res[0];
+        if (rc == ICX_BMP_OK) {
+            uint8_t* hostp = (uint8_t*)std::malloc(nout);
+            if (hostp && hipMemcpy(hostp, d_out.p, nout, hipMemcpyDeviceToHost) == hipSuccess) {
+                *out = hostp;
+                if (w) *w = res[1];
+                if (h) *h = res[2];
+                if (channels) *channels = res[3];
+            } else {
+                std::free(hostp);
+                ctx->err = "icx_bmp_decode: host allocation or copy failed";
+                rc = ICX_BMP_INTERNAL_ERR;
+            }
+        }
+    } else if (ctx->err.empty()) {
+        ctx->err = "icx_bmp_decode: HIP failure";
+    }
+    return rc;
+}
+
+size_t icx_bmp_encode_bound(int width, int height, int d) { return (size_t)bmp_encode_bound(width, height, d); }
+
+int icx_bmp_encode_device_batch(icx_ctx* ctx, int n, const uint8_t* const* d_src, const int32_t* widths,
+                                const int32_t* heights, int d, uint8_t* d_out, uint64_t out_stride,
+                                uint64_t* d_sizes, int32_t* d_status, void* stream) {
+    if (!ctx) return ICX_BMP_INTERNAL_ERR;
+    if (n < 0 || n > 65535 || (d != 1 && d != 3 && d != 4) ||
+        (n > 0 && (!d_src || !widths || !heights || !d_out || !d_sizes || !d_status)))
+        return ICX_BMP_INVALID_ARGUMENT;
+    if (n == 0) return ICX_BMP_OK;
+    ICX_HIP(ctx, hipSetDevice(ctx->device), ICX_BMP_INTERNAL_ERR);
+    const RoctxRange range("icx_bmp_encode_device_batch");
+    std::string err;
+    int rc;
+    try {  // (nothing may cross the C ABI: a host allocation failure is an internal error)
+        if (!ctx->bmpw) ctx->bmpw = bmpw_ws_create();
+        rc = bmp_encode_batch(stream ? (hipStream_t)stream : ctx->stream, *ctx->bmpw, n, d_src, widths, heights, d,
+                              d_out, out_stride, d_sizes, d_status, err);
+    } catch (const std::exception& e) {
+        err = std::string("icx_bmp_encode_device_batch: ") + e.what();
+        rc = -1;
+    }
+    if (rc != 0) {
+        ctx->err = err.empty() ? "icx_bmp_encode_device_batch: HIP failure" : err;
+        return ICX_BMP_INTERNAL_ERR;
+    }
+    return ICX_BMP_OK;
+}
+
+int icx_bmp_save_to_memory(icx_ctx* ctx, const uint8_t* pixels, int width, int height, int d, uint8_t** out,
+                           size_t* size) {
+    if (out) *out = nullptr;
+    if (size) *size = 0;
+    if (!ctx) return ICX_BMP_INTERNAL_ERR;
+    const uint64_t bound = bmp_encode_bound(width, height, d);
+    if (!pixels || !out || !size || bound == 0) return ICX_BMP_INVALID_ARGUMENT;
+    ICX_HIP(ctx, hipSetDevice(ctx->device), ICX_BMP_INTERNAL_ERR);
+    const uint64_t npx = (uint64_t)width * height * d;
+    Buf<uint8_t> d_px, d_file;
+    Buf<uint64_t> d_res;  // the file's size, then its status
+    uint64_t res[2] = {0, 0};
+    hipStream_t st = ctx->stream;
+    if (!(d_px.reserve(npx) && d_file.reserve(bound) && d_res.reserve(16) &&
+          hipMemcpyAsync(d_px.p, pixels, npx, hipMemcpyHostToDevice, st) == hipSuccess)) {
+        ctx->err = std::string("icx_bmp_save_to_memory: ") + hipGetErrorString(hipGetLastError());
+        return ICX_BMP_INTERNAL_ERR;
+    }
+    const uint8_t* src = d_px.p;
+    const int32_t w = width, h = height;
+    const int rc = icx_bmp_encode_device_batch(ctx, 1, &src, &w, &h, d, d_file.p, bound, d_res.p,
+                                               reinterpret_cast<int32_t*>(d_res.p + 1), st);
+    if (rc != ICX_BMP_OK) return rc;
+    ICX_HIP(ctx, hipMemcpy(res, d_res.p, 16, hipMemcpyDeviceToHost), ICX_BMP_INTERNAL_ERR);
+    const int code = (int32_t)(res[1] & 0xFFFFFFFFu);
+    if (code != ICX_BMP_OK) return code;
+    uint8_t* hostp = (uint8_t*)std::malloc(res[0]);
+    if (!hostp || hipMemcpy(hostp, d_file.p, res[0], hipMemcpyDeviceToHost) != hipSuccess) {
+        std::free(hostp);
+        (void)hipGetLastError();
+        ctx->err = "icx_bmp_save_to_memory: host allocation or copy failed";
+        return ICX_BMP_INTERNAL_ERR;
+    }
+    *out = hostp;
+    *size = (size_t)res[0];
+    return ICX_BMP_OK;
+}
+
+int icx_bmp_save_to_file(icx_ctx* ctx, const char* path, const uint8_t* pixels, int width, int height, int d) {
+    if (!ctx) return ICX_BMP_INTERNAL_ERR;
+    if (!path) return ICX_BMP_INVALID_ARGUMENT;
+    uint8_t* mem = nullptr;
+    size_t size = 0;
+    const int rc = icx_bmp_save_to_memory(ctx, pixels, width, height, d, &mem, &size);
+    if (rc != ICX_BMP_OK) return rc;
+    std::FILE* f = std::fopen(path, "wb");
+    const bool ok = f && std::fwrite(mem, 1, size, f) == size;
+    const bool closed = f && std::fclose(f) == 0;
+    std::free(mem);
+    if (!ok || !closed) {
+        ctx->err = std::string("icx_bmp_save_to_file: cannot write ") + path;
+        return ICX_BMP_INTERNAL_ERR;
+    }
+    return ICX_BMP_OK;
 }
 
 // --------------------------------------------------------- Netpbm (Image::readPbm / writePbm)

@@ -385,6 +385,37 @@ int pnm_encode_batch(hipStream_t st, PnmwWs& ws, int n, const uint8_t* const* d_
                      const int32_t* heights, int d, int type, int format, uint8_t* d_out, uint64_t out_stride,
                      uint64_t* d_sizes, int32_t* d_status, std::string& err);
 
+// BMP read and write (icx_bmp.hip; Image::readBmp / writeBmp, codecs.cpp:255-375). Status codes:
+// icx_bmp_core.h kBmp* = include/icx.h ICX_BMP_*.
+struct BmpDesc;
+struct BmpWs {
+    int max_images = 0, max_w = 0, max_h = 0;
+    int64_t tiles_cap = 0;        // stream tiles per image; 0: a workspace for raw files only (an RLE
+                                  // file is TOO_LARGE there, as is a stream longer than the tiles cover)
+    BmpDesc* desc = nullptr;      // [max_images]
+    uint32_t* summary = nullptr;  // [max_images][tiles_cap][kBmpEntries] x 4 words: chain summaries (k_bmp_tiles)
+    int32_t* entry = nullptr;     // [max_images][tiles_cap] slot of the tile's first packet (k_bmp_chain)
+    int32_t* cur_x = nullptr;     // [max_images][tiles_cap] the cursor on entry
+    int32_t* cur_y = nullptr;
+};
+// `stream` (may be null): 0 for a raw file, else 1 + the bytes from bfOffBits to the file's end.
+int bmp_probe(const uint8_t* data, int64_t size, int* w, int* h, int* d, int64_t* stream);
+// The longest stream a batch workspace covers: every pixel its own 2-byte packet, an end-of-line
+// per row and the end-of-bitmap.
+int64_t bmp_stream_bound(int max_w, int max_h);
+// stream_cap: stream bytes per image the tile tables cover; 0: raw files only.
+bool bmp_ws_alloc(BmpWs& ws, Blocks& mem, int max_images, int max_w, int max_h, int64_t stream_cap);
+void launch_bmp_decode(const BmpWs& ws, int n, const uint8_t* d_data, const uint64_t* d_off, const uint64_t* d_size,
+                       uint8_t* d_out, uint64_t out_stride, int32_t* d_status, int32_t* d_dims, hipStream_t st,
+                       StageHook* hook);
+struct BmpwWs;  // grow-only buffers of the write
+BmpwWs* bmpw_ws_create();
+void bmpw_ws_destroy(BmpwWs* w);
+// 0, or -1 for a HIP failure (err says which). Synchronises with `st`.
+int bmp_encode_batch(hipStream_t st, BmpwWs& ws, int n, const uint8_t* const* d_src, const int32_t* widths,
+                     const int32_t* heights, int d, uint8_t* d_out, uint64_t out_stride, uint64_t* d_sizes,
+                     int32_t* d_status, std::string& err);
+
 struct TgawWs;  // grow-only buffers of the write
 TgawWs* tgaw_ws_create();
 void tgaw_ws_destroy(TgawWs* w);

@@ -570,6 +570,118 @@ int icx_tga_encode_device_batch(icx_ctx* ctx, int n, const uint8_t* const* d_src
                                 const int32_t* heights, int d, int rle, uint8_t* d_out, uint64_t out_stride,
                                 uint64_t* d_sizes, int32_t* d_status, void* hip_stream);
 
+/* ---- BMP read (Image::readBmp, codecs.cpp:255-320) -------------------------------------------------
+ * Output: Type::UBYTE, rows top-down whatever the sign of the height, channels R,G,B(,A).
+ * Container: 14 bytes ("BM", bfSize, reserved, bfOffBits), then a DIB header of 12 (core: unsigned
+ * 16-bit width and height, 3-byte palette entries), 40, 52, 56, 64 (OS/2 v2: read as its first 40
+ * bytes, accepted only with compression 0), 108 or 124 bytes. biPlanes is ignored.
+ * Compression: 0 raw (any bit count); 1 RLE8 (8 bits); 2 RLE4 (4 bits); 3 BITFIELDS and
+ * 6 ALPHABITFIELDS (16 and 32 bits): three (3) or four (6) masks follow a 40-byte header, in a 52-byte
+ * header three and in larger ones four masks are inside the header, whichever of the two values
+ * the compression has (a 52-byte header has no alpha mask; with compression 0 the masks are
+ * ignored). Defaults with compression 0: 16 bits is 5-5-5, 32 bits is B,G,R,X with the fourth byte
+ * dropped. A field value v of n <= 8 bits maps to (v * 510 + m) / (2 * m), m = 2^n - 1 (exact
+ * rounding of v * 255 / m); a wider field gives its top 8 bits; a zero colour mask gives 0.
+ * Channels: 4 only for 16- or 32-bit files with a nonzero alpha mask; 1 only for an 8-bit file whose
+ * every palette entry i is (i, i, i) (the index is then the grey value); 3 otherwise. The palette
+ * has biClrUsed entries (0: 2^bits) of B,G,R(,x); an index at or past that number gives zero bytes.
+ * Raw rasters: rows of ((w * bits + 31) / 32) * 4 bytes from bfOffBits, for 1 and 4 bits the most
+ * significant bits first; the file's first row is the bottom row unless the height is negative.
+ * Bytes after the raster are ignored.
+ * Run-length streams (serial as stated; the kernels give the same bytes). The cursor starts at
+ * x = 0, y = 0, the bottom row; the output starts as palette entry 0 everywhere; packets are
+ * 2-byte aligned from bfOffBits:
+ *     n v   (n >= 1)   n pixels of v (RLE4: the high and the low nibble alternate, high first); x += n
+ *     0 0              x = 0, y += 1
+ *     0 1              end of bitmap
+ *     0 2 dx dy        x += dx, y += dy
+ *     0 n p... (n >= 3)  n literal pixels, n bytes (RLE4: (n + 1) / 2), padded to an even length; x += n
+ * The walk ends at the end-of-bitmap packet or where fewer than 2 bytes remain (also OK). A packet
+ * whose payload, pad byte included, is not wholly inside the file is TRUNCATED, and the image then
+ * yields no pixels. Pixels that land at x >= w or y >= h are dropped and the cursor keeps counting:
+ * no saturation, no wrap into the next row.
+ * Deliberate deviations from the reference: the output is R,G,B (the reference copies the file's
+ * B,G,R bytes as they are, and its write stores them as they are); rows are padded to 4 bytes (the reference skips w % 4
+ * bytes, right only where w % 4 is 0 or 2); a negative height gives top-down rows and a positive h
+ * (the reference returns h < 0); every form beyond 24-bit BITMAPINFOHEADER files is read. */
+enum icx_bmp_result {
+    ICX_BMP_OK = 0,
+    ICX_BMP_NOT_BMP = 1,           /* fewer than 18 bytes, or no "BM"                                */
+    ICX_BMP_BAD_HEADER = 2,        /* a header size not listed or past the file; width <= 0, height 0
+                                      or INT_MIN; a bit count not in 1, 4, 8, 16, 24, 32; a wrong bit
+                                      count for compression 1, 2, 3, 6; biClrUsed > 2^bits; masks past
+                                      the file; bfOffBits before the end of the palette or masks     */
+    ICX_BMP_UNSUPPORTED = 3,       /* compression 4, 5 or unknown; a 64-byte header with compression;
+                                      RLE with a negative height; a mask whose set bits are not
+                                      contiguous; masks that overlap                                 */
+    ICX_BMP_TRUNCATED = 4,         /* palette, raster or a run-length packet past the file's end     */
+    ICX_BMP_TOO_LARGE = 5,         /* more than 2^30 pixels; larger than the batch workspace or slot */
+    ICX_BMP_INVALID_ARGUMENT = 6,  /* write: channels not 1, 3, 4; width / height not 1..65535; null */
+    ICX_BMP_INTERNAL_ERR = -1      /* HIP failure (see icx_last_error)                               */
+};
+/* Header only (host): size and channels, or the code the header (for raw files: and the file's
+ * length) gives, checked in the order NOT_BMP, BAD_HEADER, UNSUPPORTED, TOO_LARGE, TRUNCATED. The
+ * packets of an RLE file are walked by the decode. Null data is NOT_BMP. */
+int icx_bmp_probe(const uint8_t* data, size_t size, int* width, int* height, int* channels);
+/* One image, host in / host out: *out receives a malloc()'d width*height*channels byte buffer
+ * (free with icx_free), null unless ICX_BMP_OK. A code the probe gives returns without touching
+ * the GPU. */
+int icx_bmp_decode(icx_ctx* ctx, const uint8_t* data, size_t size, uint8_t** out, int* width, int* height,
+                   int* channels);
+/* Device-resident batch: image i = d_data[d_offsets[i] .. + d_sizes[i]), output bytes at
+ * d_out + i*out_stride (out_stride >= 4*max_width*max_height, any alignment), per-image status in
+ * d_status[i] and {width, height, channels} in d_dims[3i..] (zero for a failed image, whose slot is
+ * unspecified). The workspace covers run-length streams of up to 2*max_width*max_height +
+ * 2*max_height + 2 bytes (every pixel its own packet, an end-of-line per row); a longer stream whose
+ * walk has not ended by then is ICX_BMP_TOO_LARGE (icx_bmp_decode sizes its workspace by the file).
+ * The tile tables for that bound are allocated at creation, whatever the files turn out to be:
+ * 132 x 16 bytes per 4096 stream bytes, about 1.03 x max_width x max_height bytes per image
+ * (1.1 MB at 1024 x 1024, 277 MB for a batch of 256) beside the caller's output slots.
+ * Asynchronous on hip_stream (NULL = the context's stream), no host read-back.
+ * Returns ICX_BMP_OK or ICX_BMP_INTERNAL_ERR. */
+typedef struct icx_bmp_batch icx_bmp_batch;
+icx_bmp_batch* icx_bmp_batch_create(icx_ctx* ctx, int max_images, int max_width, int max_height);
+void icx_bmp_batch_destroy(icx_bmp_batch* b);
+int icx_bmp_batch_decode(icx_bmp_batch* b, int n, const uint8_t* d_data, const uint64_t* d_offsets,
+                         const uint64_t* d_sizes, uint8_t* d_out, uint64_t out_stride, int32_t* d_status,
+                         int32_t* d_dims, void* hip_stream);
+/* Milliseconds per stage of the last icx_bmp_batch_decode ("parse", "locate", "fill", "expand",
+ * "raw"; synchronises). Returns the number of stages. */
+int icx_bmp_batch_stage_times(const icx_bmp_batch* b, const char** names, float* ms, int cap);
+
+/* ---- BMP write (Image::writeBmp, codecs.cpp:324-375) -----------------------------------------------
+ * `pixels`: width*height*d bytes, rows top-down, R,G,B(,A) or one grey byte; d = 1, 3 or 4. The
+ * 14-byte file header carries a correct bfSize (the reference stores the payload size without the
+ * 54 header bytes). Rows are written bottom-up and padded to 4 bytes with zeros; biSizeImage is
+ * set; the pels-per-metre fields are 0, as in the reference.
+ *     d = 3   a 40-byte header, 24 bits, BI_RGB, rows B,G,R
+ *     d = 4   by evident intent (the reference writes 4-byte pixels under a 24-bit header): a
+ *             108-byte V4 header, 32 bits, BI_BITFIELDS, masks 00FF0000, 0000FF00, 000000FF,
+ *             FF000000, colour space LCS_sRGB ("BGRs"), the other V4 fields zero; rows B,G,R,A.
+ *             The read returns such a file with 4 channels
+ *     d = 1   by evident intent: 8 bits with a 256-entry grey palette (biClrUsed 256); the read
+ *             returns it with 1 channel
+ * Any other d, width or height outside 1..65535, or a null pointer -> ICX_BMP_INVALID_ARGUMENT.
+ * Run-length coded files are not written. */
+/* The file's size, bfOffBits + row bytes * height; 0 for arguments the writes refuse. Host only. */
+size_t icx_bmp_encode_bound(int width, int height, int d);
+/* Host pixels in, *out receives the malloc()'d file (free with icx_free). Returns an icx_bmp_result. */
+int icx_bmp_save_to_memory(icx_ctx* ctx, const uint8_t* pixels, int width, int height, int d, uint8_t** out,
+                           size_t* size);
+/* The same file written to `path` (ICX_BMP_INTERNAL_ERR when it cannot be written). */
+int icx_bmp_save_to_file(icx_ctx* ctx, const char* path, const uint8_t* pixels, int width, int height, int d);
+/* n writes with pixels and files resident on the device: image i's pixels at d_src[i] (a host
+ * array of device pointers; widths / heights are host arrays), its file to d_out + i*out_stride
+ * (any alignment), the file's length to d_sizes[i] and an icx_bmp_result to d_status[i] (device
+ * arrays): INVALID_ARGUMENT for a bad size or null source, TOO_LARGE (nothing of the file
+ * written, d_sizes[i] says what it needs) when it is longer than out_stride. d not in 1, 3, 4,
+ * n < 0, n > 65535 (one call's limit: split larger batches) or a null array with n > 0 ->
+ * the call returns ICX_BMP_INVALID_ARGUMENT. Runs on hip_stream (NULL = the context's stream)
+ * and synchronises with it. */
+int icx_bmp_encode_device_batch(icx_ctx* ctx, int n, const uint8_t* const* d_src, const int32_t* widths,
+                                const int32_t* heights, int d, uint8_t* d_out, uint64_t out_stride,
+                                uint64_t* d_sizes, int32_t* d_status, void* hip_stream);
+
 /* ---- Netpbm read (Image::readPbm, codecs.cpp:1034-1100; PNM::load, pnm.h) ---------------------------
  * PBM, PGM, PPM and PFM. The type comes from the magic, never from a file name:
  *     P1, P4   channels 1, UBYTE: bit 0 -> 255, bit 1 -> 0 (codecs.cpp:1078-1079); maxval reads 255

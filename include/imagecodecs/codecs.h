@@ -18,6 +18,13 @@
  *               entries; type 9 included, which the reference leaves as a TODO). channels() is 3
  *               or 4 for colour and 1 for monochrome. A file the read refuses (codes in
  *               include/icx.h) leaves pixels_ null and read() throws "Could not read image data".
+ *               ".bmp" decodes BMP to 8-bit R,G,B(,A) or grey, rows top-down, on the GPU (readBmp,
+ *               codecs.cpp:255-320 -> icx_bmp_decode): core, 40-, 52-, 56-, 64-, 108- and 124-byte
+ *               headers; raw files of 1, 4, 8, 16, 24 and 32 bits; RLE4 and RLE8 streams; BITFIELDS
+ *               and ALPHABITFIELDS masks; bottom-up and top-down rows. channels() is 4 for 16- / 32-bit
+ *               files with an alpha mask, 1 for 8-bit files with a grey-identity palette, else 3.
+ *               A file the read refuses (codes in include/icx.h) leaves pixels_ null and read()
+ *               throws "Could not read image data".
  *               ".gif" decodes the first frame of a GIF onto its logical screen, 8-bit R,G,B, rows
  *               top-down, on the GPU (readGif, codecs.cpp:507-542 -> icx_gif_decode): global and
  *               local palettes, transparency, interlace, frames smaller than or clipped by the
@@ -48,6 +55,13 @@
  *               ".tga" writes the reference's 18 header bytes and the rows top-down, uncompressed
  *               (writeTga, codecs.cpp:1410-1437 -> icx_tga_save_to_file), for d = 1, 3, 4; as in
  *               the reference nothing is thrown (lastWriteOk() tells).
+ *               ".bmp" is not dispatched: write("x.bmp") throws std::invalid_argument like any unknown
+ *               extension, as it did before the BMP codec was added. The public extension
+ *               writeBmp(path) writes the rows bottom-up, padded to 4 bytes (writeBmp,
+ *               codecs.cpp:324-375 -> icx_bmp_save_to_file): d = 3 as 24-bit BI_RGB under a 40-byte
+ *               header, d = 4 as 32-bit BI_BITFIELDS under a 108-byte V4 header, d = 1 as 8 bits
+ *               with a grey palette; nothing is thrown (lastWriteOk() tells). Run-length coded
+ *               files are not written.
  *               ".hdr" writes pixels_ as w*h*4 floats R, G, B, E -- what read(".hdr") returns -- as
  *               the reference's header and four RGBE bytes per pixel (writeHdr, codecs.cpp:779-818
  *               -> icx_hdr_save_to_file, rle = 0); writing what was read reproduces every RGBE
@@ -92,6 +106,20 @@
  * Targa write, by evident intent: the payload is B,G,R(,A) (the reference stores R,G,B, :1429-1434,
  * which every TGA reader, its own included, shows with red and blue exchanged), and d = 1 is
  * written as image type 3 (the reference's type 2 with 8 bits is not a TGA form).
+ * BMP read (contract in include/icx.h): the pixels are R,G,B as every other read here gives them
+ * (the reference copies the file's B,G,R bytes as they are, and its write stores pixels_ as they
+ * are: its own round trip holds, a BMP read and written as .png has red and blue exchanged); rows are padded to a multiple of 4 bytes (the reference
+ * skips w % 4 bytes, codecs.cpp:255-320, right only where w % 4 is 0 or 2: its own test.bmp, 499
+ * wide, happens to need the 3 it skips); a negative height means top-down rows and gives a positive
+ * rows() (the reference returns a negative h); every depth and form beyond 24-bit BITMAPINFOHEADER
+ * files is read where the reference reads the bytes as if they were 24-bit. A file that cannot be
+ * opened or is no BMP leaves pixels_ null, so read() throws "Could not read image data" (the
+ * reference throws "Could not open .bmp file").
+ * BMP write: bfSize is the file's size (the reference stores the payload size without the 54
+ * header bytes, :324-375); by evident intent d = 4 is a 32-bit BI_BITFIELDS file under a V4 header
+ * (the reference writes 4-byte pixels under a 24-bit header) and d = 1 an 8-bit file with a grey
+ * palette (the reference writes 1-byte pixels under a 24-bit header). A file that cannot be opened
+ * leaves lastWriteOk() false (the reference throws "Could not open .bmp file").
  * Radiance write, by evident intent: the mantissas are floor(v * 2^(136 - E)) clamped to 0..255, the
  * exact inverse of the read (the reference calls invConvertComponent with its arguments swapped,
  * :810, and its out-of-range casts are undefined); NaN, negative values and zero write 0, +inf 255,
@@ -348,6 +376,38 @@ class Image {
         type_ = Type::UBYTE;
     }
 
+    // readBmp (codecs.cpp:255-320): d = 1, 3 or 4, Type::UBYTE, rows top-down, decoded on the GPU
+    // (icx_bmp_decode). A failure -- a file that cannot be opened included -- leaves pixels_ null, and
+    // read() throws "Could not read image data" (:85-88).
+    void readBmp(const std::string& path) {
+        std::FILE* f = std::fopen(path.c_str(), "rb");
+        std::vector<uint8_t> buf;
+        if (f) {
+            uint8_t chunk[1 << 16];
+            size_t k;
+            while ((k = std::fread(chunk, 1, sizeof chunk, f)) > 0) buf.insert(buf.end(), chunk, chunk + k);
+            std::fclose(f);
+        }
+        auto& P = detail::icx_process();
+        std::lock_guard<std::mutex> lock(P.mu);
+        uint8_t* out = nullptr;
+        int w = 0, h = 0, d = 0;
+        const int rc = icx_bmp_decode(P.get(), buf.data(), buf.size(), &out, &w, &h, &d);
+        delete[] pixels_;
+        pixels_ = nullptr;
+        w_ = h_ = d_ = 0;
+        if (rc == ICX_BMP_INTERNAL_ERR) throw std::runtime_error(std::string("icx_bmp_decode: ") + icx_last_error(P.get()));
+        if (rc != ICX_BMP_OK) return;
+        const size_t n = (size_t)w * h * d;
+        pixels_ = new unsigned char[n ? n : 1];
+        if (n) std::memcpy(pixels_, out, n);
+        icx_free(out);
+        w_ = w;
+        h_ = h;
+        d_ = d;
+        type_ = Type::UBYTE;
+    }
+
     void writeJpg(const std::string& path) {
         auto& P = detail::icx_process();
         std::lock_guard<std::mutex> lock(P.mu);
@@ -558,6 +618,25 @@ public:
     int totalBytes() const { return w_ * h_ * d_ * byteSize(); }
     Type type() const { return type_; }
     bool lastWriteOk() const { return last_write_ok_; }  // extension: tje's result of the last write()
+    // Extension: writeBmp (codecs.cpp:324-375; private in the reference) called by name, d = 1, 3, 4,
+    // whatever the path's extension. write() does not dispatch ".bmp" to it: that name still reaches
+    // the unknown-extension branch there. Nothing is thrown: a failure -- no usable GPU or a path
+    // that cannot be opened included -- only prints the message; lastWriteOk() tells.
+    void writeBmp(const std::string& path) {
+        auto& P = detail::icx_process();
+        std::lock_guard<std::mutex> lock(P.mu);
+        last_write_ok_ = false;
+        icx_ctx* c = nullptr;
+        try {
+            c = P.get();
+        } catch (const std::runtime_error& e) {
+            std::fprintf(stderr, "%s\n", e.what());
+            return;
+        }
+        const int rc = icx_bmp_save_to_file(c, path.c_str(), pixels_, w_, h_, d_);
+        last_write_ok_ = rc == ICX_BMP_OK;
+        if (!last_write_ok_) std::fprintf(stderr, "icx_bmp_save_to_file -> %d %s\n", rc, icx_last_error(c));
+    }
     // flip (codecs.h:80, codecs.cpp:162-196): reverse the row order in place.
     void flip() {
         if (empty()) return;
@@ -611,6 +690,7 @@ public:
         else if (ext == ".hdr") readHdr(filepath);
         else if (ext == ".exr") readExr(filepath);
         else if (ext == ".tga") readTga(filepath);
+        else if (ext == ".bmp") readBmp(filepath);
         else if (ext == ".gif") readGif(filepath);
         else if (ext == ".tif" || ext == ".tiff") readTiff(filepath);
         else if (detail::is_pnm_ext(ext)) readPnm(filepath);
