@@ -366,21 +366,28 @@ class Context:
         ok = lib().icx_tje_encode_with_func(self._p, sink, None, quality, width, height, comps, buf)
         return b"".join(chunks) if ok == 1 else None
 
+    def _decode_image(self, entry: str, internal: int, data: bytes, k: int, depth=None, dtype=np.uint8):
+        """The one-shot reads' ctypes side: entry(ctx, data, size, &out, k ints) -> (code, the k ints,
+        array (h, w, d) of dtype or None). The ints start with w, h; d is `depth`, or the third int."""
+        buf = C.create_string_buffer(bytes(data), max(1, len(data)))
+        out = C.c_void_p()
+        v = [C.c_int() for _ in range(k)]
+        code = getattr(lib(), entry)(self._p, buf, len(data), C.byref(out), *[C.byref(x) for x in v])
+        if code == internal:
+            raise ICXError(entry + ": " + _err(self._p))
+        v = [x.value for x in v]
+        arr = None
+        if out.value:
+            w, h, d = v[0], v[1], depth or v[2]
+            nbytes = w * h * d * np.dtype(dtype).itemsize
+            arr = np.frombuffer(C.string_at(out.value, nbytes), dtype).reshape(h, w, d).copy()
+            lib().icx_free(out)
+        return (code, *v, arr)
+
     def hdr_decode(self, data: bytes):
         """Image::readHdr (codecs.cpp:706-777) on the GPU -> (code, w, h, rows, float32 (h, w, 4) or
         None). Rows past `rows` (a truncated file) are zero; code is an icx_hdr_result."""
-        buf = C.create_string_buffer(bytes(data), max(1, len(data)))
-        out = C.c_void_p()
-        w, h, rows = C.c_int(), C.c_int(), C.c_int()
-        code = lib().icx_hdr_decode(self._p, buf, len(data), C.byref(out), C.byref(w), C.byref(h), C.byref(rows))
-        if code == HDR_INTERNAL_ERR:
-            raise ICXError("icx_hdr_decode: " + _err(self._p))
-        arr = None
-        if out.value:
-            n = w.value * h.value * 4
-            arr = np.frombuffer(C.string_at(out.value, n * 4), np.float32).reshape(h.value, w.value, 4).copy()
-            lib().icx_free(out)
-        return code, w.value, h.value, rows.value, arr
+        return self._decode_image("icx_hdr_decode", HDR_INTERNAL_ERR, data, 3, 4, np.float32)
 
     def hdr_encode(self, arr, rle: bool = False):
         """Image::writeHdr (codecs.cpp:779-818; contract in include/icx.h) on the GPU: float32 (h, w, 4)
@@ -418,18 +425,7 @@ class Context:
     def png_decode(self, data: bytes):
         """Image::readPng (codecs.cpp:903-1020) on the GPU -> (code, w, h, uint8 (h, w, 4) RGBA or
         None); code is an icx_png_read_result."""
-        buf = C.create_string_buffer(bytes(data), max(1, len(data)))
-        out = C.c_void_p()
-        w, h = C.c_int(), C.c_int()
-        code = lib().icx_png_decode(self._p, buf, len(data), C.byref(out), C.byref(w), C.byref(h))
-        if code == PNGR_INTERNAL_ERR:
-            raise ICXError("icx_png_decode: " + _err(self._p))
-        arr = None
-        if out.value:
-            n = w.value * h.value * 4
-            arr = np.frombuffer(C.string_at(out.value, n), np.uint8).reshape(h.value, w.value, 4).copy()
-            lib().icx_free(out)
-        return code, w.value, h.value, arr
+        return self._decode_image("icx_png_decode", PNGR_INTERNAL_ERR, data, 2, 4)
 
     def exr_decode(self, data: bytes):
         """Image::readExr's LoadEXRFromMemory (tinyexr.h:6645) on the GPU -> (code, w, h, float32
@@ -531,50 +527,17 @@ class Context:
     def tga_decode(self, data: bytes):
         """Image::readTga (codecs.cpp:1304-1407; contract in include/icx.h) on the GPU -> (code, w, h,
         channels, uint8 (h, w, channels) or None); code is an icx_tga_result."""
-        buf = C.create_string_buffer(bytes(data), max(1, len(data)))
-        out = C.c_void_p()
-        w, h, d = C.c_int(), C.c_int(), C.c_int()
-        code = lib().icx_tga_decode(self._p, buf, len(data), C.byref(out), C.byref(w), C.byref(h), C.byref(d))
-        if code == TGA_INTERNAL_ERR:
-            raise ICXError("icx_tga_decode: " + _err(self._p))
-        arr = None
-        if out.value:
-            n = w.value * h.value * d.value
-            arr = np.frombuffer(C.string_at(out.value, n), np.uint8).reshape(h.value, w.value, d.value).copy()
-            lib().icx_free(out)
-        return code, w.value, h.value, d.value, arr
+        return self._decode_image("icx_tga_decode", TGA_INTERNAL_ERR, data, 3)
 
     def gif_decode(self, data: bytes):
         """Image::readGif (codecs.cpp:507-542; contract in include/icx.h) on the GPU -> (code, w, h,
         uint8 (h, w, 3) or None); code is an icx_gif_result."""
-        buf = C.create_string_buffer(bytes(data), max(1, len(data)))
-        out = C.c_void_p()
-        w, h = C.c_int(), C.c_int()
-        code = lib().icx_gif_decode(self._p, buf, len(data), C.byref(out), C.byref(w), C.byref(h))
-        if code == GIF_INTERNAL_ERR:
-            raise ICXError("icx_gif_decode: " + _err(self._p))
-        arr = None
-        if out.value:
-            n = w.value * h.value * 3
-            arr = np.frombuffer(C.string_at(out.value, n), np.uint8).reshape(h.value, w.value, 3).copy()
-            lib().icx_free(out)
-        return code, w.value, h.value, arr
+        return self._decode_image("icx_gif_decode", GIF_INTERNAL_ERR, data, 2, 3)
 
     def tiff_decode(self, data: bytes):
         """Image::readTiff (codecs.cpp:1439-1484; contract in include/icx.h) on the GPU -> (code, w, h,
         d, uint8 (h, w, d) or None); code is an icx_tiff_result."""
-        buf = C.create_string_buffer(bytes(data), max(1, len(data)))
-        out = C.c_void_p()
-        w, h, d = C.c_int(), C.c_int(), C.c_int()
-        code = lib().icx_tiff_decode(self._p, buf, len(data), C.byref(out), C.byref(w), C.byref(h), C.byref(d))
-        if code == TIFF_INTERNAL_ERR:
-            raise ICXError("icx_tiff_decode: " + _err(self._p))
-        arr = None
-        if out.value:
-            n = w.value * h.value * d.value
-            arr = np.frombuffer(C.string_at(out.value, n), np.uint8).reshape(h.value, w.value, d.value).copy()
-            lib().icx_free(out)
-        return code, w.value, h.value, d.value, arr
+        return self._decode_image("icx_tiff_decode", TIFF_INTERNAL_ERR, data, 3)
 
     def tga_encode(self, px, rle: bool = False):
         """Image::writeTga (codecs.cpp:1410-1437) on the GPU: uint8 (h, w) or (h, w, d), d in 1, 3, 4,
@@ -613,18 +576,7 @@ class Context:
     def bmp_decode(self, data: bytes):
         """Image::readBmp (codecs.cpp:255-320; contract in include/icx.h) on the GPU -> (code, w, h,
         channels, uint8 (h, w, channels) or None); code is an icx_bmp_result."""
-        buf = C.create_string_buffer(bytes(data), max(1, len(data)))
-        out = C.c_void_p()
-        w, h, d = C.c_int(), C.c_int(), C.c_int()
-        code = lib().icx_bmp_decode(self._p, buf, len(data), C.byref(out), C.byref(w), C.byref(h), C.byref(d))
-        if code == BMP_INTERNAL_ERR:
-            raise ICXError("icx_bmp_decode: " + _err(self._p))
-        arr = None
-        if out.value:
-            n = w.value * h.value * d.value
-            arr = np.frombuffer(C.string_at(out.value, n), np.uint8).reshape(h.value, w.value, d.value).copy()
-            lib().icx_free(out)
-        return code, w.value, h.value, d.value, arr
+        return self._decode_image("icx_bmp_decode", BMP_INTERNAL_ERR, data, 3)
 
     def bmp_save_to_memory(self, px):
         """Image::writeBmp (codecs.cpp:324-375) on the GPU: uint8 (h, w) or (h, w, d), d in 1, 3, 4,
@@ -1068,40 +1020,59 @@ def pnm_encode_bound(width: int, height: int, d: int, type_: int, fmt: int) -> i
     return int(lib().icx_pnm_encode_bound(width, height, d, type_, fmt))
 
 
-class PnmBatch:
-    """Device-resident batched Netpbm decode (icx_pnm_batch_*): image i is
-    d_data[d_offsets[i] .. + d_sizes[i]); its elements at d_out + i*out_stride (d_out 16-byte aligned,
-    out_stride a multiple of 16), status in d_status[i], {width, height, channels, type, maxval} in
-    d_dims[5i..]."""
+class _ReadBatch:
+    """What the read batches share (icx_<fmt>_batch_*); a subclass names its entries and codes."""
+
+    _prefix = ""    # the entries are <_prefix>_create, _destroy, _decode, _stage_times
+    _ok = 0
+    _returned = ()  # codes besides _ok that _decode returns instead of raising
 
     def __init__(self, ctx: Context, max_images: int, max_width: int, max_height: int):
         self.ctx = ctx
-        self._p = lib().icx_pnm_batch_create(ctx.ptr, max_images, max_width, max_height)
+        self._p = self._entry("create")(ctx.ptr, max_images, max_width, max_height)
         if not self._p:
-            raise ICXError("icx_pnm_batch_create failed: " + _err(ctx.ptr))
+            raise ICXError(f"{self._prefix}_create failed: " + _err(ctx.ptr))
         self.max_images, self.max_width, self.max_height = max_images, max_width, max_height
+
+    def _entry(self, name: str):
+        return getattr(lib(), f"{self._prefix}_{name}")
 
     def close(self):
         if getattr(self, "_p", None):
-            lib().icx_pnm_batch_destroy(self._p)
+            self._entry("destroy")(self._p)
             self._p = None
 
     def __del__(self):
         self.close()
 
-    def decode_device(self, n, d_data, d_offsets, d_sizes, d_out, out_stride, d_status, d_dims, stream=0) -> int:
-        """-> PNM_OK, or PNM_INVALID_ARGUMENT for a d_out or out_stride that is not 16-byte aligned."""
-        rc = lib().icx_pnm_batch_decode(self._p, n, d_data, d_offsets, d_sizes, d_out, out_stride,
-                                        d_status, d_dims, stream or None)
-        if rc not in (PNM_OK, PNM_INVALID_ARGUMENT):
-            raise ICXError(f"icx_pnm_batch_decode -> {rc}: {_err(self.ctx.ptr)}")
+    def _decode(self, n, d_data, d_offsets, d_sizes, d_out, out_stride, d_status, d_dims, stream=0) -> int:
+        rc = self._entry("decode")(self._p, n, d_data, d_offsets, d_sizes, d_out, out_stride, d_status, d_dims,
+                                   stream or None)
+        if rc != self._ok and rc not in self._returned:
+            raise ICXError(f"{self._prefix}_decode -> {rc}: {_err(self.ctx.ptr)}")
         return rc
+
+    def decode_device(self, n, d_data, d_offsets, d_sizes, d_out, out_stride, d_status, d_dims, stream=0):
+        self._decode(n, d_data, d_offsets, d_sizes, d_out, out_stride, d_status, d_dims, stream)
 
     def stage_times(self) -> dict:
         names = (C.c_char_p * 8)()
         ms = (C.c_float * 8)()
-        k = lib().icx_pnm_batch_stage_times(self._p, names, ms, 8)
+        k = self._entry("stage_times")(self._p, names, ms, 8)
         return {names[i].decode(): float(ms[i]) for i in range(k)}
+
+
+class PnmBatch(_ReadBatch):
+    """Device-resident batched Netpbm decode (icx_pnm_batch_*): image i is
+    d_data[d_offsets[i] .. + d_sizes[i]); its elements at d_out + i*out_stride (d_out 16-byte aligned,
+    out_stride a multiple of 16), status in d_status[i], {width, height, channels, type, maxval} in
+    d_dims[5i..]."""
+
+    _prefix, _ok, _returned = "icx_pnm_batch", PNM_OK, (PNM_INVALID_ARGUMENT,)
+
+    def decode_device(self, n, d_data, d_offsets, d_sizes, d_out, out_stride, d_status, d_dims, stream=0) -> int:
+        """-> PNM_OK, or PNM_INVALID_ARGUMENT for a d_out or out_stride that is not 16-byte aligned."""
+        return self._decode(n, d_data, d_offsets, d_sizes, d_out, out_stride, d_status, d_dims, stream)
 
 
 def png_probe(data: bytes):
@@ -1112,202 +1083,52 @@ def png_probe(data: bytes):
     return code, w.value, h.value
 
 
-class PngBatch:
+class PngBatch(_ReadBatch):
     """Device-resident batched PNG decode (icx_png_batch_*): image i is
     d_data[d_offsets[i] .. + d_sizes[i]); RGBA8 at d_out + i*out_stride bytes, status in
     d_status[i], {width, height, 4} in d_dims[3i..]."""
 
-    def __init__(self, ctx: Context, max_images: int, max_width: int, max_height: int):
-        self.ctx = ctx
-        self._p = lib().icx_png_batch_create(ctx.ptr, max_images, max_width, max_height)
-        if not self._p:
-            raise ICXError("icx_png_batch_create failed: " + _err(ctx.ptr))
-        self.max_images, self.max_width, self.max_height = max_images, max_width, max_height
-
-    def close(self):
-        if getattr(self, "_p", None):
-            lib().icx_png_batch_destroy(self._p)
-            self._p = None
-
-    def __del__(self):
-        self.close()
-
-    def decode_device(self, n, d_data, d_offsets, d_sizes, d_out, out_stride, d_status, d_dims, stream=0):
-        rc = lib().icx_png_batch_decode(self._p, n, d_data, d_offsets, d_sizes, d_out, out_stride,
-                                        d_status, d_dims, stream or None)
-        if rc != PNGR_OK:
-            raise ICXError(f"icx_png_batch_decode -> {rc}: {_err(self.ctx.ptr)}")
-
-    def stage_times(self) -> dict:
-        names = (C.c_char_p * 8)()
-        ms = (C.c_float * 8)()
-        k = lib().icx_png_batch_stage_times(self._p, names, ms, 8)
-        return {names[i].decode(): float(ms[i]) for i in range(k)}
+    _prefix, _ok = "icx_png_batch", PNGR_OK
 
 
-class TgaBatch:
+class TgaBatch(_ReadBatch):
     """Device-resident batched Targa decode (icx_tga_batch_*): image i is
     d_data[d_offsets[i] .. + d_sizes[i]); its bytes at d_out + i*out_stride, status in d_status[i],
     {width, height, channels} in d_dims[3i..]."""
 
-    def __init__(self, ctx: Context, max_images: int, max_width: int, max_height: int):
-        self.ctx = ctx
-        self._p = lib().icx_tga_batch_create(ctx.ptr, max_images, max_width, max_height)
-        if not self._p:
-            raise ICXError("icx_tga_batch_create failed: " + _err(ctx.ptr))
-        self.max_images, self.max_width, self.max_height = max_images, max_width, max_height
-
-    def close(self):
-        if getattr(self, "_p", None):
-            lib().icx_tga_batch_destroy(self._p)
-            self._p = None
-
-    def __del__(self):
-        self.close()
-
-    def decode_device(self, n, d_data, d_offsets, d_sizes, d_out, out_stride, d_status, d_dims, stream=0):
-        rc = lib().icx_tga_batch_decode(self._p, n, d_data, d_offsets, d_sizes, d_out, out_stride,
-                                        d_status, d_dims, stream or None)
-        if rc != TGA_OK:
-            raise ICXError(f"icx_tga_batch_decode -> {rc}: {_err(self.ctx.ptr)}")
-
-    def stage_times(self) -> dict:
-        names = (C.c_char_p * 8)()
-        ms = (C.c_float * 8)()
-        k = lib().icx_tga_batch_stage_times(self._p, names, ms, 8)
-        return {names[i].decode(): float(ms[i]) for i in range(k)}
+    _prefix, _ok = "icx_tga_batch", TGA_OK
 
 
-class BmpBatch:
+class BmpBatch(_ReadBatch):
     """Device-resident batched BMP decode (icx_bmp_batch_*): image i is
     d_data[d_offsets[i] .. + d_sizes[i]); its bytes at d_out + i*out_stride, status in d_status[i],
     {width, height, channels} in d_dims[3i..]."""
 
-    def __init__(self, ctx: Context, max_images: int, max_width: int, max_height: int):
-        self.ctx = ctx
-        self._p = lib().icx_bmp_batch_create(ctx.ptr, max_images, max_width, max_height)
-        if not self._p:
-            raise ICXError("icx_bmp_batch_create failed: " + _err(ctx.ptr))
-        self.max_images, self.max_width, self.max_height = max_images, max_width, max_height
-
-    def close(self):
-        if getattr(self, "_p", None):
-            lib().icx_bmp_batch_destroy(self._p)
-            self._p = None
-
-    def __del__(self):
-        self.close()
-
-    def decode_device(self, n, d_data, d_offsets, d_sizes, d_out, out_stride, d_status, d_dims, stream=0):
-        rc = lib().icx_bmp_batch_decode(self._p, n, d_data, d_offsets, d_sizes, d_out, out_stride,
-                                        d_status, d_dims, stream or None)
-        if rc != BMP_OK:
-            raise ICXError(f"icx_bmp_batch_decode -> {rc}: {_err(self.ctx.ptr)}")
-
-    def stage_times(self) -> dict:
-        names = (C.c_char_p * 8)()
-        ms = (C.c_float * 8)()
-        k = lib().icx_bmp_batch_stage_times(self._p, names, ms, 8)
-        return {names[i].decode(): float(ms[i]) for i in range(k)}
+    _prefix, _ok = "icx_bmp_batch", BMP_OK
 
 
-class GifBatch:
+class GifBatch(_ReadBatch):
     """Device-resident batched GIF decode (icx_gif_batch_*): image i is
     d_data[d_offsets[i] .. + d_sizes[i]); its R,G,B bytes at d_out + i*out_stride, status in
     d_status[i], {width, height, 3} in d_dims[3i..]."""
 
-    def __init__(self, ctx: Context, max_images: int, max_width: int, max_height: int):
-        self.ctx = ctx
-        self._p = lib().icx_gif_batch_create(ctx.ptr, max_images, max_width, max_height)
-        if not self._p:
-            raise ICXError("icx_gif_batch_create failed: " + _err(ctx.ptr))
-        self.max_images, self.max_width, self.max_height = max_images, max_width, max_height
-
-    def close(self):
-        if getattr(self, "_p", None):
-            lib().icx_gif_batch_destroy(self._p)
-            self._p = None
-
-    def __del__(self):
-        self.close()
-
-    def decode_device(self, n, d_data, d_offsets, d_sizes, d_out, out_stride, d_status, d_dims, stream=0):
-        rc = lib().icx_gif_batch_decode(self._p, n, d_data, d_offsets, d_sizes, d_out, out_stride,
-                                        d_status, d_dims, stream or None)
-        if rc != GIF_OK:
-            raise ICXError(f"icx_gif_batch_decode -> {rc}: {_err(self.ctx.ptr)}")
-
-    def stage_times(self) -> dict:
-        names = (C.c_char_p * 8)()
-        ms = (C.c_float * 8)()
-        k = lib().icx_gif_batch_stage_times(self._p, names, ms, 8)
-        return {names[i].decode(): float(ms[i]) for i in range(k)}
+    _prefix, _ok = "icx_gif_batch", GIF_OK
 
 
-class TiffBatch:
+class TiffBatch(_ReadBatch):
     """Device-resident batched TIFF decode (icx_tiff_batch_*): image i is
     d_data[d_offsets[i] .. + d_sizes[i]); its bytes at d_out + i*out_stride
     (out_stride >= 4 * max_width * max_height), status in
     d_status[i], {width, height, channels} in d_dims[3i..]."""
 
-    def __init__(self, ctx: Context, max_images: int, max_width: int, max_height: int):
-        self.ctx = ctx
-        self._p = lib().icx_tiff_batch_create(ctx.ptr, max_images, max_width, max_height)
-        if not self._p:
-            raise ICXError("icx_tiff_batch_create failed: " + _err(ctx.ptr))
-        self.max_images, self.max_width, self.max_height = max_images, max_width, max_height
-
-    def close(self):
-        if getattr(self, "_p", None):
-            lib().icx_tiff_batch_destroy(self._p)
-            self._p = None
-
-    def __del__(self):
-        self.close()
-
-    def decode_device(self, n, d_data, d_offsets, d_sizes, d_out, out_stride, d_status, d_dims, stream=0):
-        rc = lib().icx_tiff_batch_decode(self._p, n, d_data, d_offsets, d_sizes, d_out, out_stride,
-                                        d_status, d_dims, stream or None)
-        if rc != TIFF_OK:
-            raise ICXError(f"icx_tiff_batch_decode -> {rc}: {_err(self.ctx.ptr)}")
-
-    def stage_times(self) -> dict:
-        names = (C.c_char_p * 8)()
-        ms = (C.c_float * 8)()
-        k = lib().icx_tiff_batch_stage_times(self._p, names, ms, 8)
-        return {names[i].decode(): float(ms[i]) for i in range(k)}
+    _prefix, _ok = "icx_tiff_batch", TIFF_OK
 
 
-class HdrBatch:
+class HdrBatch(_ReadBatch):
     """Device-resident batched Radiance .hdr decode (icx_hdr_batch_*): image i is
     d_data[d_offsets[i] .. + d_sizes[i]); 4 floats per pixel at d_out + i*out_stride floats."""
 
-    def __init__(self, ctx: Context, max_images: int, max_width: int, max_height: int):
-        self.ctx = ctx
-        self._p = lib().icx_hdr_batch_create(ctx.ptr, max_images, max_width, max_height)
-        if not self._p:
-            raise ICXError("icx_hdr_batch_create failed: " + _err(ctx.ptr))
-        self.max_images, self.max_width, self.max_height = max_images, max_width, max_height
-
-    def close(self):
-        if getattr(self, "_p", None):
-            lib().icx_hdr_batch_destroy(self._p)
-            self._p = None
-
-    def __del__(self):
-        self.close()
-
-    def decode_device(self, n, d_data, d_offsets, d_sizes, d_out, out_stride, d_status, d_dims, stream=0):
-        rc = lib().icx_hdr_batch_decode(self._p, n, d_data, d_offsets, d_sizes, d_out, out_stride,
-                                        d_status, d_dims, stream or None)
-        if rc != HDR_OK:
-            raise ICXError(f"icx_hdr_batch_decode -> {rc}: {_err(self.ctx.ptr)}")
-
-    def stage_times(self) -> dict:
-        names = (C.c_char_p * 8)()
-        ms = (C.c_float * 8)()
-        k = lib().icx_hdr_batch_stage_times(self._p, names, ms, 8)
-        return {names[i].decode(): float(ms[i]) for i in range(k)}
+    _prefix, _ok = "icx_hdr_batch", HDR_OK
 
 
 class Image:
@@ -1388,61 +1209,40 @@ class Image:
         self.pixels_ = px.reshape(-1).view(np.uint8).copy()
         self.type_ = Image.FLOAT
 
+    def _read_bytes(self, decode, ok: int, filepath: str, d=None):
+        """The byte readers' body: decode(file) -> (code, w, h[, d], pixels); d where the format fixes it."""
+        code, w, h, *dd, px = decode(open(filepath, "rb").read())
+        if code != ok:
+            raise RuntimeError("Could not read image data")
+        self.w_, self.h_, self.d_ = w, h, d or dd[0]
+        self.pixels_ = px.reshape(-1).copy()
+        self.type_ = Image.UBYTE
+
     def _read_png(self, filepath: str):
         """readPng (codecs.cpp:903-1020): d = 4, type UBYTE, 8-bit RGBA rows top-down. Every
         failure is Image::read's RuntimeError("Could not read image data") (:85-88: readPng leaves
         pixels_ null)."""
-        data = open(filepath, "rb").read()
-        code, w, h, px = self.context().png_decode(data)
-        if code != PNGR_OK:
-            raise RuntimeError("Could not read image data")
-        self.w_, self.h_, self.d_ = w, h, 4
-        self.pixels_ = px.reshape(-1).copy()
-        self.type_ = Image.UBYTE
+        self._read_bytes(self.context().png_decode, PNGR_OK, filepath, 4)
 
     def _read_tga(self, filepath: str):
         """readTga (codecs.cpp:1304-1407): d = 1, 3 or 4, type UBYTE, rows top-down. Every failure is
         Image::read's RuntimeError("Could not read image data") (:85-88: pixels_ stays null)."""
-        data = open(filepath, "rb").read()
-        code, w, h, d, px = self.context().tga_decode(data)
-        if code != TGA_OK:
-            raise RuntimeError("Could not read image data")
-        self.w_, self.h_, self.d_ = w, h, d
-        self.pixels_ = px.reshape(-1).copy()
-        self.type_ = Image.UBYTE
+        self._read_bytes(self.context().tga_decode, TGA_OK, filepath)
 
     def _read_bmp(self, filepath: str):
         """readBmp (codecs.cpp:255-320): d = 1, 3 or 4, type UBYTE, rows top-down. Every failure is
         Image::read's RuntimeError("Could not read image data") (:85-88: pixels_ stays null)."""
-        data = open(filepath, "rb").read()
-        code, w, h, d, px = self.context().bmp_decode(data)
-        if code != BMP_OK:
-            raise RuntimeError("Could not read image data")
-        self.w_, self.h_, self.d_ = w, h, d
-        self.pixels_ = px.reshape(-1).copy()
-        self.type_ = Image.UBYTE
+        self._read_bytes(self.context().bmp_decode, BMP_OK, filepath)
 
     def _read_gif(self, filepath: str):
         """readGif (codecs.cpp:507-542): the first frame on the logical screen, d = 3, type UBYTE,
         rows top-down. Every failure is Image::read's RuntimeError("Could not read image data")."""
-        data = open(filepath, "rb").read()
-        code, w, h, px = self.context().gif_decode(data)
-        if code != GIF_OK:
-            raise RuntimeError("Could not read image data")
-        self.w_, self.h_, self.d_ = w, h, 3
-        self.pixels_ = px.reshape(-1).copy()
-        self.type_ = Image.UBYTE
+        self._read_bytes(self.context().gif_decode, GIF_OK, filepath, 3)
 
     def _read_tiff(self, filepath: str):
         """readTiff (codecs.cpp:1439-1484): the first IFD, d = 1, 3 or 4, type UBYTE, rows top-down.
         Every failure is Image::read's RuntimeError("Could not read image data")."""
-        data = open(filepath, "rb").read()
-        code, w, h, d, px = self.context().tiff_decode(data)
-        if code != TIFF_OK:
-            raise RuntimeError("Could not read image data")
-        self.w_, self.h_, self.d_ = w, h, d
-        self.pixels_ = px.reshape(-1).copy()
-        self.type_ = Image.UBYTE
+        self._read_bytes(self.context().tiff_decode, TIFF_OK, filepath)
 
     def _read_pnm(self, filepath: str):
         """readPbm (codecs.cpp:1034-1100): the type is the magic's, whatever the name; d = 1 or 3, type

@@ -11,6 +11,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <exception>
+#include <initializer_list>
 #include <memory>
 #include <string>
 #include <vector>
@@ -142,6 +143,367 @@ struct EventHook : StageHook {
         for (auto e : pool) (void)hipEventDestroy(e);
     }
 };
+
+// ------------------------------------------- the host layer the read batches share
+// Every read format but JPEG and EXR has the same host side: a batch {ctx, ws, mem, hook}, its
+// create / destroy / decode / stage_times, and a one-shot decode through a batch of one. A ReadFmt
+// says what differs: the workspace, the codes, the entry names in messages and roctx ranges, the
+// stages, the limits create refuses, the workspace allocation, the launcher and what decode asks
+// of d_out and out_stride. A new format writes one such struct and entries of a few lines.
+namespace {  // (this file's own types: none of them is exported)
+
+template <class F>
+struct ReadBatch {
+    icx_ctx* ctx = nullptr;
+    typename F::Ws ws;
+    Blocks mem;  // the device memory ws points into
+    std::unique_ptr<EventHook> hook;
+};
+
+struct ReadFmtDefaults {
+    static constexpr int kStridePx = 4;  // out_stride is at least this x max_w x max_h (0: no floor)
+    static int out_refused(icx_ctx*, const void*, uint64_t) { return 0; }  // d_out / out_stride alignment
+};
+
+struct HdrFmt : ReadFmtDefaults {
+    using Ws = HdrWs;
+    using Px = float;
+    using Batch = icx_hdr_batch;
+    static constexpr int kOk = ICX_HDR_OK, kInternal = ICX_HDR_INTERNAL_ERR;
+    static constexpr const char *kCreate = "icx_hdr_batch_create", *kDecode = "icx_hdr_batch_decode", *kOne = "icx_hdr_decode";
+    static constexpr Stage kOrder[] = {kStParse, kStUnstuff, kStEntropy, kStConvert};
+    static constexpr const char* kLabel[] = {"parse", "locate", "unpack", "convert"};
+    static bool over_limit(int, int, int) { return false; }
+    static bool alloc(Ws& ws, Blocks& mem, icx_ctx*, int n, int w, int h) { return hdr_ws_alloc(ws, mem, n, w, h); }
+    static constexpr auto launch = &launch_hdr_decode;
+};
+
+struct PngFmt : ReadFmtDefaults {
+    using Ws = PngdWs;
+    using Px = uint8_t;
+    using Batch = icx_png_batch;
+    static constexpr int kOk = ICX_PNGR_OK, kInternal = ICX_PNGR_INTERNAL_ERR;
+    static constexpr const char *kCreate = "icx_png_batch_create", *kDecode = "icx_png_batch_decode", *kOne = "icx_png_decode";
+    static constexpr Stage kOrder[] = {kStParse, kStUnstuff, kStEntropy, kStIdct, kStConvert};
+    static constexpr const char* kLabel[] = {"parse", "gather", "inflate", "unfilter", "expand"};
+    // (images are one grid dimension; no image the walk accepts is larger than the pixel limit)
+    static bool over_limit(int n, int w, int h) { return n > 65535 || w > 0x1000000 || h > 0x1000000; }
+    static bool alloc(Ws& ws, Blocks& mem, icx_ctx*, int n, int w, int h) { return pngd_ws_alloc(ws, mem, n, w, h); }
+    static constexpr auto launch = &launch_pngd_decode;
+    static int out_refused(icx_ctx* ctx, const void* d_out, uint64_t out_stride) {
+        if (!(reinterpret_cast<uintptr_t>(d_out) & 3) && !(out_stride & 3)) return 0;
+        ctx->err = "icx_png_batch_decode: d_out and out_stride must be multiples of 4";
+        return ICX_PNGR_INTERNAL_ERR;
+    }
+};
+
+struct TgaFmt : ReadFmtDefaults {
+    using Ws = TgaWs;
+    using Px = uint8_t;
+    using Batch = icx_tga_batch;
+    static constexpr int kOk = ICX_TGA_OK, kInternal = ICX_TGA_INTERNAL_ERR;
+    static constexpr const char *kCreate = "icx_tga_batch_create", *kDecode = "icx_tga_batch_decode", *kOne = "icx_tga_decode";
+    static constexpr Stage kOrder[] = {kStParse, kStUnstuff, kStEntropy, kStConvert};
+    static constexpr const char* kLabel[] = {"parse", "locate", "expand", "raw"};
+    // (images are one grid dimension; pixel indices are 32-bit in the tile tables)
+    static bool over_limit(int n, int w, int h, bool) {
+        return n > 65535 || w > 65535 || h > 65535 || (int64_t)w * h > ((int64_t)1 << 30);
+    }
+    // rle false: a workspace for raw files only (no tile tables, no RLE kernels launched).
+    static bool alloc(Ws& ws, Blocks& mem, icx_ctx*, int n, int w, int h, bool rle) { return tga_ws_alloc(ws, mem, n, w, h, rle); }
+    static constexpr auto launch = &launch_tga_decode;
+};
+
+struct BmpFmt : ReadFmtDefaults {
+    using Ws = BmpWs;
+    using Px = uint8_t;
+    using Batch = icx_bmp_batch;
+    static constexpr int kOk = ICX_BMP_OK, kInternal = ICX_BMP_INTERNAL_ERR;
+    static constexpr const char *kCreate = "icx_bmp_batch_create", *kDecode = "icx_bmp_batch_decode", *kOne = "icx_bmp_decode";
+    static constexpr Stage kOrder[] = {kStParse, kStUnstuff, kStWrite, kStEntropy, kStConvert};
+    static constexpr const char* kLabel[] = {"parse", "locate", "fill", "expand", "raw"};
+    // (images are one grid dimension, a stream's tiles another)
+    static bool over_limit(int n, int w, int h, int64_t stream_cap) {
+        return n > 65535 || (int64_t)w * h > ((int64_t)1 << 30) || stream_cap < 0 || stream_cap > ((int64_t)1 << 42);
+    }
+    // stream_cap: the run-length stream bytes per image the tile tables cover; 0: a workspace for
+    // raw files only (no tile tables, no RLE kernels launched).
+    static bool alloc(Ws& ws, Blocks& mem, icx_ctx*, int n, int w, int h, int64_t stream_cap) {
+        return bmp_ws_alloc(ws, mem, n, w, h, stream_cap);
+    }
+    static constexpr auto launch = &launch_bmp_decode;
+};
+
+struct PnmFmt : ReadFmtDefaults {
+    using Ws = PnmWs;
+    using Px = uint8_t;
+    using Batch = icx_pnm_batch;
+    static constexpr int kOk = ICX_PNM_OK, kInternal = ICX_PNM_INTERNAL_ERR;
+    static constexpr const char *kCreate = "icx_pnm_batch_create", *kDecode = "icx_pnm_batch_decode", *kOne = "icx_pnm_decode";
+    static constexpr Stage kOrder[] = {kStParse, kStUnstuff, kStEntropy, kStConvert};
+    static constexpr const char* kLabel[] = {"parse", "locate", "text", "stream"};
+    // (images are one grid dimension)
+    static bool over_limit(int n, int w, int h, int64_t) { return n > 65535 || (int64_t)w * h > ((int64_t)1 << 30); }
+    // tiles_cap: tiles of raster text per image (0: a workspace for binary files only).
+    static bool alloc(Ws& ws, Blocks& mem, icx_ctx*, int n, int w, int h, int64_t tiles_cap) {
+        return pnm_ws_alloc(ws, mem, n, w, h, tiles_cap);
+    }
+    static constexpr auto launch = &launch_pnm_decode;
+    static constexpr int kStridePx = 0;  // (a slot holds what the caller sized it for: TOO_LARGE per image)
+    static int out_refused(icx_ctx*, const void* d_out, uint64_t out_stride) {  // (sets no message)
+        return (reinterpret_cast<uintptr_t>(d_out) & 15) || (out_stride & 15) ? ICX_PNM_INVALID_ARGUMENT : 0;
+    }
+};
+
+struct GifFmt : ReadFmtDefaults {
+    using Ws = GifWs;
+    using Px = uint8_t;
+    using Batch = icx_gif_batch;
+    static constexpr int kOk = ICX_GIF_OK, kInternal = ICX_GIF_INTERNAL_ERR;
+    static constexpr const char *kCreate = "icx_gif_batch_create", *kDecode = "icx_gif_batch_decode", *kOne = "icx_gif_decode";
+    static constexpr Stage kOrder[] = {kStParse, kStEntropy, kStConvert};
+    static constexpr const char* kLabel[] = {"parse", "lzw", "render"};
+    // (images are one grid dimension; pixel indices are 32-bit in the index plane)
+    static bool over_limit(int n, int w, int h) {
+        return n > 65535 || w > 65535 || h > 65535 || (int64_t)w * h > ((int64_t)1 << 30);
+    }
+    static bool alloc(Ws& ws, Blocks& mem, icx_ctx*, int n, int w, int h) { return gif_ws_alloc(ws, mem, n, w, h); }
+    static constexpr auto launch = &launch_gif_decode;
+    static constexpr int kStridePx = 3;
+};
+
+struct TiffFmt : ReadFmtDefaults {
+    using Ws = TiffWs;
+    using Px = uint8_t;
+    using Batch = icx_tiff_batch;
+    static constexpr int kOk = ICX_TIFF_OK, kInternal = ICX_TIFF_INTERNAL_ERR;
+    static constexpr const char *kCreate = "icx_tiff_batch_create", *kDecode = "icx_tiff_batch_decode", *kOne = "icx_tiff_decode";
+    static constexpr Stage kOrder[] = {kStParse, kStEntropy, kStConvert};
+    static constexpr const char* kLabel[] = {"parse", "unpack", "render"};
+    // (images are one grid dimension; byte positions inside a chunk are 32-bit)
+    static bool over_limit(int n, int w, int h) { return n > 65535 || (int64_t)w * h > ((int64_t)1 << 30); }
+    static bool alloc(Ws& ws, Blocks& mem, icx_ctx* ctx, int n, int w, int h) {
+        return tiff_ws_alloc(ws, mem, ctx->device, n, w, h);
+    }
+    static constexpr auto launch = &launch_tiff_decode;
+};
+
+// The device side of a one-shot decode through a batch of one: the file, its {offset, size}, the
+// pixels and the result record {status, dims...}. A one-shot declares its batch before this, so
+// these buffers are freed first, then the batch.
+struct OneShot {
+    Buf<uint8_t> in, out;
+    Buf<uint64_t> meta;
+    Buf<int32_t> res;
+    int32_t rec[6] = {0, 0, 0, 0, 0, 0};
+};
+
+}  // namespace
+
+
+struct icx_hdr_batch : ReadBatch<HdrFmt> {};
+struct icx_png_batch : ReadBatch<PngFmt> {};
+struct icx_tga_batch : ReadBatch<TgaFmt> {};
+struct icx_bmp_batch : ReadBatch<BmpFmt> {};
+struct icx_pnm_batch : ReadBatch<PnmFmt> {};
+struct icx_gif_batch : ReadBatch<GifFmt> {};
+struct icx_tiff_batch : ReadBatch<TiffFmt> {};
+
+// `extra`: what the format's workspace takes beyond the sizes (TgaFmt, BmpFmt, PnmFmt).
+template <class F, class... Extra>
+static typename F::Batch* read_batch_new(icx_ctx* ctx, int max_images, int max_w, int max_h, Extra... extra) {
+    if (!ctx || max_images <= 0 || max_w <= 0 || max_h <= 0 || F::over_limit(max_images, max_w, max_h, extra...)) {
+        if (ctx) ctx->err = std::string(F::kCreate) + ": bad arguments";
+        return nullptr;
+    }
+    ICX_HIP(ctx, hipSetDevice(ctx->device), nullptr);
+    auto* b = new typename F::Batch();
+    b->ctx = ctx;
+    b->hook = std::make_unique<EventHook>();
+    if (!F::alloc(b->ws, b->mem, ctx, max_images, max_w, max_h, extra...)) {
+        ctx->err = std::string(F::kCreate) + ": out of device memory: " + hipGetErrorString(hipGetLastError());
+        delete b;
+        return nullptr;
+    }
+    return b;
+}
+
+template <class B>
+static void read_batch_destroy(B* b) {
+    if (!b) return;
+    (void)hipSetDevice(b->ctx->device);
+    delete b;
+}
+
+// The checks in this order: n, nothing to do, null pointers, the stride floor, the format's alignment.
+template <class F, class Out>
+static int read_batch_decode(typename F::Batch* b, int n, const uint8_t* d_data, const uint64_t* d_off,
+                             const uint64_t* d_size, Out* d_out, uint64_t out_stride, int32_t* d_status, int32_t* d_dims,
+                             void* stream) {
+    if (!b) return F::kInternal;
+    icx_ctx* ctx = b->ctx;
+    if (n < 0 || n > b->ws.max_images) { ctx->err = std::string(F::kDecode) + ": n exceeds batch capacity"; return F::kInternal; }
+    if (n == 0) return F::kOk;
+    if (!d_data || !d_off || !d_size || !d_out || !d_status || !d_dims) { ctx->err = "null pointer"; return F::kInternal; }
+    if (out_stride < (uint64_t)F::kStridePx * b->ws.max_w * b->ws.max_h) { ctx->err = std::string(F::kDecode) + ": out_stride too small"; return F::kInternal; }
+    if (const int rc = F::out_refused(ctx, d_out, out_stride)) return rc;
+    ICX_HIP(ctx, hipSetDevice(ctx->device), F::kInternal);
+    hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
+    const RoctxRange range(F::kDecode);
+    b->hook->reset();
+    F::launch(b->ws, n, d_data, d_off, d_size, static_cast<typename F::Px*>(d_out), out_stride, d_status, d_dims, st, b->hook.get());
+    ICX_HIP(ctx, hipGetLastError(), F::kInternal);
+    return F::kOk;
+}
+
+template <int K>
+static int read_stage_times(const EventHook& hook, const Stage (&order)[K], const char* const (&label)[K], const char** names,
+                            float* ms, int cap) {
+    float acc[kStCount];
+    hook.sum(acc);
+    for (int k = 0; k < K && k < cap; ++k) {
+        if (names) names[k] = label[k];
+        if (ms) ms[k] = acc[order[k]];
+    }
+    return K;
+}
+
+// A probe's outputs: what it found when it returned `ok`, else zero.
+static int probe_out(int rc, int ok, int* w, int ww, int* h, int hh, int* d = nullptr, int dd = 0) {
+    if (w) *w = rc == ok ? ww : 0;
+    if (h) *h = rc == ok ? hh : 0;
+    if (d) *d = rc == ok ? dd : 0;
+    return rc;
+}
+
+static void zero_out(std::initializer_list<int*> outs) {
+    for (int* p : outs)
+        if (p) *p = 0;
+}
+
+// Uploads the file, runs launch(io, st) and downloads rec_ints ints of the record. False: a HIP call failed.
+template <class Launch>
+static bool one_shot_run(icx_ctx* ctx, OneShot& io, const uint8_t* data, size_t size, size_t in_cap, uint64_t out_bytes,
+                         int rec_ints, Launch launch) {
+    const uint64_t meta[2] = {0, (uint64_t)size};
+    hipStream_t st = ctx->stream;
+    return io.in.reserve(in_cap) && io.out.reserve(out_bytes) && io.meta.reserve(16) && io.res.reserve(4 * rec_ints) &&
+           hipMemcpyAsync(io.in.p, data, size, hipMemcpyHostToDevice, st) == hipSuccess &&
+           hipMemcpyAsync(io.meta.p, meta, 16, hipMemcpyHostToDevice, st) == hipSuccess && launch(io, st) &&
+           hipMemcpyAsync(io.rec, io.res.p, 4 * rec_ints, hipMemcpyDeviceToHost, st) == hipSuccess &&
+           hipStreamSynchronize(st) == hipSuccess;
+}
+
+// The launcher itself with a null hook, for a batch of one whose slot is `stride`.
+template <class F>
+static auto launch_direct(const typename F::Ws& ws, uint64_t stride) {
+    return [&ws, stride](OneShot& io, hipStream_t st) {
+        F::launch(ws, 1, io.in.p, io.meta.p, io.meta.p + 1, io.out.p, stride, io.res.p, io.res.p + 1, st, nullptr);
+        return hipGetLastError() == hipSuccess;
+    };
+}
+
+// Hands the caller `nbytes` of pixels and the record's dims; returns the record's status.
+template <class F, class T>
+static int one_shot_take(icx_ctx* ctx, const OneShot& io, uint64_t nbytes, T** out, std::initializer_list<int*> dims) {
+    void* hostp = std::malloc(nbytes);
+    if (!hostp || hipMemcpy(hostp, io.out.p, nbytes, hipMemcpyDeviceToHost) != hipSuccess) {
+        std::free(hostp);
+        ctx->err = std::string(F::kOne) + ": host allocation or copy failed";
+        return F::kInternal;
+    }
+    *out = static_cast<T*>(hostp);
+    const int32_t* r = io.rec + 1;
+    for (int* p : dims) {
+        if (p) *p = *r;
+        ++r;
+    }
+    return io.rec[0];
+}
+
+// The one-shot of the byte formats after the probe: pixels only for an image that decoded.
+template <class F, class Launch>
+static int read_one(icx_ctx* ctx, const uint8_t* data, size_t size, uint64_t nbytes, uint8_t** out,
+                    std::initializer_list<int*> dims, Launch launch) {
+    OneShot io;
+    if (!one_shot_run(ctx, io, data, size, size, nbytes, 4, launch)) {
+        if (ctx->err.empty()) ctx->err = std::string(F::kOne) + ": HIP failure";
+        return F::kInternal;
+    }
+    return io.rec[0] == F::kOk ? one_shot_take<F>(ctx, io, nbytes, out, dims) : io.rec[0];
+}
+
+// ------------------------------------------- the host layer the writers share (tga, bmp, pnm, hdr)
+// The guarded part of encode_device_batch: encode(ws, err) returns 0, or fails with what `err` says;
+// nothing may cross the C ABI, so a host allocation failure is an internal error too.
+template <class Ws, class Encode>
+static int encode_batch_guarded(icx_ctx* ctx, const char* entry, Ws*& ws, Ws* (*create)(), int ok, int internal,
+                                Encode encode) {
+    ICX_HIP(ctx, hipSetDevice(ctx->device), internal);
+    const RoctxRange range(entry);
+    std::string err;
+    int rc;
+    try {
+        if (!ws) ws = create();
+        rc = encode(*ws, err);
+    } catch (const std::exception& e) {
+        err = std::string(entry) + ": " + e.what();
+        rc = -1;
+    }
+    if (rc != 0) {
+        ctx->err = err.empty() ? std::string(entry) + ": HIP failure" : err;
+        return internal;
+    }
+    return ok;
+}
+
+// save_to_memory once the arguments are checked: uploads `nbytes` of pixels, has
+// encode(&src, d_file, d_size, d_status, st) write one file of at most `bound` bytes through the
+// batch entry, reads {size, status} and hands the caller a copy of the file.
+template <class T, class Encode>
+static int save_one(icx_ctx* ctx, const char* entry, const void* pixels, uint64_t nbytes, uint64_t bound, uint8_t** out,
+                    size_t* size, int ok, int internal, Encode encode) {
+    ICX_HIP(ctx, hipSetDevice(ctx->device), internal);
+    Buf<T> d_px;
+    Buf<uint8_t> d_file;
+    Buf<uint64_t> d_res;  // the file's size, then its status
+    uint64_t res[2] = {0, 0};
+    hipStream_t st = ctx->stream;
+    if (!(d_px.reserve(nbytes) && d_file.reserve(bound) && d_res.reserve(16) &&
+          hipMemcpyAsync(d_px.p, pixels, nbytes, hipMemcpyHostToDevice, st) == hipSuccess)) {
+        ctx->err = std::string(entry) + ": " + hipGetErrorString(hipGetLastError());
+        return internal;
+    }
+    const T* src = d_px.p;
+    const int rc = encode(&src, d_file.p, d_res.p, reinterpret_cast<int32_t*>(d_res.p + 1), st);
+    if (rc != ok) return rc;
+    ICX_HIP(ctx, hipMemcpy(res, d_res.p, 16, hipMemcpyDeviceToHost), internal);
+    const int code = (int32_t)(res[1] & 0xFFFFFFFFu);
+    if (code != ok) return code;
+    uint8_t* hostp = (uint8_t*)std::malloc(res[0]);
+    if (!hostp || hipMemcpy(hostp, d_file.p, res[0], hipMemcpyDeviceToHost) != hipSuccess) {
+        std::free(hostp);
+        (void)hipGetLastError();
+        ctx->err = std::string(entry) + ": host allocation or copy failed";
+        return internal;
+    }
+    *out = hostp;
+    *size = (size_t)res[0];
+    return ok;
+}
+
+// save_to_file's tail: writes the file save_to_memory made, and frees it.
+static int write_file(icx_ctx* ctx, const char* entry, const char* path, uint8_t* mem, size_t size, int ok, int internal) {
+    std::FILE* f = std::fopen(path, "wb");
+    const bool wrote = f && std::fwrite(mem, 1, size, f) == size;
+    const bool closed = f && std::fclose(f) == 0;
+    std::free(mem);
+    if (!wrote || !closed) {
+        ctx->err = std::string(entry) + ": cannot write " + path;
+        return internal;
+    }
+    return ok;
+}
 
 extern "C" {
 
@@ -918,232 +1280,89 @@ int icx_png_encoder_stage_times(icx_png_encoder* enc, const char** names, float*
 }
 
 // --------------------------------------------------------- Radiance .hdr (Image::readHdr)
-struct icx_hdr_batch {
-    icx_ctx* ctx = nullptr;
-    HdrWs ws;
-    Blocks mem;  // the device memory ws points into
-    std::unique_ptr<EventHook> hook;
-};
-
 int icx_hdr_probe(const uint8_t* data, size_t size, int* w, int* h) {
     int ww = 0, hh = 0;
     const int rc = data ? hdr_probe(data, (int64_t)size, &ww, &hh) : ICX_HDR_NOT_RADIANCE;
-    if (w) *w = rc == ICX_HDR_OK ? ww : 0;
-    if (h) *h = rc == ICX_HDR_OK ? hh : 0;
-    return rc;
+    return probe_out(rc, ICX_HDR_OK, w, ww, h, hh);
 }
 
 icx_hdr_batch* icx_hdr_batch_create(icx_ctx* ctx, int max_images, int max_w, int max_h) {
-    if (!ctx || max_images <= 0 || max_w <= 0 || max_h <= 0) {
-        if (ctx) ctx->err = "icx_hdr_batch_create: bad arguments";
-        return nullptr;
-    }
-    ICX_HIP(ctx, hipSetDevice(ctx->device), nullptr);
-    auto* b = new icx_hdr_batch();
-    b->ctx = ctx;
-    b->hook = std::make_unique<EventHook>();
-    if (!hdr_ws_alloc(b->ws, b->mem, max_images, max_w, max_h)) {
-        ctx->err = std::string("icx_hdr_batch_create: out of device memory: ") + hipGetErrorString(hipGetLastError());
-        delete b;
-        return nullptr;
-    }
-    return b;
+    return read_batch_new<HdrFmt>(ctx, max_images, max_w, max_h);
 }
 
-void icx_hdr_batch_destroy(icx_hdr_batch* b) {
-    if (!b) return;
-    (void)hipSetDevice(b->ctx->device);
-    delete b;
-}
+void icx_hdr_batch_destroy(icx_hdr_batch* b) { read_batch_destroy(b); }
 
 int icx_hdr_batch_decode(icx_hdr_batch* b, int n, const uint8_t* d_data, const uint64_t* d_off, const uint64_t* d_size,
                          float* d_out, uint64_t out_stride, int32_t* d_status, int32_t* d_dims, void* stream) {
-    if (!b) return ICX_HDR_INTERNAL_ERR;
-    icx_ctx* ctx = b->ctx;
-    if (n < 0 || n > b->ws.max_images) { ctx->err = "icx_hdr_batch_decode: n exceeds batch capacity"; return ICX_HDR_INTERNAL_ERR; }
-    if (n == 0) return ICX_HDR_OK;
-    if (!d_data || !d_off || !d_size || !d_out || !d_status || !d_dims) { ctx->err = "null pointer"; return ICX_HDR_INTERNAL_ERR; }
-    if (out_stride < 4ull * b->ws.max_w * b->ws.max_h) { ctx->err = "icx_hdr_batch_decode: out_stride too small"; return ICX_HDR_INTERNAL_ERR; }
-    ICX_HIP(ctx, hipSetDevice(ctx->device), ICX_HDR_INTERNAL_ERR);
-    hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
-    const RoctxRange range("icx_hdr_batch_decode");
-    b->hook->reset();
-    launch_hdr_decode(b->ws, n, d_data, d_off, d_size, d_out, out_stride, d_status, d_dims, st, b->hook.get());
-    ICX_HIP(ctx, hipGetLastError(), ICX_HDR_INTERNAL_ERR);
-    return ICX_HDR_OK;
+    return read_batch_decode<HdrFmt>(b, n, d_data, d_off, d_size, d_out, out_stride, d_status, d_dims, stream);
 }
 
 int icx_hdr_batch_stage_times(const icx_hdr_batch* b, const char** names, float* ms, int cap) {
-    if (!b) return 0;
-    static const Stage order[4] = {kStParse, kStUnstuff, kStEntropy, kStConvert};
-    static const char* const label[4] = {"parse", "locate", "unpack", "convert"};
-    float acc[kStCount];
-    b->hook->sum(acc);
-    for (int k = 0; k < 4 && k < cap; ++k) {
-        if (names) names[k] = label[k];
-        if (ms) ms[k] = acc[order[k]];
-    }
-    return 4;
+    return b ? read_stage_times(*b->hook, HdrFmt::kOrder, HdrFmt::kLabel, names, ms, cap) : 0;
 }
 
 int icx_hdr_decode(icx_ctx* ctx, const uint8_t* data, size_t size, float** out, int* w, int* h, int* rows) {
     if (out) *out = nullptr;
-    if (w) *w = 0;
-    if (h) *h = 0;
-    if (rows) *rows = 0;
+    zero_out({w, h, rows});
     if (!ctx || !out) return ICX_HDR_INTERNAL_ERR;
     int ww = 0, hh = 0;
     const int prc = icx_hdr_probe(data, size, &ww, &hh);
     if (prc != ICX_HDR_OK) return prc;  // header errors need no device work
     ICX_HIP(ctx, hipSetDevice(ctx->device), ICX_HDR_INTERNAL_ERR);
-    // (declared before the buffers: they are freed first, then the batch)
     std::unique_ptr<icx_hdr_batch, void (*)(icx_hdr_batch*)> b(icx_hdr_batch_create(ctx, 1, ww, hh), icx_hdr_batch_destroy);
     if (!b) return ICX_HDR_INTERNAL_ERR;
-    const uint64_t nout = 4ull * ww * hh;
-    Buf<uint8_t> d_in;
-    Buf<float> d_out;
-    Buf<uint64_t> d_meta;
-    Buf<int32_t> d_res;
-    int rc = ICX_HDR_INTERNAL_ERR;
-    const uint64_t meta[2] = {0, (uint64_t)size};
-    int32_t res[4] = {0, 0, 0, 0};
-    hipStream_t st = ctx->stream;
-    if (d_in.reserve(size + 16) && d_out.reserve(nout * 4) && d_meta.reserve(16) && d_res.reserve(16) &&
-        hipMemcpyAsync(d_in.p, data, size, hipMemcpyHostToDevice, st) == hipSuccess &&
-        hipMemcpyAsync(d_meta.p, meta, 16, hipMemcpyHostToDevice, st) == hipSuccess &&
-        icx_hdr_batch_decode(b.get(), 1, d_in.p, d_meta.p, d_meta.p + 1, d_out.p, nout, d_res.p, d_res.p + 1, st) == ICX_HDR_OK &&
-        hipMemcpyAsync(res, d_res.p, 16, hipMemcpyDeviceToHost, st) == hipSuccess && hipStreamSynchronize(st) == hipSuccess) {
-        rc = res[0];
-        float* hostp = (float*)std::malloc(nout * 4);
-        if (hostp && hipMemcpy(hostp, d_out.p, nout * 4, hipMemcpyDeviceToHost) == hipSuccess) {
-            *out = hostp;
-            if (w) *w = res[1];
-            if (h) *h = res[2];
-            if (rows) *rows = res[3];
-        } else {
-            std::free(hostp);
-            ctx->err = "icx_hdr_decode: host allocation or copy failed";
-            rc = ICX_HDR_INTERNAL_ERR;
-        }
-    } else if (ctx->err.empty()) {
-        ctx->err = "icx_hdr_decode: HIP failure";
+    const uint64_t nout = 4ull * ww * hh;  // floats
+    OneShot io;
+    // (through the public entry: its hook and roctx range; the readers load past the file's end)
+    if (!one_shot_run(ctx, io, data, size, size + 16, nout * 4, 4, [&](OneShot& o, hipStream_t st) {
+            return icx_hdr_batch_decode(b.get(), 1, o.in.p, o.meta.p, o.meta.p + 1, reinterpret_cast<float*>(o.out.p), nout,
+                                        o.res.p, o.res.p + 1, st) == ICX_HDR_OK;
+        })) {
+        if (ctx->err.empty()) ctx->err = "icx_hdr_decode: HIP failure";
+        return ICX_HDR_INTERNAL_ERR;
     }
-    return rc;
+    // whatever the status: a truncated file returns the rows it had, and how many
+    return one_shot_take<HdrFmt>(ctx, io, nout * 4, out, {w, h, rows});
 }
 
 // --------------------------------------------------------- PNG read (Image::readPng)
-struct icx_png_batch {
-    icx_ctx* ctx = nullptr;
-    PngdWs ws;
-    Blocks mem;  // the device memory ws points into
-    std::unique_ptr<EventHook> hook;
-};
-
 int icx_png_probe(const uint8_t* data, size_t size, int* w, int* h) {
     int ww = 0, hh = 0;
     const int rc = data ? pngd_probe(data, (int64_t)size, &ww, &hh) : ICX_PNGR_NOT_PNG;
-    if (w) *w = rc == ICX_PNGR_OK ? ww : 0;
-    if (h) *h = rc == ICX_PNGR_OK ? hh : 0;
-    return rc;
+    return probe_out(rc, ICX_PNGR_OK, w, ww, h, hh);
 }
 
 icx_png_batch* icx_png_batch_create(icx_ctx* ctx, int max_images, int max_w, int max_h) {
-    // (images are one grid dimension; no image the walk accepts is larger than the pixel limit)
-    if (!ctx || max_images <= 0 || max_images > 65535 || max_w <= 0 || max_h <= 0 || max_w > 0x1000000 || max_h > 0x1000000) {
-        if (ctx) ctx->err = "icx_png_batch_create: bad arguments";
-        return nullptr;
-    }
-    ICX_HIP(ctx, hipSetDevice(ctx->device), nullptr);
-    auto* b = new icx_png_batch();
-    b->ctx = ctx;
-    b->hook = std::make_unique<EventHook>();
-    if (!pngd_ws_alloc(b->ws, b->mem, max_images, max_w, max_h)) {
-        ctx->err = std::string("icx_png_batch_create: out of device memory: ") + hipGetErrorString(hipGetLastError());
-        delete b;
-        return nullptr;
-    }
-    return b;
+    return read_batch_new<PngFmt>(ctx, max_images, max_w, max_h);
 }
 
-void icx_png_batch_destroy(icx_png_batch* b) {
-    if (!b) return;
-    (void)hipSetDevice(b->ctx->device);
-    delete b;
-}
+void icx_png_batch_destroy(icx_png_batch* b) { read_batch_destroy(b); }
 
 int icx_png_batch_decode(icx_png_batch* b, int n, const uint8_t* d_data, const uint64_t* d_off, const uint64_t* d_size,
                          uint8_t* d_out, uint64_t out_stride, int32_t* d_status, int32_t* d_dims, void* stream) {
-    if (!b) return ICX_PNGR_INTERNAL_ERR;
-    icx_ctx* ctx = b->ctx;
-    if (n < 0 || n > b->ws.max_images) { ctx->err = "icx_png_batch_decode: n exceeds batch capacity"; return ICX_PNGR_INTERNAL_ERR; }
-    if (n == 0) return ICX_PNGR_OK;
-    if (!d_data || !d_off || !d_size || !d_out || !d_status || !d_dims) { ctx->err = "null pointer"; return ICX_PNGR_INTERNAL_ERR; }
-    if (out_stride < 4ull * b->ws.max_w * b->ws.max_h) { ctx->err = "icx_png_batch_decode: out_stride too small"; return ICX_PNGR_INTERNAL_ERR; }
-    if ((reinterpret_cast<uintptr_t>(d_out) & 3) || (out_stride & 3)) { ctx->err = "icx_png_batch_decode: d_out and out_stride must be multiples of 4"; return ICX_PNGR_INTERNAL_ERR; }
-    ICX_HIP(ctx, hipSetDevice(ctx->device), ICX_PNGR_INTERNAL_ERR);
-    hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
-    const RoctxRange range("icx_png_batch_decode");
-    b->hook->reset();
-    launch_pngd_decode(b->ws, n, d_data, d_off, d_size, d_out, out_stride, d_status, d_dims, st, b->hook.get());
-    ICX_HIP(ctx, hipGetLastError(), ICX_PNGR_INTERNAL_ERR);
-    return ICX_PNGR_OK;
+    return read_batch_decode<PngFmt>(b, n, d_data, d_off, d_size, d_out, out_stride, d_status, d_dims, stream);
 }
 
 int icx_png_batch_stage_times(const icx_png_batch* b, const char** names, float* ms, int cap) {
-    if (!b) return 0;
-    static const Stage order[5] = {kStParse, kStUnstuff, kStEntropy, kStIdct, kStConvert};
-    static const char* const label[5] = {"parse", "gather", "inflate", "unfilter", "expand"};
-    float acc[kStCount];
-    b->hook->sum(acc);
-    for (int k = 0; k < 5 && k < cap; ++k) {
-        if (names) names[k] = label[k];
-        if (ms) ms[k] = acc[order[k]];
-    }
-    return 5;
+    return b ? read_stage_times(*b->hook, PngFmt::kOrder, PngFmt::kLabel, names, ms, cap) : 0;
 }
 
 int icx_png_decode(icx_ctx* ctx, const uint8_t* data, size_t size, uint8_t** out, int* w, int* h) {
     if (out) *out = nullptr;
-    if (w) *w = 0;
-    if (h) *h = 0;
+    zero_out({w, h});
     if (!ctx || !out) return ICX_PNGR_INTERNAL_ERR;
     int ww = 0, hh = 0;
     const int prc = icx_png_probe(data, size, &ww, &hh);
     if (prc != ICX_PNGR_OK) return prc;  // header and chunk errors need no device work
     ICX_HIP(ctx, hipSetDevice(ctx->device), ICX_PNGR_INTERNAL_ERR);
-    // (declared before the buffers: they are freed first, then the batch)
     std::unique_ptr<icx_png_batch, void (*)(icx_png_batch*)> b(icx_png_batch_create(ctx, 1, ww, hh), icx_png_batch_destroy);
     if (!b) return ICX_PNGR_INTERNAL_ERR;
     const uint64_t nout = 4ull * ww * hh;
-    Buf<uint8_t> d_in, d_out;
-    Buf<uint64_t> d_meta;
-    Buf<int32_t> d_res;
-    int rc = ICX_PNGR_INTERNAL_ERR;
-    const uint64_t meta[2] = {0, (uint64_t)size};
-    int32_t res[4] = {0, 0, 0, 0};
-    hipStream_t st = ctx->stream;
-    if (d_in.reserve(size) && d_out.reserve(nout) && d_meta.reserve(16) && d_res.reserve(16) &&
-        hipMemcpyAsync(d_in.p, data, size, hipMemcpyHostToDevice, st) == hipSuccess &&
-        hipMemcpyAsync(d_meta.p, meta, 16, hipMemcpyHostToDevice, st) == hipSuccess &&
-        icx_png_batch_decode(b.get(), 1, d_in.p, d_meta.p, d_meta.p + 1, d_out.p, nout, d_res.p, d_res.p + 1, st) == ICX_PNGR_OK &&
-        hipMemcpyAsync(res, d_res.p, 16, hipMemcpyDeviceToHost, st) == hipSuccess && hipStreamSynchronize(st) == hipSuccess) {
-        rc = res[0];
-        if (rc == ICX_PNGR_OK) {
-            uint8_t* hostp = (uint8_t*)std::malloc(nout);
-            if (hostp && hipMemcpy(hostp, d_out.p, nout, hipMemcpyDeviceToHost) == hipSuccess) {
-                *out = hostp;
-                if (w) *w = res[1];
-                if (h) *h = res[2];
-            } else {
-                std::free(hostp);
-                ctx->err = "icx_png_decode: host allocation or copy failed";
-                rc = ICX_PNGR_INTERNAL_ERR;
-            }
-        }
-    } else if (ctx->err.empty()) {
-        ctx->err = "icx_png_decode: HIP failure";
-    }
-    return rc;
+    // (through the public entry: its hook and roctx range)
+    return read_one<PngFmt>(ctx, data, size, nout, out, {w, h}, [&](OneShot& o, hipStream_t st) {
+        return icx_png_batch_decode(b.get(), 1, o.in.p, o.meta.p, o.meta.p + 1, o.out.p, nout, o.res.p, o.res.p + 1, st) ==
+               ICX_PNGR_OK;
+    });
 }
 
 // --------------------------------------------------------- OpenEXR (Image::readExr)
@@ -1321,142 +1540,47 @@ int icx_exr_save_to_file(icx_ctx* ctx, const char* path, const float* data, int 
     size_t size = 0;
     const int rc = icx_exr_save_to_memory(ctx, data, width, height, components, save_as_fp16, &mem, &size);
     if (rc != ICX_EXR_SUCCESS) return rc;
-    std::FILE* f = std::fopen(path, "wb");
-    const bool ok = f && std::fwrite(mem, 1, size, f) == size;
-    const bool closed = f && std::fclose(f) == 0;
-    std::free(mem);
-    if (!ok || !closed) {
-        ctx->err = std::string("icx_exr_save_to_file: cannot write ") + path;
-        return ICX_EXR_INTERNAL_ERR;
-    }
-    return ICX_EXR_SUCCESS;
+    return write_file(ctx, "icx_exr_save_to_file", path, mem, size, ICX_EXR_SUCCESS, ICX_EXR_INTERNAL_ERR);
 }
 
 // --------------------------------------------------------- Targa (Image::readTga / writeTga)
-struct icx_tga_batch {
-    icx_ctx* ctx = nullptr;
-    TgaWs ws;
-    Blocks mem;  // the device memory ws points into
-    std::unique_ptr<EventHook> hook;
-};
-
 int icx_tga_probe(const uint8_t* data, size_t size, int* w, int* h, int* channels) {
     int ww = 0, hh = 0, dd = 0;
     const int rc = data ? tga_probe(data, (int64_t)size, &ww, &hh, &dd) : ICX_TGA_BAD_HEADER;
-    if (w) *w = rc == ICX_TGA_OK ? ww : 0;
-    if (h) *h = rc == ICX_TGA_OK ? hh : 0;
-    if (channels) *channels = rc == ICX_TGA_OK ? dd : 0;
-    return rc;
-}
-
-// rle false: a workspace for raw files only (no tile tables, no RLE kernels launched).
-static icx_tga_batch* tga_batch_new(icx_ctx* ctx, int max_images, int max_w, int max_h, bool rle) {
-    // (images are one grid dimension; pixel indices are 32-bit in the tile tables)
-    if (!ctx || max_images <= 0 || max_images > 65535 || max_w <= 0 || max_h <= 0 || max_w > 65535 || max_h > 65535 ||
-        (int64_t)max_w * max_h > ((int64_t)1 << 30)) {
-        if (ctx) ctx->err = "icx_tga_batch_create: bad arguments";
-        return nullptr;
-    }
-    ICX_HIP(ctx, hipSetDevice(ctx->device), nullptr);
-    auto* b = new icx_tga_batch();
-    b->ctx = ctx;
-    b->hook = std::make_unique<EventHook>();
-    if (!tga_ws_alloc(b->ws, b->mem, max_images, max_w, max_h, rle)) {
-        ctx->err = std::string("icx_tga_batch_create: out of device memory: ") + hipGetErrorString(hipGetLastError());
-        delete b;
-        return nullptr;
-    }
-    return b;
+    return probe_out(rc, ICX_TGA_OK, w, ww, h, hh, channels, dd);
 }
 
 icx_tga_batch* icx_tga_batch_create(icx_ctx* ctx, int max_images, int max_w, int max_h) {
-    return tga_batch_new(ctx, max_images, max_w, max_h, true);
+    return read_batch_new<TgaFmt>(ctx, max_images, max_w, max_h, true);
 }
 
-void icx_tga_batch_destroy(icx_tga_batch* b) {
-    if (!b) return;
-    (void)hipSetDevice(b->ctx->device);
-    delete b;
-}
+void icx_tga_batch_destroy(icx_tga_batch* b) { read_batch_destroy(b); }
 
 int icx_tga_batch_decode(icx_tga_batch* b, int n, const uint8_t* d_data, const uint64_t* d_off, const uint64_t* d_size,
                          uint8_t* d_out, uint64_t out_stride, int32_t* d_status, int32_t* d_dims, void* stream) {
-    if (!b) return ICX_TGA_INTERNAL_ERR;
-    icx_ctx* ctx = b->ctx;
-    if (n < 0 || n > b->ws.max_images) { ctx->err = "icx_tga_batch_decode: n exceeds batch capacity"; return ICX_TGA_INTERNAL_ERR; }
-    if (n == 0) return ICX_TGA_OK;
-    if (!d_data || !d_off || !d_size || !d_out || !d_status || !d_dims) { ctx->err = "null pointer"; return ICX_TGA_INTERNAL_ERR; }
-    if (out_stride < 4ull * b->ws.max_w * b->ws.max_h) { ctx->err = "icx_tga_batch_decode: out_stride too small"; return ICX_TGA_INTERNAL_ERR; }
-    ICX_HIP(ctx, hipSetDevice(ctx->device), ICX_TGA_INTERNAL_ERR);
-    hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
-    const RoctxRange range("icx_tga_batch_decode");
-    b->hook->reset();
-    launch_tga_decode(b->ws, n, d_data, d_off, d_size, d_out, out_stride, d_status, d_dims, st, b->hook.get());
-    ICX_HIP(ctx, hipGetLastError(), ICX_TGA_INTERNAL_ERR);
-    return ICX_TGA_OK;
+    return read_batch_decode<TgaFmt>(b, n, d_data, d_off, d_size, d_out, out_stride, d_status, d_dims, stream);
 }
 
 int icx_tga_batch_stage_times(const icx_tga_batch* b, const char** names, float* ms, int cap) {
-    if (!b) return 0;
-    static const Stage order[4] = {kStParse, kStUnstuff, kStEntropy, kStConvert};
-    static const char* const label[4] = {"parse", "locate", "expand", "raw"};
-    float acc[kStCount];
-    b->hook->sum(acc);
-    for (int k = 0; k < 4 && k < cap; ++k) {
-        if (names) names[k] = label[k];
-        if (ms) ms[k] = acc[order[k]];
-    }
-    return 4;
+    return b ? read_stage_times(*b->hook, TgaFmt::kOrder, TgaFmt::kLabel, names, ms, cap) : 0;
 }
 
 int icx_tga_decode(icx_ctx* ctx, const uint8_t* data, size_t size, uint8_t** out, int* w, int* h, int* channels) {
     if (out) *out = nullptr;
-    if (w) *w = 0;
-    if (h) *h = 0;
-    if (channels) *channels = 0;
+    zero_out({w, h, channels});
     if (!ctx || !out) return ICX_TGA_INTERNAL_ERR;
     int ww = 0, hh = 0, dd = 0;
     const int prc = icx_tga_probe(data, size, &ww, &hh, &dd);
     if (prc != ICX_TGA_OK) return prc;  // header errors need no device work
     if ((int64_t)ww * hh > ((int64_t)1 << 30)) return ICX_TGA_TOO_LARGE;  // (no batch workspace is that large)
     ICX_HIP(ctx, hipSetDevice(ctx->device), ICX_TGA_INTERNAL_ERR);
-    // (declared before the buffers: they are freed first, then the batch)
     // (the probe accepted the header: byte 2 is the image type, 9-11 run-length coded; a raw file
     // needs no tile tables, and the one slot holds just the image's w*h*d bytes)
-    std::unique_ptr<icx_tga_batch, void (*)(icx_tga_batch*)> b(tga_batch_new(ctx, 1, ww, hh, data[2] >= 9), icx_tga_batch_destroy);
+    std::unique_ptr<icx_tga_batch, void (*)(icx_tga_batch*)> b(read_batch_new<TgaFmt>(ctx, 1, ww, hh, data[2] >= 9),
+                                                               icx_tga_batch_destroy);
     if (!b) return ICX_TGA_INTERNAL_ERR;
-    const uint64_t nout = (uint64_t)ww * hh * dd, stride = nout;
-    Buf<uint8_t> d_in, d_out;
-    Buf<uint64_t> d_meta;
-    Buf<int32_t> d_res;
-    int rc = ICX_TGA_INTERNAL_ERR;
-    const uint64_t meta[2] = {0, (uint64_t)size};
-    int32_t res[4] = {0, 0, 0, 0};
-    hipStream_t st = ctx->stream;
-    if (d_in.reserve(size) && d_out.reserve(stride) && d_meta.reserve(16) && d_res.reserve(16) &&
-        hipMemcpyAsync(d_in.p, data, size, hipMemcpyHostToDevice, st) == hipSuccess &&
-        hipMemcpyAsync(d_meta.p, meta, 16, hipMemcpyHostToDevice, st) == hipSuccess &&
-        (launch_tga_decode(b->ws, 1, d_in.p, d_meta.p, d_meta.p + 1, d_out.p, stride, d_res.p, d_res.p + 1, st, nullptr),
-         hipGetLastError() == hipSuccess) &&
-        hipMemcpyAsync(res, d_res.p, 16, hipMemcpyDeviceToHost, st) == hipSuccess && hipStreamSynchronize(st) == hipSuccess) {
-        rc = res[0];
-        if (rc == ICX_TGA_OK) {
-            uint8_t* hostp = (uint8_t*)std::malloc(nout);
-            if (hostp && hipMemcpy(hostp, d_out.p, nout, hipMemcpyDeviceToHost) == hipSuccess) {
-                *out = hostp;
-                if (w) *w = res[1];
-                if (h) *h = res[2];
-                if (channels) *channels = res[3];
-            } else {
-                std::free(hostp);
-                ctx->err = "icx_tga_decode: host allocation or copy failed";
-                rc = ICX_TGA_INTERNAL_ERR;
-            }
-        }
-    } else if (ctx->err.empty()) {
-        ctx->err = "icx_tga_decode: HIP failure";
-    }
-    return rc;
+    const uint64_t nout = (uint64_t)ww * hh * dd;
+    return read_one<TgaFmt>(ctx, data, size, nout, out, {w, h, channels}, launch_direct<TgaFmt>(b->ws, nout));
 }
 
 size_t icx_tga_encode_bound(int width, int height, int d) { return (size_t)tga_encode_bound(width, height, d); }
@@ -1469,23 +1593,11 @@ int icx_tga_encode_device_batch(icx_ctx* ctx, int n, const uint8_t* const* d_src
         (n > 0 && (!d_src || !widths || !heights || !d_out || !d_sizes || !d_status)))
         return ICX_TGA_INVALID_ARGUMENT;
     if (n == 0) return ICX_TGA_OK;
-    ICX_HIP(ctx, hipSetDevice(ctx->device), ICX_TGA_INTERNAL_ERR);
-    const RoctxRange range("icx_tga_encode_device_batch");
-    std::string err;
-    int rc;
-    try {  // (nothing may cross the C ABI: a host allocation failure is an internal error)
-        if (!ctx->tgaw) ctx->tgaw = tgaw_ws_create();
-        rc = tga_encode_batch(stream ? (hipStream_t)stream : ctx->stream, *ctx->tgaw, n, d_src, widths, heights, d,
-                              rle != 0, d_out, out_stride, d_sizes, d_status, err);
-    } catch (const std::exception& e) {
-        err = std::string("icx_tga_encode_device_batch: ") + e.what();
-        rc = -1;
-    }
-    if (rc != 0) {
-        ctx->err = err.empty() ? "icx_tga_encode_device_batch: HIP failure" : err;
-        return ICX_TGA_INTERNAL_ERR;
-    }
-    return ICX_TGA_OK;
+    return encode_batch_guarded(ctx, "icx_tga_encode_device_batch", ctx->tgaw, tgaw_ws_create, ICX_TGA_OK,
+                                ICX_TGA_INTERNAL_ERR, [&](TgawWs& ws, std::string& err) {
+                                    return tga_encode_batch(stream ? (hipStream_t)stream : ctx->stream, ws, n, d_src, widths,
+                                                            heights, d, rle != 0, d_out, out_stride, d_sizes, d_status, err);
+                                });
 }
 
 int icx_tga_save_to_memory(icx_ctx* ctx, const uint8_t* pixels, int width, int height, int d, int rle, uint8_t** out,
@@ -1495,35 +1607,12 @@ int icx_tga_save_to_memory(icx_ctx* ctx, const uint8_t* pixels, int width, int h
     if (!ctx) return ICX_TGA_INTERNAL_ERR;
     const uint64_t bound = tga_encode_bound(width, height, d);
     if (!pixels || !out || !size || bound == 0) return ICX_TGA_INVALID_ARGUMENT;
-    ICX_HIP(ctx, hipSetDevice(ctx->device), ICX_TGA_INTERNAL_ERR);
-    const uint64_t npx = (uint64_t)width * height * d;
-    Buf<uint8_t> d_px, d_file;
-    Buf<uint64_t> d_res;  // the file's size, then its status
-    uint64_t res[2] = {0, 0};
-    hipStream_t st = ctx->stream;
-    if (!(d_px.reserve(npx) && d_file.reserve(bound) && d_res.reserve(16) &&
-          hipMemcpyAsync(d_px.p, pixels, npx, hipMemcpyHostToDevice, st) == hipSuccess)) {
-        ctx->err = std::string("icx_tga_save_to_memory: ") + hipGetErrorString(hipGetLastError());
-        return ICX_TGA_INTERNAL_ERR;
-    }
-    const uint8_t* src = d_px.p;
     const int32_t w = width, h = height;
-    const int rc = icx_tga_encode_device_batch(ctx, 1, &src, &w, &h, d, rle, d_file.p, bound, d_res.p,
-                                               reinterpret_cast<int32_t*>(d_res.p + 1), st);
-    if (rc != ICX_TGA_OK) return rc;
-    ICX_HIP(ctx, hipMemcpy(res, d_res.p, 16, hipMemcpyDeviceToHost), ICX_TGA_INTERNAL_ERR);
-    const int code = (int32_t)(res[1] & 0xFFFFFFFFu);
-    if (code != ICX_TGA_OK) return code;
-    uint8_t* hostp = (uint8_t*)std::malloc(res[0]);
-    if (!hostp || hipMemcpy(hostp, d_file.p, res[0], hipMemcpyDeviceToHost) != hipSuccess) {
-        std::free(hostp);
-        (void)hipGetLastError();
-        ctx->err = "icx_tga_save_to_memory: host allocation or copy failed";
-        return ICX_TGA_INTERNAL_ERR;
-    }
-    *out = hostp;
-    *size = (size_t)res[0];
-    return ICX_TGA_OK;
+    return save_one<uint8_t>(ctx, "icx_tga_save_to_memory", pixels, (uint64_t)width * height * d, bound, out, size, ICX_TGA_OK,
+                             ICX_TGA_INTERNAL_ERR,
+                             [&](const uint8_t* const* src, uint8_t* d_file, uint64_t* d_size, int32_t* d_status, hipStream_t st) {
+                                 return icx_tga_encode_device_batch(ctx, 1, src, &w, &h, d, rle, d_file, bound, d_size, d_status, st);
+                             });
 }
 
 int icx_tga_save_to_file(icx_ctx* ctx, const char* path, const uint8_t* pixels, int width, int height, int d, int rle) {
@@ -1533,145 +1622,50 @@ int icx_tga_save_to_file(icx_ctx* ctx, const char* path, const uint8_t* pixels, 
     size_t size = 0;
     const int rc = icx_tga_save_to_memory(ctx, pixels, width, height, d, rle, &mem, &size);
     if (rc != ICX_TGA_OK) return rc;
-    std::FILE* f = std::fopen(path, "wb");
-    const bool ok = f && std::fwrite(mem, 1, size, f) == size;
-    const bool closed = f && std::fclose(f) == 0;
-    std::free(mem);
-    if (!ok || !closed) {
-        ctx->err = std::string("icx_tga_save_to_file: cannot write ") + path;
-        return ICX_TGA_INTERNAL_ERR;
-    }
-    return ICX_TGA_OK;
+    return write_file(ctx, "icx_tga_save_to_file", path, mem, size, ICX_TGA_OK, ICX_TGA_INTERNAL_ERR);
 }
 
-// --------------------------------------------------------- BMP (Image::readBmp / writeBmp)
-struct icx_bmp_batch {
-    icx_ctx* ctx = nullptr;
-    BmpWs ws;
-    Blocks mem;  // the device memory ws points into
-    std::unique_ptr<EventHook> hook;
-};
 
+// --------------------------------------------------------- BMP (Image::readBmp / writeBmp)
 int icx_bmp_probe(const uint8_t* data, size_t size, int* w, int* h, int* channels) {
     int ww = 0, hh = 0, dd = 0;
     const int rc = data ? bmp_probe(data, (int64_t)size, &ww, &hh, &dd, nullptr) : ICX_BMP_NOT_BMP;
-    if (w) *w = rc == ICX_BMP_OK ? ww : 0;
-    if (h) *h = rc == ICX_BMP_OK ? hh : 0;
-    if (channels) *channels = rc == ICX_BMP_OK ? dd : 0;
-    return rc;
-}
-
-// stream_cap: the run-length stream bytes per image the tile tables cover; 0: a workspace for raw
-// files only (no tile tables, no RLE kernels launched).
-static icx_bmp_batch* bmp_batch_new(icx_ctx* ctx, int max_images, int max_w, int max_h, int64_t stream_cap) {
-    // (images are one grid dimension, a stream's tiles another)
-    if (!ctx || max_images <= 0 || max_images > 65535 || max_w <= 0 || max_h <= 0 ||
-        (int64_t)max_w * max_h > ((int64_t)1 << 30) || stream_cap < 0 || stream_cap > ((int64_t)1 << 42)) {
-        if (ctx) ctx->err = "icx_bmp_batch_create: bad arguments";
-        return nullptr;
-    }
-    ICX_HIP(ctx, hipSetDevice(ctx->device), nullptr);
-    auto* b = new icx_bmp_batch();
-    b->ctx = ctx;
-    b->hook = std::make_unique<EventHook>();
-    if (!bmp_ws_alloc(b->ws, b->mem, max_images, max_w, max_h, stream_cap)) {
-        ctx->err = std::string("icx_bmp_batch_create: out of device memory: ") + hipGetErrorString(hipGetLastError());
-        delete b;
-        return nullptr;
-    }
-    return b;
+    return probe_out(rc, ICX_BMP_OK, w, ww, h, hh, channels, dd);
 }
 
 icx_bmp_batch* icx_bmp_batch_create(icx_ctx* ctx, int max_images, int max_w, int max_h) {
-    // (sizes bmp_batch_new refuses have no bound to speak of)
+    // (sizes read_batch_new refuses have no bound to speak of)
     const bool sized = max_w > 0 && max_h > 0 && (int64_t)max_w * max_h <= ((int64_t)1 << 30);
-    return bmp_batch_new(ctx, max_images, max_w, max_h, sized ? bmp_stream_bound(max_w, max_h) : 0);
+    return read_batch_new<BmpFmt>(ctx, max_images, max_w, max_h, sized ? bmp_stream_bound(max_w, max_h) : 0);
 }
 
-void icx_bmp_batch_destroy(icx_bmp_batch* b) {
-    if (!b) return;
-    (void)hipSetDevice(b->ctx->device);
-    delete b;
-}
+void icx_bmp_batch_destroy(icx_bmp_batch* b) { read_batch_destroy(b); }
 
 int icx_bmp_batch_decode(icx_bmp_batch* b, int n, const uint8_t* d_data, const uint64_t* d_off, const uint64_t* d_size,
                          uint8_t* d_out, uint64_t out_stride, int32_t* d_status, int32_t* d_dims, void* stream) {
-    if (!b) return ICX_BMP_INTERNAL_ERR;
-    icx_ctx* ctx = b->ctx;
-    if (n < 0 || n > b->ws.max_images) { ctx->err = "icx_bmp_batch_decode: n exceeds batch capacity"; return ICX_BMP_INTERNAL_ERR; }
-    if (n == 0) return ICX_BMP_OK;
-    if (!d_data || !d_off || !d_size || !d_out || !d_status || !d_dims) { ctx->err = "null pointer"; return ICX_BMP_INTERNAL_ERR; }
-    if (out_stride < 4ull * b->ws.max_w * b->ws.max_h) { ctx->err = "icx_bmp_batch_decode: out_stride too small"; return ICX_BMP_INTERNAL_ERR; }
-    ICX_HIP(ctx, hipSetDevice(ctx->device), ICX_BMP_INTERNAL_ERR);
-    hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
-    const RoctxRange range("icx_bmp_batch_decode");
-    b->hook->reset();
-    launch_bmp_decode(b->ws, n, d_data, d_off, d_size, d_out, out_stride, d_status, d_dims, st, b->hook.get());
-    ICX_HIP(ctx, hipGetLastError(), ICX_BMP_INTERNAL_ERR);
-    return ICX_BMP_OK;
+    return read_batch_decode<BmpFmt>(b, n, d_data, d_off, d_size, d_out, out_stride, d_status, d_dims, stream);
 }
 
 int icx_bmp_batch_stage_times(const icx_bmp_batch* b, const char** names, float* ms, int cap) {
-    if (!b) return 0;
-    static const Stage order[5] = {kStParse, kStUnstuff, kStWrite, kStEntropy, kStConvert};
-    static const char* const label[5] = {"parse", "locate", "fill", "expand", "raw"};
-    float acc[kStCount];
-    b->hook->sum(acc);
-    for (int k = 0; k < 5 && k < cap; ++k) {
-        if (names) names[k] = label[k];
-        if (ms) ms[k] = acc[order[k]];
-    }
-    return 5;
+    return b ? read_stage_times(*b->hook, BmpFmt::kOrder, BmpFmt::kLabel, names, ms, cap) : 0;
 }
 
 int icx_bmp_decode(icx_ctx* ctx, const uint8_t* data, size_t size, uint8_t** out, int* w, int* h, int* channels) {
     if (out) *out = nullptr;
-    if (w) *w = 0;
-    if (h) *h = 0;
-    if (channels) *channels = 0;
+    zero_out({w, h, channels});
     if (!ctx || !out) return ICX_BMP_INTERNAL_ERR;
     int ww = 0, hh = 0, dd = 0;
     int64_t stream = 0;
     const int prc = data ? bmp_probe(data, (int64_t)size, &ww, &hh, &dd, &stream) : ICX_BMP_NOT_BMP;
     if (prc != ICX_BMP_OK) return prc;  // header errors (more than 2^30 pixels among them) need no device work
     ICX_HIP(ctx, hipSetDevice(ctx->device), ICX_BMP_INTERNAL_ERR);
-    // (declared before the buffers: they are freed first, then the batch)
     // (the tile tables cover this file's own stream, whatever its length; a raw file needs none,
     // and the one slot holds just the image's w*h*d bytes)
-    std::unique_ptr<icx_bmp_batch, void (*)(icx_bmp_batch*)> b(bmp_batch_new(ctx, 1, ww, hh, stream), icx_bmp_batch_destroy);
+    std::unique_ptr<icx_bmp_batch, void (*)(icx_bmp_batch*)> b(read_batch_new<BmpFmt>(ctx, 1, ww, hh, stream),
+                                                               icx_bmp_batch_destroy);
     if (!b) return ICX_BMP_INTERNAL_ERR;
-    const uint64_t nout = (uint64_t)ww * hh * dd, stride = nout;
-    Buf<uint8_t> d_in, d_out;
-    Buf<uint64_t> d_meta;
-    Buf<int32_t> d_res;
-    int rc = ICX_BMP_INTERNAL_ERR;
-    const uint64_t meta[2] = {0, (uint64_t)size};
-    int32_t res[4] = {0, 0, 0, 0};
-    hipStream_t st = ctx->stream;
-    if (d_in.reserve(size) && d_out.reserve(stride) && d_meta.reserve(16) && d_res.reserve(16) &&
-        hipMemcpyAsync(d_in.p, data, size, hipMemcpyHostToDevice, st) == hipSuccess &&
-        hipMemcpyAsync(d_meta.p, meta, 16, hipMemcpyHostToDevice, st) == hipSuccess &&
-        (launch_bmp_decode(b->ws, 1, d_in.p, d_meta.p, d_meta.p + 1, d_out.p, stride, d_res.p, d_res.p + 1, st, nullptr),
-         hipGetLastError() == hipSuccess) &&
-        hipMemcpyAsync(res, d_res.p, 16, hipMemcpyDeviceToHost, st) == hipSuccess && hipStreamSynchronize(st) == hipSuccess) {
-        rc = res[0];
-        if (rc == ICX_BMP_OK) {
-            uint8_t* hostp = (uint8_t*)std::malloc(nout);
-            if (hostp && hipMemcpy(hostp, d_out.p, nout, hipMemcpyDeviceToHost) == hipSuccess) {
-                *out = hostp;
-                if (w) *w = res[1];
-                if (h) *h = res[2];
-                if (channels) *channels = res[3];
-            } else {
-                std::free(hostp);
-                ctx->err = "icx_bmp_decode: host allocation or copy failed";
-                rc = ICX_BMP_INTERNAL_ERR;
-            }
-        }
-    } else if (ctx->err.empty()) {
-        ctx->err = "icx_bmp_decode: HIP failure";
-    }
-    return rc;
+    const uint64_t nout = (uint64_t)ww * hh * dd;
+    return read_one<BmpFmt>(ctx, data, size, nout, out, {w, h, channels}, launch_direct<BmpFmt>(b->ws, nout));
 }
 
 size_t icx_bmp_encode_bound(int width, int height, int d) { return (size_t)bmp_encode_bound(width, height, d); }
@@ -1684,23 +1678,11 @@ int icx_bmp_encode_device_batch(icx_ctx* ctx, int n, const uint8_t* const* d_src
         (n > 0 && (!d_src || !widths || !heights || !d_out || !d_sizes || !d_status)))
         return ICX_BMP_INVALID_ARGUMENT;
     if (n == 0) return ICX_BMP_OK;
-    ICX_HIP(ctx, hipSetDevice(ctx->device), ICX_BMP_INTERNAL_ERR);
-    const RoctxRange range("icx_bmp_encode_device_batch");
-    std::string err;
-    int rc;
-    try {  // (nothing may cross the C ABI: a host allocation failure is an internal error)
-        if (!ctx->bmpw) ctx->bmpw = bmpw_ws_create();
-        rc = bmp_encode_batch(stream ? (hipStream_t)stream : ctx->stream, *ctx->bmpw, n, d_src, widths, heights, d,
-                              d_out, out_stride, d_sizes, d_status, err);
-    } catch (const std::exception& e) {
-        err = std::string("icx_bmp_encode_device_batch: ") + e.what();
-        rc = -1;
-    }
-    if (rc != 0) {
-        ctx->err = err.empty() ? "icx_bmp_encode_device_batch: HIP failure" : err;
-        return ICX_BMP_INTERNAL_ERR;
-    }
-    return ICX_BMP_OK;
+    return encode_batch_guarded(ctx, "icx_bmp_encode_device_batch", ctx->bmpw, bmpw_ws_create, ICX_BMP_OK,
+                                ICX_BMP_INTERNAL_ERR, [&](BmpwWs& ws, std::string& err) {
+                                    return bmp_encode_batch(stream ? (hipStream_t)stream : ctx->stream, ws, n, d_src, widths,
+                                                            heights, d, d_out, out_stride, d_sizes, d_status, err);
+                                });
 }
 
 int icx_bmp_save_to_memory(icx_ctx* ctx, const uint8_t* pixels, int width, int height, int d, uint8_t** out,
@@ -1710,35 +1692,12 @@ int icx_bmp_save_to_memory(icx_ctx* ctx, const uint8_t* pixels, int width, int h
     if (!ctx) return ICX_BMP_INTERNAL_ERR;
     const uint64_t bound = bmp_encode_bound(width, height, d);
     if (!pixels || !out || !size || bound == 0) return ICX_BMP_INVALID_ARGUMENT;
-    ICX_HIP(ctx, hipSetDevice(ctx->device), ICX_BMP_INTERNAL_ERR);
-    const uint64_t npx = (uint64_t)width * height * d;
-    Buf<uint8_t> d_px, d_file;
-    Buf<uint64_t> d_res;  // the file's size, then its status
-    uint64_t res[2] = {0, 0};
-    hipStream_t st = ctx->stream;
-    if (!(d_px.reserve(npx) && d_file.reserve(bound) && d_res.reserve(16) &&
-          hipMemcpyAsync(d_px.p, pixels, npx, hipMemcpyHostToDevice, st) == hipSuccess)) {
-        ctx->err = std::string("icx_bmp_save_to_memory: ") + hipGetErrorString(hipGetLastError());
-        return ICX_BMP_INTERNAL_ERR;
-    }
-    const uint8_t* src = d_px.p;
     const int32_t w = width, h = height;
-    const int rc = icx_bmp_encode_device_batch(ctx, 1, &src, &w, &h, d, d_file.p, bound, d_res.p,
-                                               reinterpret_cast<int32_t*>(d_res.p + 1), st);
-    if (rc != ICX_BMP_OK) return rc;
-    ICX_HIP(ctx, hipMemcpy(res, d_res.p, 16, hipMemcpyDeviceToHost), ICX_BMP_INTERNAL_ERR);
-    const int code = (int32_t)(res[1] & 0xFFFFFFFFu);
-    if (code != ICX_BMP_OK) return code;
-    uint8_t* hostp = (uint8_t*)std::malloc(res[0]);
-    if (!hostp || hipMemcpy(hostp, d_file.p, res[0], hipMemcpyDeviceToHost) != hipSuccess) {
-        std::free(hostp);
-        (void)hipGetLastError();
-        ctx->err = "icx_bmp_save_to_memory: host allocation or copy failed";
-        return ICX_BMP_INTERNAL_ERR;
-    }
-    *out = hostp;
-    *size = (size_t)res[0];
-    return ICX_BMP_OK;
+    return save_one<uint8_t>(ctx, "icx_bmp_save_to_memory", pixels, (uint64_t)width * height * d, bound, out, size, ICX_BMP_OK,
+                             ICX_BMP_INTERNAL_ERR,
+                             [&](const uint8_t* const* src, uint8_t* d_file, uint64_t* d_size, int32_t* d_status, hipStream_t st) {
+                                 return icx_bmp_encode_device_batch(ctx, 1, src, &w, &h, d, d_file, bound, d_size, d_status, st);
+                             });
 }
 
 int icx_bmp_save_to_file(icx_ctx* ctx, const char* path, const uint8_t* pixels, int width, int height, int d) {
@@ -1748,24 +1707,11 @@ int icx_bmp_save_to_file(icx_ctx* ctx, const char* path, const uint8_t* pixels, 
     size_t size = 0;
     const int rc = icx_bmp_save_to_memory(ctx, pixels, width, height, d, &mem, &size);
     if (rc != ICX_BMP_OK) return rc;
-    std::FILE* f = std::fopen(path, "wb");
-    const bool ok = f && std::fwrite(mem, 1, size, f) == size;
-    const bool closed = f && std::fclose(f) == 0;
-    std::free(mem);
-    if (!ok || !closed) {
-        ctx->err = std::string("icx_bmp_save_to_file: cannot write ") + path;
-        return ICX_BMP_INTERNAL_ERR;
-    }
-    return ICX_BMP_OK;
+    return write_file(ctx, "icx_bmp_save_to_file", path, mem, size, ICX_BMP_OK, ICX_BMP_INTERNAL_ERR);
 }
 
+
 // --------------------------------------------------------- Netpbm (Image::readPbm / writePbm)
-struct icx_pnm_batch {
-    icx_ctx* ctx = nullptr;
-    PnmWs ws;
-    Blocks mem;  // the device memory ws points into
-    std::unique_ptr<EventHook> hook;
-};
 
 static int pnm_probe_at(const uint8_t* data, size_t size, int* w, int* h, int* d, int* type, int* maxval, int64_t* raster_at) {
     int v[5] = {0, 0, 0, 0, 0};
@@ -1782,119 +1728,48 @@ int icx_pnm_probe(const uint8_t* data, size_t size, int* w, int* h, int* channel
     return pnm_probe_at(data, size, w, h, channels, type, maxval, nullptr);
 }
 
-// tiles_cap: tiles of raster text per image (0: a workspace for binary files only).
-static icx_pnm_batch* pnm_batch_new(icx_ctx* ctx, int max_images, int max_w, int max_h, int64_t tiles_cap) {
-    // (images are one grid dimension)
-    if (!ctx || max_images <= 0 || max_images > 65535 || max_w <= 0 || max_h <= 0 ||
-        (int64_t)max_w * max_h > ((int64_t)1 << 30)) {
-        if (ctx) ctx->err = "icx_pnm_batch_create: bad arguments";
-        return nullptr;
-    }
-    ICX_HIP(ctx, hipSetDevice(ctx->device), nullptr);
-    auto* b = new icx_pnm_batch();
-    b->ctx = ctx;
-    b->hook = std::make_unique<EventHook>();
-    if (!pnm_ws_alloc(b->ws, b->mem, max_images, max_w, max_h, tiles_cap)) {
-        ctx->err = std::string("icx_pnm_batch_create: out of device memory: ") + hipGetErrorString(hipGetLastError());
-        delete b;
-        return nullptr;
-    }
-    return b;
-}
-
 icx_pnm_batch* icx_pnm_batch_create(icx_ctx* ctx, int max_images, int max_w, int max_h) {
-    if (max_w <= 0 || max_h <= 0) return pnm_batch_new(ctx, max_images, max_w, max_h, 0);  // (refused there)
-    return pnm_batch_new(ctx, max_images, max_w, max_h, pnm_default_tiles(max_w, max_h));
+    if (max_w <= 0 || max_h <= 0) return read_batch_new<PnmFmt>(ctx, max_images, max_w, max_h, (int64_t)0);  // (refused there)
+    return read_batch_new<PnmFmt>(ctx, max_images, max_w, max_h, pnm_default_tiles(max_w, max_h));
 }
 
-void icx_pnm_batch_destroy(icx_pnm_batch* b) {
-    if (!b) return;
-    (void)hipSetDevice(b->ctx->device);
-    delete b;
-}
+void icx_pnm_batch_destroy(icx_pnm_batch* b) { read_batch_destroy(b); }
 
 int icx_pnm_batch_decode(icx_pnm_batch* b, int n, const uint8_t* d_data, const uint64_t* d_off, const uint64_t* d_size,
                          void* d_out, uint64_t out_stride, int32_t* d_status, int32_t* d_dims, void* stream) {
-    if (!b) return ICX_PNM_INTERNAL_ERR;
-    icx_ctx* ctx = b->ctx;
-    if (n < 0 || n > b->ws.max_images) { ctx->err = "icx_pnm_batch_decode: n exceeds batch capacity"; return ICX_PNM_INTERNAL_ERR; }
-    if (n == 0) return ICX_PNM_OK;
-    if (!d_data || !d_off || !d_size || !d_out || !d_status || !d_dims) { ctx->err = "null pointer"; return ICX_PNM_INTERNAL_ERR; }
-    if ((reinterpret_cast<uintptr_t>(d_out) & 15) || (out_stride & 15)) return ICX_PNM_INVALID_ARGUMENT;
-    ICX_HIP(ctx, hipSetDevice(ctx->device), ICX_PNM_INTERNAL_ERR);
-    hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
-    const RoctxRange range("icx_pnm_batch_decode");
-    b->hook->reset();
-    launch_pnm_decode(b->ws, n, d_data, d_off, d_size, static_cast<uint8_t*>(d_out), out_stride, d_status, d_dims, st,
-                      b->hook.get());
-    ICX_HIP(ctx, hipGetLastError(), ICX_PNM_INTERNAL_ERR);
-    return ICX_PNM_OK;
+    return read_batch_decode<PnmFmt>(b, n, d_data, d_off, d_size, d_out, out_stride, d_status, d_dims, stream);
 }
 
 int icx_pnm_batch_stage_times(const icx_pnm_batch* b, const char** names, float* ms, int cap) {
-    if (!b) return 0;
-    static const Stage order[4] = {kStParse, kStUnstuff, kStEntropy, kStConvert};
-    static const char* const label[4] = {"parse", "locate", "text", "stream"};
-    float acc[kStCount];
-    b->hook->sum(acc);
-    for (int k = 0; k < 4 && k < cap; ++k) {
-        if (names) names[k] = label[k];
-        if (ms) ms[k] = acc[order[k]];
-    }
-    return 4;
+    return b ? read_stage_times(*b->hook, PnmFmt::kOrder, PnmFmt::kLabel, names, ms, cap) : 0;
 }
 
+// (the two halves of read_one with a tail of its own: a six-int record, a slot rounded up to 16
+// bytes, and messages that say more)
 int icx_pnm_decode(icx_ctx* ctx, const uint8_t* data, size_t size, void** out, int* w, int* h, int* channels, int* type,
                    int* maxval) {
     if (out) *out = nullptr;
-    int* const res_out[5] = {w, h, channels, type, maxval};
-    for (int* p : res_out)
-        if (p) *p = 0;
+    zero_out({w, h, channels, type, maxval});
     if (!ctx || !out) return ICX_PNM_INTERNAL_ERR;
     int ww = 0, hh = 0, dd = 0, tt = 0, mv = 0;
     int64_t raster_at = -1;
     const int prc = pnm_probe_at(data, size, &ww, &hh, &dd, &tt, &mv, &raster_at);
     if (prc != ICX_PNM_OK) return prc;  // header errors and a short binary raster need no device work
     ICX_HIP(ctx, hipSetDevice(ctx->device), ICX_PNM_INTERNAL_ERR);
-    // (declared before the buffers: they are freed first, then the batch)
     // (a text file gets a tile for every kPnmTile bytes of its text: nothing is TOO_LARGE here)
     const int64_t tiles = raster_at >= 0 ? ((int64_t)size - raster_at + kPnmTile - 1) / kPnmTile + 1 : 0;
-    std::unique_ptr<icx_pnm_batch, void (*)(icx_pnm_batch*)> b(pnm_batch_new(ctx, 1, ww, hh, tiles), icx_pnm_batch_destroy);
+    std::unique_ptr<icx_pnm_batch, void (*)(icx_pnm_batch*)> b(read_batch_new<PnmFmt>(ctx, 1, ww, hh, tiles),
+                                                               icx_pnm_batch_destroy);
     if (!b) return ICX_PNM_INTERNAL_ERR;
     const uint64_t nout = (uint64_t)ww * hh * dd * pnm_elem_bytes(tt), stride = (nout + 15) & ~(uint64_t)15;
-    Buf<uint8_t> d_in, d_out;
-    Buf<uint64_t> d_meta;
-    Buf<int32_t> d_res;
-    int rc = ICX_PNM_INTERNAL_ERR;
-    const uint64_t meta[2] = {0, (uint64_t)size};
-    int32_t res[6] = {0, 0, 0, 0, 0, 0};
-    hipStream_t st = ctx->stream;
-    if (d_in.reserve(size) && d_out.reserve(stride) && d_meta.reserve(16) && d_res.reserve(sizeof res) &&
-        hipMemcpyAsync(d_in.p, data, size, hipMemcpyHostToDevice, st) == hipSuccess &&
-        hipMemcpyAsync(d_meta.p, meta, 16, hipMemcpyHostToDevice, st) == hipSuccess &&
-        (launch_pnm_decode(b->ws, 1, d_in.p, d_meta.p, d_meta.p + 1, d_out.p, stride, d_res.p, d_res.p + 1, st, nullptr),
-         hipGetLastError() == hipSuccess) &&
-        hipMemcpyAsync(res, d_res.p, sizeof res, hipMemcpyDeviceToHost, st) == hipSuccess && hipStreamSynchronize(st) == hipSuccess) {
-        rc = res[0];
-        if (rc == ICX_PNM_OK) {
-            uint8_t* hostp = (uint8_t*)std::malloc(nout);
-            if (hostp && hipMemcpy(hostp, d_out.p, nout, hipMemcpyDeviceToHost) == hipSuccess) {
-                *out = hostp;
-                for (int k = 0; k < 5; ++k)
-                    if (res_out[k]) *res_out[k] = res[1 + k];
-            } else {
-                std::free(hostp);
-                ctx->err = "icx_pnm_decode: host allocation or copy failed";
-                rc = ICX_PNM_INTERNAL_ERR;
-            }
-        } else if (rc == ICX_PNM_INTERNAL_ERR) {
-            ctx->err = "icx_pnm_decode: the text kernels left no verdict";
-        }
-    } else {
+    OneShot io;
+    if (!one_shot_run(ctx, io, data, size, size, stride, 6, launch_direct<PnmFmt>(b->ws, stride))) {
         const hipError_t e = hipGetLastError();
         ctx->err = std::string("icx_pnm_decode: HIP failure: ") + hipGetErrorString(e);
+        return ICX_PNM_INTERNAL_ERR;
     }
-    return rc;
+    if (io.rec[0] == ICX_PNM_INTERNAL_ERR) ctx->err = "icx_pnm_decode: the text kernels left no verdict";
+    return io.rec[0] == ICX_PNM_OK ? one_shot_take<PnmFmt>(ctx, io, nout, out, {w, h, channels, type, maxval}) : io.rec[0];
 }
 
 size_t icx_pnm_encode_bound(int width, int height, int d, int type, int format) {
@@ -1910,24 +1785,12 @@ int icx_pnm_encode_device_batch(icx_ctx* ctx, int n, const void* const* d_src, c
         (n > 0 && (!d_src || !widths || !heights || !d_out || !d_sizes || !d_status)))
         return ICX_PNM_INVALID_ARGUMENT;
     if (n == 0) return ICX_PNM_OK;
-    ICX_HIP(ctx, hipSetDevice(ctx->device), ICX_PNM_INTERNAL_ERR);
-    const RoctxRange range("icx_pnm_encode_device_batch");
-    std::string err;
-    int rc;
-    try {  // (nothing may cross the C ABI: a host allocation failure is an internal error)
-        if (!ctx->pnmw) ctx->pnmw = pnmw_ws_create();
-        rc = pnm_encode_batch(stream ? (hipStream_t)stream : ctx->stream, *ctx->pnmw, n,
-                              reinterpret_cast<const uint8_t* const*>(d_src), widths, heights, d, type, format, d_out,
-                              out_stride, d_sizes, d_status, err);
-    } catch (const std::exception& e) {
-        err = std::string("icx_pnm_encode_device_batch: ") + e.what();
-        rc = -1;
-    }
-    if (rc != 0) {
-        ctx->err = err.empty() ? "icx_pnm_encode_device_batch: HIP failure" : err;
-        return ICX_PNM_INTERNAL_ERR;
-    }
-    return ICX_PNM_OK;
+    return encode_batch_guarded(ctx, "icx_pnm_encode_device_batch", ctx->pnmw, pnmw_ws_create, ICX_PNM_OK,
+                                ICX_PNM_INTERNAL_ERR, [&](PnmwWs& ws, std::string& err) {
+                                    return pnm_encode_batch(stream ? (hipStream_t)stream : ctx->stream, ws, n,
+                                                            reinterpret_cast<const uint8_t* const*>(d_src), widths, heights, d,
+                                                            type, format, d_out, out_stride, d_sizes, d_status, err);
+                                });
 }
 
 int icx_pnm_save_to_memory(icx_ctx* ctx, const void* pixels, int width, int height, int d, int type, int format,
@@ -1937,35 +1800,13 @@ int icx_pnm_save_to_memory(icx_ctx* ctx, const void* pixels, int width, int heig
     if (!ctx) return ICX_PNM_INTERNAL_ERR;
     const uint64_t bound = pnm_encode_bound(width, height, d, type, format);
     if (!pixels || !out || !size || bound == 0) return ICX_PNM_INVALID_ARGUMENT;
-    ICX_HIP(ctx, hipSetDevice(ctx->device), ICX_PNM_INTERNAL_ERR);
-    const uint64_t npx = (uint64_t)width * height * d * pnm_elem_bytes(type);
-    Buf<uint8_t> d_px, d_file;
-    Buf<uint64_t> d_res;  // the file's size, then its status
-    uint64_t res[2] = {0, 0};
-    hipStream_t st = ctx->stream;
-    if (!(d_px.reserve(npx) && d_file.reserve(bound) && d_res.reserve(16) &&
-          hipMemcpyAsync(d_px.p, pixels, npx, hipMemcpyHostToDevice, st) == hipSuccess)) {
-        ctx->err = std::string("icx_pnm_save_to_memory: ") + hipGetErrorString(hipGetLastError());
-        return ICX_PNM_INTERNAL_ERR;
-    }
-    const void* src = d_px.p;
     const int32_t w = width, h = height;
-    const int rc = icx_pnm_encode_device_batch(ctx, 1, &src, &w, &h, d, type, format, d_file.p, bound, d_res.p,
-                                               reinterpret_cast<int32_t*>(d_res.p + 1), st);
-    if (rc != ICX_PNM_OK) return rc;
-    ICX_HIP(ctx, hipMemcpy(res, d_res.p, 16, hipMemcpyDeviceToHost), ICX_PNM_INTERNAL_ERR);
-    const int code = (int32_t)(res[1] & 0xFFFFFFFFu);
-    if (code != ICX_PNM_OK) return code;
-    uint8_t* hostp = (uint8_t*)std::malloc(res[0]);
-    if (!hostp || hipMemcpy(hostp, d_file.p, res[0], hipMemcpyDeviceToHost) != hipSuccess) {
-        std::free(hostp);
-        (void)hipGetLastError();
-        ctx->err = "icx_pnm_save_to_memory: host allocation or copy failed";
-        return ICX_PNM_INTERNAL_ERR;
-    }
-    *out = hostp;
-    *size = (size_t)res[0];
-    return ICX_PNM_OK;
+    return save_one<uint8_t>(ctx, "icx_pnm_save_to_memory", pixels, (uint64_t)width * height * d * pnm_elem_bytes(type), bound,
+                             out, size, ICX_PNM_OK, ICX_PNM_INTERNAL_ERR,
+                             [&](const uint8_t* const* src, uint8_t* d_file, uint64_t* d_size, int32_t* d_status, hipStream_t st) {
+                                 return icx_pnm_encode_device_batch(ctx, 1, reinterpret_cast<const void* const*>(src), &w, &h, d,
+                                                                    type, format, d_file, bound, d_size, d_status, st);
+                             });
 }
 
 int icx_pnm_save_to_file(icx_ctx* ctx, const char* path, const void* pixels, int width, int height, int d, int type,
@@ -1976,20 +1817,13 @@ int icx_pnm_save_to_file(icx_ctx* ctx, const char* path, const void* pixels, int
     size_t size = 0;
     const int rc = icx_pnm_save_to_memory(ctx, pixels, width, height, d, type, format, &mem, &size);
     if (rc != ICX_PNM_OK) return rc;
-    std::FILE* f = std::fopen(path, "wb");
-    const bool ok = f && std::fwrite(mem, 1, size, f) == size;
-    const bool closed = f && std::fclose(f) == 0;
-    std::free(mem);
-    if (!ok || !closed) {
-        ctx->err = std::string("icx_pnm_save_to_file: cannot write ") + path;
-        return ICX_PNM_INTERNAL_ERR;
-    }
-    return ICX_PNM_OK;
+    return write_file(ctx, "icx_pnm_save_to_file", path, mem, size, ICX_PNM_OK, ICX_PNM_INTERNAL_ERR);
 }
 
 // --------------------------------------------------------- Radiance .hdr write (Image::writeHdr)
 size_t icx_hdr_encode_bound(int width, int height, int d, int rle) { return (size_t)hdrw_encode_bound(width, height, d, rle); }
 
+// (the arguments are checked before the context here, unlike the byte writers)
 int icx_hdr_encode_device_batch(icx_ctx* ctx, int n, const float* const* d_src, const int32_t* widths,
                                 const int32_t* heights, int d, int rle, uint8_t* d_out, uint64_t out_stride,
                                 uint64_t* d_sizes, int32_t* d_status, void* stream) {
@@ -1998,23 +1832,11 @@ int icx_hdr_encode_device_batch(icx_ctx* ctx, int n, const float* const* d_src, 
         return ICX_HDR_INVALID_ARGUMENT;
     if (!ctx) return ICX_HDR_INTERNAL_ERR;
     if (n == 0) return ICX_HDR_OK;
-    ICX_HIP(ctx, hipSetDevice(ctx->device), ICX_HDR_INTERNAL_ERR);
-    const RoctxRange range("icx_hdr_encode_device_batch");
-    std::string err;
-    int rc;
-    try {  // (nothing may cross the C ABI: a host allocation failure is an internal error)
-        if (!ctx->hdrw) ctx->hdrw = hdrw_ws_create();
-        rc = hdr_encode_batch(stream ? (hipStream_t)stream : ctx->stream, *ctx->hdrw, n, d_src, widths, heights, d,
-                              rle != 0, d_out, out_stride, d_sizes, d_status, err);
-    } catch (const std::exception& e) {
-        err = std::string("icx_hdr_encode_device_batch: ") + e.what();
-        rc = -1;
-    }
-    if (rc != 0) {
-        ctx->err = err.empty() ? "icx_hdr_encode_device_batch: HIP failure" : err;
-        return ICX_HDR_INTERNAL_ERR;
-    }
-    return ICX_HDR_OK;
+    return encode_batch_guarded(ctx, "icx_hdr_encode_device_batch", ctx->hdrw, hdrw_ws_create, ICX_HDR_OK,
+                                ICX_HDR_INTERNAL_ERR, [&](HdrwWs& ws, std::string& err) {
+                                    return hdr_encode_batch(stream ? (hipStream_t)stream : ctx->stream, ws, n, d_src, widths,
+                                                            heights, d, rle != 0, d_out, out_stride, d_sizes, d_status, err);
+                                });
 }
 
 int icx_hdr_save_to_memory(icx_ctx* ctx, const float* pixels, int width, int height, int d, int rle, uint8_t** out,
@@ -2024,36 +1846,12 @@ int icx_hdr_save_to_memory(icx_ctx* ctx, const float* pixels, int width, int hei
     const uint64_t bound = hdrw_encode_bound(width, height, d, rle);
     if (!pixels || !out || !size || bound == 0) return ICX_HDR_INVALID_ARGUMENT;  // (before any device work)
     if (!ctx) return ICX_HDR_INTERNAL_ERR;
-    ICX_HIP(ctx, hipSetDevice(ctx->device), ICX_HDR_INTERNAL_ERR);
-    const uint64_t nbytes = (uint64_t)width * height * d * sizeof(float);
-    Buf<float> d_px;
-    Buf<uint8_t> d_file;
-    Buf<uint64_t> d_res;  // the file's size, then its status
-    uint64_t res[2] = {0, 0};
-    hipStream_t st = ctx->stream;
-    if (!(d_px.reserve(nbytes) && d_file.reserve(bound) && d_res.reserve(16) &&
-          hipMemcpyAsync(d_px.p, pixels, nbytes, hipMemcpyHostToDevice, st) == hipSuccess)) {
-        ctx->err = std::string("icx_hdr_save_to_memory: ") + hipGetErrorString(hipGetLastError());
-        return ICX_HDR_INTERNAL_ERR;
-    }
-    const float* src = d_px.p;
     const int32_t w = width, h = height;
-    const int rc = icx_hdr_encode_device_batch(ctx, 1, &src, &w, &h, d, rle, d_file.p, bound, d_res.p,
-                                               reinterpret_cast<int32_t*>(d_res.p + 1), st);
-    if (rc != ICX_HDR_OK) return rc;
-    ICX_HIP(ctx, hipMemcpy(res, d_res.p, 16, hipMemcpyDeviceToHost), ICX_HDR_INTERNAL_ERR);
-    const int code = (int32_t)(res[1] & 0xFFFFFFFFu);
-    if (code != ICX_HDR_OK) return code;
-    uint8_t* hostp = (uint8_t*)std::malloc(res[0]);
-    if (!hostp || hipMemcpy(hostp, d_file.p, res[0], hipMemcpyDeviceToHost) != hipSuccess) {
-        std::free(hostp);
-        (void)hipGetLastError();
-        ctx->err = "icx_hdr_save_to_memory: host allocation or copy failed";
-        return ICX_HDR_INTERNAL_ERR;
-    }
-    *out = hostp;
-    *size = (size_t)res[0];
-    return ICX_HDR_OK;
+    return save_one<float>(ctx, "icx_hdr_save_to_memory", pixels, (uint64_t)width * height * d * sizeof(float), bound, out, size,
+                           ICX_HDR_OK, ICX_HDR_INTERNAL_ERR,
+                           [&](const float* const* src, uint8_t* d_file, uint64_t* d_size, int32_t* d_status, hipStream_t st) {
+                               return icx_hdr_encode_device_batch(ctx, 1, src, &w, &h, d, rle, d_file, bound, d_size, d_status, st);
+                           });
 }
 
 int icx_hdr_save_to_file(icx_ctx* ctx, const char* path, const float* pixels, int width, int height, int d, int rle) {
@@ -2062,252 +1860,81 @@ int icx_hdr_save_to_file(icx_ctx* ctx, const char* path, const float* pixels, in
     size_t size = 0;
     const int rc = icx_hdr_save_to_memory(ctx, pixels, width, height, d, rle, &mem, &size);
     if (rc != ICX_HDR_OK) return rc;
-    std::FILE* f = std::fopen(path, "wb");
-    const bool ok = f && std::fwrite(mem, 1, size, f) == size;
-    const bool closed = f && std::fclose(f) == 0;
-    std::free(mem);
-    if (!ok || !closed) {
-        ctx->err = std::string("icx_hdr_save_to_file: cannot write ") + path;
-        return ICX_HDR_INTERNAL_ERR;
-    }
-    return ICX_HDR_OK;
+    return write_file(ctx, "icx_hdr_save_to_file", path, mem, size, ICX_HDR_OK, ICX_HDR_INTERNAL_ERR);
 }
 
 // --------------------------------------------------------- GIF (Image::readGif)
-struct icx_gif_batch {
-    icx_ctx* ctx = nullptr;
-    GifWs ws;
-    Blocks mem;  // the device memory ws points into
-    std::unique_ptr<EventHook> hook;
-};
-
 int icx_gif_probe(const uint8_t* data, size_t size, int* w, int* h) {
     int ww = 0, hh = 0;
     const int rc = data ? gif_probe(data, (int64_t)size, &ww, &hh) : ICX_GIF_BAD_HEADER;
-    if (w) *w = rc == ICX_GIF_OK ? ww : 0;
-    if (h) *h = rc == ICX_GIF_OK ? hh : 0;
-    return rc;
+    return probe_out(rc, ICX_GIF_OK, w, ww, h, hh);
 }
 
 icx_gif_batch* icx_gif_batch_create(icx_ctx* ctx, int max_images, int max_w, int max_h) {
-    // (images are one grid dimension; pixel indices are 32-bit in the index plane)
-    if (!ctx || max_images <= 0 || max_images > 65535 || max_w <= 0 || max_h <= 0 || max_w > 65535 || max_h > 65535 ||
-        (int64_t)max_w * max_h > ((int64_t)1 << 30)) {
-        if (ctx) ctx->err = "icx_gif_batch_create: bad arguments";
-        return nullptr;
-    }
-    ICX_HIP(ctx, hipSetDevice(ctx->device), nullptr);
-    auto* b = new icx_gif_batch();
-    b->ctx = ctx;
-    b->hook = std::make_unique<EventHook>();
-    if (!gif_ws_alloc(b->ws, b->mem, max_images, max_w, max_h)) {
-        ctx->err = std::string("icx_gif_batch_create: out of device memory: ") + hipGetErrorString(hipGetLastError());
-        delete b;
-        return nullptr;
-    }
-    return b;
+    return read_batch_new<GifFmt>(ctx, max_images, max_w, max_h);
 }
 
-void icx_gif_batch_destroy(icx_gif_batch* b) {
-    if (!b) return;
-    (void)hipSetDevice(b->ctx->device);
-    delete b;
-}
+void icx_gif_batch_destroy(icx_gif_batch* b) { read_batch_destroy(b); }
 
 int icx_gif_batch_decode(icx_gif_batch* b, int n, const uint8_t* d_data, const uint64_t* d_off, const uint64_t* d_size,
                          uint8_t* d_out, uint64_t out_stride, int32_t* d_status, int32_t* d_dims, void* stream) {
-    if (!b) return ICX_GIF_INTERNAL_ERR;
-    icx_ctx* ctx = b->ctx;
-    if (n < 0 || n > b->ws.max_images) { ctx->err = "icx_gif_batch_decode: n exceeds batch capacity"; return ICX_GIF_INTERNAL_ERR; }
-    if (n == 0) return ICX_GIF_OK;
-    if (!d_data || !d_off || !d_size || !d_out || !d_status || !d_dims) { ctx->err = "null pointer"; return ICX_GIF_INTERNAL_ERR; }
-    if (out_stride < 3ull * b->ws.max_w * b->ws.max_h) { ctx->err = "icx_gif_batch_decode: out_stride too small"; return ICX_GIF_INTERNAL_ERR; }
-    ICX_HIP(ctx, hipSetDevice(ctx->device), ICX_GIF_INTERNAL_ERR);
-    hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
-    const RoctxRange range("icx_gif_batch_decode");
-    b->hook->reset();
-    launch_gif_decode(b->ws, n, d_data, d_off, d_size, d_out, out_stride, d_status, d_dims, st, b->hook.get());
-    ICX_HIP(ctx, hipGetLastError(), ICX_GIF_INTERNAL_ERR);
-    return ICX_GIF_OK;
+    return read_batch_decode<GifFmt>(b, n, d_data, d_off, d_size, d_out, out_stride, d_status, d_dims, stream);
 }
 
 int icx_gif_batch_stage_times(const icx_gif_batch* b, const char** names, float* ms, int cap) {
-    if (!b) return 0;
-    static const Stage order[3] = {kStParse, kStEntropy, kStConvert};
-    static const char* const label[3] = {"parse", "lzw", "render"};
-    float acc[kStCount];
-    b->hook->sum(acc);
-    for (int k = 0; k < 3 && k < cap; ++k) {
-        if (names) names[k] = label[k];
-        if (ms) ms[k] = acc[order[k]];
-    }
-    return 3;
+    return b ? read_stage_times(*b->hook, GifFmt::kOrder, GifFmt::kLabel, names, ms, cap) : 0;
 }
 
 int icx_gif_decode(icx_ctx* ctx, const uint8_t* data, size_t size, uint8_t** out, int* w, int* h) {
     if (out) *out = nullptr;
-    if (w) *w = 0;
-    if (h) *h = 0;
+    zero_out({w, h});
     if (!ctx || !out) return ICX_GIF_INTERNAL_ERR;
     int ww = 0, hh = 0;
     const int prc = icx_gif_probe(data, size, &ww, &hh);
     if (prc != ICX_GIF_OK) return prc;  // container errors need no device work
     if ((int64_t)ww * hh > ((int64_t)1 << 30)) return ICX_GIF_TOO_LARGE;  // (no batch workspace is that large)
     ICX_HIP(ctx, hipSetDevice(ctx->device), ICX_GIF_INTERNAL_ERR);
-    // (declared before the buffers: they are freed first, then the batch)
     std::unique_ptr<icx_gif_batch, void (*)(icx_gif_batch*)> b(icx_gif_batch_create(ctx, 1, ww, hh), icx_gif_batch_destroy);
     if (!b) return ICX_GIF_INTERNAL_ERR;
-    const uint64_t nout = (uint64_t)ww * hh * 3, stride = nout;
-    Buf<uint8_t> d_in, d_out;
-    Buf<uint64_t> d_meta;
-    Buf<int32_t> d_res;
-    int rc = ICX_GIF_INTERNAL_ERR;
-    const uint64_t meta[2] = {0, (uint64_t)size};
-    int32_t res[4] = {0, 0, 0, 0};
-    hipStream_t st = ctx->stream;
-    if (d_in.reserve(size) && d_out.reserve(stride) && d_meta.reserve(16) && d_res.reserve(16) &&
-        hipMemcpyAsync(d_in.p, data, size, hipMemcpyHostToDevice, st) == hipSuccess &&
-        hipMemcpyAsync(d_meta.p, meta, 16, hipMemcpyHostToDevice, st) == hipSuccess &&
-        (launch_gif_decode(b->ws, 1, d_in.p, d_meta.p, d_meta.p + 1, d_out.p, stride, d_res.p, d_res.p + 1, st, nullptr),
-         hipGetLastError() == hipSuccess) &&
-        hipMemcpyAsync(res, d_res.p, 16, hipMemcpyDeviceToHost, st) == hipSuccess && hipStreamSynchronize(st) == hipSuccess) {
-        rc = res[0];
-        if (rc == ICX_GIF_OK) {
-            uint8_t* hostp = (uint8_t*)std::malloc(nout);
-            if (hostp && hipMemcpy(hostp, d_out.p, nout, hipMemcpyDeviceToHost) == hipSuccess) {
-                *out = hostp;
-                if (w) *w = res[1];
-                if (h) *h = res[2];
-            } else {
-                std::free(hostp);
-                ctx->err = "icx_gif_decode: host allocation or copy failed";
-                rc = ICX_GIF_INTERNAL_ERR;
-            }
-        }
-    } else if (ctx->err.empty()) {
-        ctx->err = "icx_gif_decode: HIP failure";
-    }
-    return rc;
+    const uint64_t nout = (uint64_t)ww * hh * 3;
+    return read_one<GifFmt>(ctx, data, size, nout, out, {w, h}, launch_direct<GifFmt>(b->ws, nout));
 }
 
 // --------------------------------------------------------- TIFF (Image::readTiff)
-struct icx_tiff_batch {
-    icx_ctx* ctx = nullptr;
-    TiffWs ws;
-    Blocks mem;  // the device memory ws points into
-    std::unique_ptr<EventHook> hook;
-};
-
 int icx_tiff_probe(const uint8_t* data, size_t size, int* w, int* h, int* d) {
     int ww = 0, hh = 0, dd = 0, pw = 0, ph = 0;
     const int rc = data ? tiff_probe(data, (int64_t)size, &ww, &hh, &dd, &pw, &ph) : ICX_TIFF_NOT_TIFF;
-    if (w) *w = rc == ICX_TIFF_OK ? ww : 0;
-    if (h) *h = rc == ICX_TIFF_OK ? hh : 0;
-    if (d) *d = rc == ICX_TIFF_OK ? dd : 0;
-    return rc;
+    return probe_out(rc, ICX_TIFF_OK, w, ww, h, hh, d, dd);
 }
 
 icx_tiff_batch* icx_tiff_batch_create(icx_ctx* ctx, int max_images, int max_w, int max_h) {
-    // (images are one grid dimension; byte positions inside a chunk are 32-bit)
-    if (!ctx || max_images <= 0 || max_images > 65535 || max_w <= 0 || max_h <= 0 ||
-        (int64_t)max_w * max_h > ((int64_t)1 << 30)) {
-        if (ctx) ctx->err = "icx_tiff_batch_create: bad arguments";
-        return nullptr;
-    }
-    ICX_HIP(ctx, hipSetDevice(ctx->device), nullptr);
-    auto* b = new icx_tiff_batch();
-    b->ctx = ctx;
-    b->hook = std::make_unique<EventHook>();
-    if (!tiff_ws_alloc(b->ws, b->mem, ctx->device, max_images, max_w, max_h)) {
-        ctx->err = std::string("icx_tiff_batch_create: out of device memory: ") + hipGetErrorString(hipGetLastError());
-        delete b;
-        return nullptr;
-    }
-    return b;
+    return read_batch_new<TiffFmt>(ctx, max_images, max_w, max_h);
 }
 
-void icx_tiff_batch_destroy(icx_tiff_batch* b) {
-    if (!b) return;
-    (void)hipSetDevice(b->ctx->device);
-    delete b;
-}
+void icx_tiff_batch_destroy(icx_tiff_batch* b) { read_batch_destroy(b); }
 
 int icx_tiff_batch_decode(icx_tiff_batch* b, int n, const uint8_t* d_data, const uint64_t* d_off, const uint64_t* d_size,
-                         uint8_t* d_out, uint64_t out_stride, int32_t* d_status, int32_t* d_dims, void* stream) {
-    if (!b) return ICX_TIFF_INTERNAL_ERR;
-    icx_ctx* ctx = b->ctx;
-    if (n < 0 || n > b->ws.max_images) { ctx->err = "icx_tiff_batch_decode: n exceeds batch capacity"; return ICX_TIFF_INTERNAL_ERR; }
-    if (n == 0) return ICX_TIFF_OK;
-    if (!d_data || !d_off || !d_size || !d_out || !d_status || !d_dims) { ctx->err = "null pointer"; return ICX_TIFF_INTERNAL_ERR; }
-    if (out_stride < 4ull * b->ws.max_w * b->ws.max_h) { ctx->err = "icx_tiff_batch_decode: out_stride too small"; return ICX_TIFF_INTERNAL_ERR; }
-    ICX_HIP(ctx, hipSetDevice(ctx->device), ICX_TIFF_INTERNAL_ERR);
-    hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
-    const RoctxRange range("icx_tiff_batch_decode");
-    b->hook->reset();
-    launch_tiff_decode(b->ws, n, d_data, d_off, d_size, d_out, out_stride, d_status, d_dims, st, b->hook.get());
-    ICX_HIP(ctx, hipGetLastError(), ICX_TIFF_INTERNAL_ERR);
-    return ICX_TIFF_OK;
+                          uint8_t* d_out, uint64_t out_stride, int32_t* d_status, int32_t* d_dims, void* stream) {
+    return read_batch_decode<TiffFmt>(b, n, d_data, d_off, d_size, d_out, out_stride, d_status, d_dims, stream);
 }
 
 int icx_tiff_batch_stage_times(const icx_tiff_batch* b, const char** names, float* ms, int cap) {
-    if (!b) return 0;
-    static const Stage order[3] = {kStParse, kStEntropy, kStConvert};
-    static const char* const label[3] = {"parse", "unpack", "render"};
-    float acc[kStCount];
-    b->hook->sum(acc);
-    for (int k = 0; k < 3 && k < cap; ++k) {
-        if (names) names[k] = label[k];
-        if (ms) ms[k] = acc[order[k]];
-    }
-    return 3;
+    return b ? read_stage_times(*b->hook, TiffFmt::kOrder, TiffFmt::kLabel, names, ms, cap) : 0;
 }
 
 int icx_tiff_decode(icx_ctx* ctx, const uint8_t* data, size_t size, uint8_t** out, int* w, int* h, int* d) {
     if (out) *out = nullptr;
-    if (w) *w = 0;
-    if (h) *h = 0;
-    if (d) *d = 0;
+    zero_out({w, h, d});
     if (!ctx || !out) return ICX_TIFF_INTERNAL_ERR;
     int ww = 0, hh = 0, dd = 0, pw = 0, ph = 0;
     const int prc = data ? tiff_probe(data, (int64_t)size, &ww, &hh, &dd, &pw, &ph) : ICX_TIFF_NOT_TIFF;
     if (prc != ICX_TIFF_OK) return prc;  // container errors need no device work
     ICX_HIP(ctx, hipSetDevice(ctx->device), ICX_TIFF_INTERNAL_ERR);
     // a workspace for the size padded to whole chunks: every file the walk accepts fits its scratch
-    // (declared before the buffers: they are freed first, then the batch)
     std::unique_ptr<icx_tiff_batch, void (*)(icx_tiff_batch*)> b(icx_tiff_batch_create(ctx, 1, pw, ph), icx_tiff_batch_destroy);
     if (!b) return ICX_TIFF_INTERNAL_ERR;
-    const uint64_t nout = (uint64_t)ww * hh * dd, stride = nout;
-    Buf<uint8_t> d_in, d_out;
-    Buf<uint64_t> d_meta;
-    Buf<int32_t> d_res;
-    int rc = ICX_TIFF_INTERNAL_ERR;
-    const uint64_t meta[2] = {0, (uint64_t)size};
-    int32_t res[4] = {0, 0, 0, 0};
-    hipStream_t st = ctx->stream;
-    if (d_in.reserve(size) && d_out.reserve(stride) && d_meta.reserve(16) && d_res.reserve(16) &&
-        hipMemcpyAsync(d_in.p, data, size, hipMemcpyHostToDevice, st) == hipSuccess &&
-        hipMemcpyAsync(d_meta.p, meta, 16, hipMemcpyHostToDevice, st) == hipSuccess &&
-        (launch_tiff_decode(b->ws, 1, d_in.p, d_meta.p, d_meta.p + 1, d_out.p, stride, d_res.p, d_res.p + 1, st, nullptr),
-         hipGetLastError() == hipSuccess) &&
-        hipMemcpyAsync(res, d_res.p, 16, hipMemcpyDeviceToHost, st) == hipSuccess && hipStreamSynchronize(st) == hipSuccess) {
-        rc = res[0];
-        if (rc == ICX_TIFF_OK) {
-            uint8_t* hostp = (uint8_t*)std::malloc(nout);
-            if (hostp && hipMemcpy(hostp, d_out.p, nout, hipMemcpyDeviceToHost) == hipSuccess) {
-                *out = hostp;
-                if (w) *w = res[1];
-                if (h) *h = res[2];
-                if (d) *d = res[3];
-            } else {
-                std::free(hostp);
-                ctx->err = "icx_tiff_decode: host allocation or copy failed";
-                rc = ICX_TIFF_INTERNAL_ERR;
-            }
-        }
-    } else if (ctx->err.empty()) {
-        ctx->err = "icx_tiff_decode: HIP failure";
-    }
-    return rc;
+    const uint64_t nout = (uint64_t)ww * hh * dd;
+    return read_one<TiffFmt>(ctx, data, size, nout, out, {w, h, d}, launch_direct<TiffFmt>(b->ws, nout));
 }
 
 }  // extern "C"

@@ -201,6 +201,16 @@ inline std::string lower_ext(const std::string& path) {
     for (auto& c : e) c = (char)std::tolower((unsigned char)c);
     return e;
 }
+// The file's bytes; false (and none) when it cannot be opened.
+inline bool read_file(const std::string& path, std::vector<uint8_t>& buf) {
+    std::FILE* f = std::fopen(path.c_str(), "rb");
+    if (!f) return false;
+    uint8_t chunk[1 << 16];
+    size_t k;
+    while ((k = std::fread(chunk, 1, sizeof chunk, f)) > 0) buf.insert(buf.end(), chunk, chunk + k);
+    std::fclose(f);
+    return true;
+}
 inline bool is_pnm_ext(const std::string& e) {
     return e == ".pbm" || e == ".pgm" || e == ".ppm" || e == ".pnm" || e == ".pfm";
 }
@@ -214,14 +224,36 @@ class Image {
 
     int byteSize(Type t) const { return t == Type::FLOAT ? 4 : t == Type::USHORT ? 2 : 1; }
 
-    void readJpg(const std::string& path) {
-        std::FILE* f = std::fopen(path.c_str(), "rb");
-        if (!f) throw std::runtime_error("Could not open " + path);
+    // The byte readers' body (png, tga, bmp, gif, tiff): decode(ctx, data, size, &out, &w, &h, &d)
+    // sets d or leaves the `d` given here. As in the reference a failure -- a file that cannot be
+    // opened included -- leaves pixels_ null; only an internal error throws, with the library's message.
+    template <class Decode>
+    void readBytes(const std::string& path, const char* entry, int ok, int internal, int d, Decode decode) {
         std::vector<uint8_t> buf;
-        uint8_t chunk[1 << 16];
-        size_t k;
-        while ((k = std::fread(chunk, 1, sizeof chunk, f)) > 0) buf.insert(buf.end(), chunk, chunk + k);
-        std::fclose(f);
+        detail::read_file(path, buf);
+        auto& P = detail::icx_process();
+        std::lock_guard<std::mutex> lock(P.mu);
+        uint8_t* out = nullptr;
+        int w = 0, h = 0;
+        const int rc = decode(P.get(), buf.data(), buf.size(), &out, &w, &h, &d);
+        delete[] pixels_;
+        pixels_ = nullptr;
+        w_ = h_ = d_ = 0;
+        if (rc == internal) throw std::runtime_error(std::string(entry) + ": " + icx_last_error(P.get()));
+        if (rc != ok) return;
+        const size_t n = (size_t)w * h * d;
+        pixels_ = new unsigned char[n ? n : 1];
+        if (n) std::memcpy(pixels_, out, n);
+        icx_free(out);
+        w_ = w;
+        h_ = h;
+        d_ = d;
+        type_ = Type::UBYTE;
+    }
+
+    void readJpg(const std::string& path) {
+        std::vector<uint8_t> buf;
+        if (!detail::read_file(path, buf)) throw std::runtime_error("Could not open " + path);
         auto& P = detail::icx_process();
         std::lock_guard<std::mutex> lock(P.mu);
         uint8_t* out = nullptr;
@@ -248,13 +280,8 @@ class Image {
     // rest (the reference leaves them uninitialised); header errors and run-length data the
     // reference cannot decode throw "Invalid file format" (:719, :748).
     void readHdr(const std::string& path) {
-        std::FILE* f = std::fopen(path.c_str(), "rb");
-        if (!f) throw std::runtime_error("Cannot open file");  // codecs.cpp:713-714
         std::vector<uint8_t> buf;
-        uint8_t chunk[1 << 16];
-        size_t k;
-        while ((k = std::fread(chunk, 1, sizeof chunk, f)) > 0) buf.insert(buf.end(), chunk, chunk + k);
-        std::fclose(f);
+        if (!detail::read_file(path, buf)) throw std::runtime_error("Cannot open file");  // codecs.cpp:713-714
         auto& P = detail::icx_process();
         std::lock_guard<std::mutex> lock(P.mu);
         float* out = nullptr;
@@ -281,14 +308,8 @@ class Image {
     // loop stores one byte more than the file holds (ifile.get()'s EOF as 0xFF, :468-471); it is
     // passed on the same way. A failure throws "Could not load .exr" (:489).
     void readExr(const std::string& path) {
-        std::FILE* f = std::fopen(path.c_str(), "rb");
         std::vector<uint8_t> buf;
-        if (f) {
-            uint8_t chunk[1 << 16];
-            size_t k;
-            while ((k = std::fread(chunk, 1, sizeof chunk, f)) > 0) buf.insert(buf.end(), chunk, chunk + k);
-            std::fclose(f);
-        }
+        detail::read_file(path, buf);
         buf.push_back(0xFF);
         auto& P = detail::icx_process();
         std::lock_guard<std::mutex> lock(P.mu);
@@ -316,96 +337,24 @@ class Image {
     // fills them bottom-up and flips). As in the reference a failure leaves pixels_ null, and
     // read() throws "Could not read image data" (:85-88).
     void readPng(const std::string& path) {
-        std::FILE* f = std::fopen(path.c_str(), "rb");
-        std::vector<uint8_t> buf;
-        if (f) {
-            uint8_t chunk[1 << 16];
-            size_t k;
-            while ((k = std::fread(chunk, 1, sizeof chunk, f)) > 0) buf.insert(buf.end(), chunk, chunk + k);
-            std::fclose(f);
-        }
-        auto& P = detail::icx_process();
-        std::lock_guard<std::mutex> lock(P.mu);
-        uint8_t* out = nullptr;
-        int w = 0, h = 0;
-        const int rc = icx_png_decode(P.get(), buf.data(), buf.size(), &out, &w, &h);
-        delete[] pixels_;
-        pixels_ = nullptr;
-        w_ = h_ = d_ = 0;
-        if (rc == ICX_PNGR_INTERNAL_ERR) throw std::runtime_error(std::string("icx_png_decode: ") + icx_last_error(P.get()));
-        if (rc != ICX_PNGR_OK) return;
-        const size_t n = (size_t)w * h * 4;
-        pixels_ = new unsigned char[n ? n : 1];
-        if (n) std::memcpy(pixels_, out, n);
-        icx_free(out);
-        w_ = w;
-        h_ = h;
-        d_ = 4;
-        type_ = Type::UBYTE;
+        readBytes(path, "icx_png_decode", ICX_PNGR_OK, ICX_PNGR_INTERNAL_ERR, 4,
+                  [](icx_ctx* c, const uint8_t* p, size_t n, uint8_t** out, int* w, int* h, int*) {
+                      return icx_png_decode(c, p, n, out, w, h);
+                  });
     }
 
     // readTga (codecs.cpp:1304-1407): d = 1, 3 or 4, Type::UBYTE, rows top-down, decoded on the GPU
     // (icx_tga_decode). As in the reference a failure (type 0 included) leaves pixels_ null, and
     // read() throws "Could not read image data" (:85-88).
     void readTga(const std::string& path) {
-        std::FILE* f = std::fopen(path.c_str(), "rb");
-        std::vector<uint8_t> buf;
-        if (f) {
-            uint8_t chunk[1 << 16];
-            size_t k;
-            while ((k = std::fread(chunk, 1, sizeof chunk, f)) > 0) buf.insert(buf.end(), chunk, chunk + k);
-            std::fclose(f);
-        }
-        auto& P = detail::icx_process();
-        std::lock_guard<std::mutex> lock(P.mu);
-        uint8_t* out = nullptr;
-        int w = 0, h = 0, d = 0;
-        const int rc = icx_tga_decode(P.get(), buf.data(), buf.size(), &out, &w, &h, &d);
-        delete[] pixels_;
-        pixels_ = nullptr;
-        w_ = h_ = d_ = 0;
-        if (rc == ICX_TGA_INTERNAL_ERR) throw std::runtime_error(std::string("icx_tga_decode: ") + icx_last_error(P.get()));
-        if (rc != ICX_TGA_OK) return;
-        const size_t n = (size_t)w * h * d;
-        pixels_ = new unsigned char[n ? n : 1];
-        if (n) std::memcpy(pixels_, out, n);
-        icx_free(out);
-        w_ = w;
-        h_ = h;
-        d_ = d;
-        type_ = Type::UBYTE;
+        readBytes(path, "icx_tga_decode", ICX_TGA_OK, ICX_TGA_INTERNAL_ERR, 0, icx_tga_decode);
     }
 
     // readBmp (codecs.cpp:255-320): d = 1, 3 or 4, Type::UBYTE, rows top-down, decoded on the GPU
     // (icx_bmp_decode). A failure -- a file that cannot be opened included -- leaves pixels_ null, and
     // read() throws "Could not read image data" (:85-88).
     void readBmp(const std::string& path) {
-        std::FILE* f = std::fopen(path.c_str(), "rb");
-        std::vector<uint8_t> buf;
-        if (f) {
-            uint8_t chunk[1 << 16];
-            size_t k;
-            while ((k = std::fread(chunk, 1, sizeof chunk, f)) > 0) buf.insert(buf.end(), chunk, chunk + k);
-            std::fclose(f);
-        }
-        auto& P = detail::icx_process();
-        std::lock_guard<std::mutex> lock(P.mu);
-        uint8_t* out = nullptr;
-        int w = 0, h = 0, d = 0;
-        const int rc = icx_bmp_decode(P.get(), buf.data(), buf.size(), &out, &w, &h, &d);
-        delete[] pixels_;
-        pixels_ = nullptr;
-        w_ = h_ = d_ = 0;
-        if (rc == ICX_BMP_INTERNAL_ERR) throw std::runtime_error(std::string("icx_bmp_decode: ") + icx_last_error(P.get()));
-        if (rc != ICX_BMP_OK) return;
-        const size_t n = (size_t)w * h * d;
-        pixels_ = new unsigned char[n ? n : 1];
-        if (n) std::memcpy(pixels_, out, n);
-        icx_free(out);
-        w_ = w;
-        h_ = h;
-        d_ = d;
-        type_ = Type::UBYTE;
+        readBytes(path, "icx_bmp_decode", ICX_BMP_OK, ICX_BMP_INTERNAL_ERR, 0, icx_bmp_decode);
     }
 
     void writeJpg(const std::string& path) {
@@ -446,64 +395,17 @@ class Image {
     // top-down, decoded on the GPU (icx_gif_decode). A failure leaves pixels_ null, and read() throws
     // "Could not read image data" (:85-88).
     void readGif(const std::string& path) {
-        std::FILE* f = std::fopen(path.c_str(), "rb");
-        std::vector<uint8_t> buf;
-        if (f) {
-            uint8_t chunk[1 << 16];
-            size_t k;
-            while ((k = std::fread(chunk, 1, sizeof chunk, f)) > 0) buf.insert(buf.end(), chunk, chunk + k);
-            std::fclose(f);
-        }
-        auto& P = detail::icx_process();
-        std::lock_guard<std::mutex> lock(P.mu);
-        uint8_t* out = nullptr;
-        int w = 0, h = 0;
-        const int rc = icx_gif_decode(P.get(), buf.data(), buf.size(), &out, &w, &h);
-        delete[] pixels_;
-        pixels_ = nullptr;
-        w_ = h_ = d_ = 0;
-        if (rc == ICX_GIF_INTERNAL_ERR) throw std::runtime_error(std::string("icx_gif_decode: ") + icx_last_error(P.get()));
-        if (rc != ICX_GIF_OK) return;
-        const size_t n = (size_t)w * h * 3;
-        pixels_ = new unsigned char[n ? n : 1];
-        if (n) std::memcpy(pixels_, out, n);
-        icx_free(out);
-        w_ = w;
-        h_ = h;
-        d_ = 3;
-        type_ = Type::UBYTE;
+        readBytes(path, "icx_gif_decode", ICX_GIF_OK, ICX_GIF_INTERNAL_ERR, 3,
+                  [](icx_ctx* c, const uint8_t* p, size_t n, uint8_t** out, int* w, int* h, int*) {
+                      return icx_gif_decode(c, p, n, out, w, h);
+                  });
     }
 
     // readTiff (codecs.cpp:1439-1484): the first IFD, d = 1, 3 or 4, Type::UBYTE, rows top-down,
     // decoded on the GPU (icx_tiff_decode). A failure leaves pixels_ null, and read() throws "Could
     // not read image data" (:85-88).
     void readTiff(const std::string& path) {
-        std::FILE* f = std::fopen(path.c_str(), "rb");
-        std::vector<uint8_t> buf;
-        if (f) {
-            uint8_t chunk[1 << 16];
-            size_t k;
-            while ((k = std::fread(chunk, 1, sizeof chunk, f)) > 0) buf.insert(buf.end(), chunk, chunk + k);
-            std::fclose(f);
-        }
-        auto& P = detail::icx_process();
-        std::lock_guard<std::mutex> lock(P.mu);
-        uint8_t* out = nullptr;
-        int w = 0, h = 0, d = 0;
-        const int rc = icx_tiff_decode(P.get(), buf.data(), buf.size(), &out, &w, &h, &d);
-        delete[] pixels_;
-        pixels_ = nullptr;
-        w_ = h_ = d_ = 0;
-        if (rc == ICX_TIFF_INTERNAL_ERR) throw std::runtime_error(std::string("icx_tiff_decode: ") + icx_last_error(P.get()));
-        if (rc != ICX_TIFF_OK) return;
-        const size_t n = (size_t)w * h * d;
-        pixels_ = new unsigned char[n ? n : 1];
-        if (n) std::memcpy(pixels_, out, n);
-        icx_free(out);
-        w_ = w;
-        h_ = h;
-        d_ = d;
-        type_ = Type::UBYTE;
+        readBytes(path, "icx_tiff_decode", ICX_TIFF_OK, ICX_TIFF_INTERNAL_ERR, 0, icx_tiff_decode);
     }
 
     // writeTga (codecs.cpp:1410-1437): uncompressed, d = 1, 3, 4. As in the reference nothing is
@@ -529,14 +431,8 @@ class Image {
     // d = 1 or 3, Type::UBYTE, USHORT or FLOAT, rows top-down, decoded on the GPU (icx_pnm_decode). A
     // failure leaves pixels_ null, and read() throws "Could not read image data" (:85-88).
     void readPnm(const std::string& path) {
-        std::FILE* f = std::fopen(path.c_str(), "rb");
         std::vector<uint8_t> buf;
-        if (f) {
-            uint8_t chunk[1 << 16];
-            size_t k;
-            while ((k = std::fread(chunk, 1, sizeof chunk, f)) > 0) buf.insert(buf.end(), chunk, chunk + k);
-            std::fclose(f);
-        }
+        detail::read_file(path, buf);
         auto& P = detail::icx_process();
         std::lock_guard<std::mutex> lock(P.mu);
         void* out = nullptr;
