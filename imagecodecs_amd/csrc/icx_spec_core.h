@@ -559,6 +559,52 @@ ICX_HD WriteOut write_step_more(Reader& r, const Tab& T, const Huff* H, const Se
     const uint32_t e = step_entry(r, T, H, S, b, false, x);
     return write_decode(r, e, x, S, b, z, near_err);
 }
+// write_step_more for a window of any fill: the further AC lookup is also taken out of a window of
+// nb <= 32 bits when every bit it uses is valid. A Huffman symbol is fixed by its own bits, and
+// `buf` holds exactly nb valid bits with zeros below them, so the entry read at the zero-padded
+// peek is the right symbol -- or the right pair -- whenever it takes no more than nb bits. A lane
+// with nb <= 32 reads the first-level table alone and takes the lookup iff the entry is a plain one
+// (not SUB / SEARCH, not err1: the next iteration's full-window lookup decides those, and zero
+// padding never sends a wave into the pool / resolve branches) and tot1 + tot2 <= nb (a pair whose
+// second symbol does not fit is refused whole: one add and one compare, where committing symbol 1
+// alone would take a second compare on every iteration for a case photographic streams do not
+// have). A lane with nb > 32 does exactly what write_step_more does (there tot1 + tot2 <= 32 < nb).
+// short_entry is the lookup -- the entry, its peek, and the wave mask of the lanes that take it --
+// and write_step_short the whole step; it returns false for a lane that refuses: r, b, z and o are
+// then untouched. Call with z != 0. (k_gw_lane calls short_entry and decodes under the mask itself:
+// a step that hands its WriteOut out of the branch has its bools merged by scalar mask moves and
+// the branch split in two -- measured, 25 % more SALU per wave and a third of the kernel's gain.)
+// Reader invariants: consume(n) only with n <= nb; after a short lookup nb may be 0, and the next
+// refill() then gives nb = 32, exactly what step_entry's 32-bit peek needs; still one refill per
+// iteration and at most one word per refill, so the slot rule (tick, phase()) is unchanged.
+// The lane conditions are wave masks (ballots ANDed in SGPRs, read back by lane_in).
+constexpr uint32_t kStErr1 = 1u << 15;  // st_err1's bit
+template <class Tab>
+ICX_HD uint64_t short_entry(const Reader& r, const Tab& T, const Huff* H, const Sel& S, int b, uint32_t& x, uint32_t& e) {
+    x = (uint32_t)(r.buf >> 32);
+    e = T.look_b(b, false, x);
+    const uint64_t fullm = wave_ballot(r.nb > 32);
+    const uint64_t oddm = wave_ballot((e & (kStSlow | kStErr1)) != 0u);  // slow or error entries
+    if (fullm & oddm) {  // step_entry's long codes, for full windows alone
+        const bool full = lane_in(fullm);
+        const uint32_t ep = T.pool_b(b, false, x);
+        if (fullm & wave_ballot((e & kStSearch) != 0u)) {
+            const bool walk = full && (e & kStSearch) != 0u;
+            const uint32_t es = T.resolve(S.tab(b, false), x, walk ? e : kStSub, H);
+            e = walk ? es : e;
+        }
+        e = full && (e & kStSub) ? ep : e;
+    }
+    const uint64_t fitm = wave_ballot((int)(st_tot1(e) + ((e >> 16) & 15u)) <= r.nb);
+    return fitm & (fullm | ~oddm);
+}
+template <class Tab>
+ICX_HD bool write_step_short(Reader& r, const Tab& T, const Huff* H, const Sel& S, int& b, int& z, bool near_err, WriteOut& o) {
+    uint32_t x, e;
+    if (!lane_in(short_entry(r, T, H, S, b, x, e))) return false;
+    o = write_decode(r, e, x, S, b, z, near_err);
+    return true;
+}
 
 // ------------------------------------------------------------------------ lane logic
 // Guess lane: decode [start - lead, end) from the block-start guess (b0, z=0) at start - lead
