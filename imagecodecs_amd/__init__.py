@@ -126,6 +126,7 @@ _SIGS = {
     "icx_hdr_batch_destroy": (None, [_vp]),
     "icx_hdr_batch_decode": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _vp]),
     "icx_hdr_batch_stage_times": (_i32, [_vp, _vp, _vp, _i32]),
+    "icx_hdr_batch_locate_stats": (_i32, [_vp, _vp, _vp, _i32]),
     "icx_hdr_encode_bound": (_sz, [_i32, _i32, _i32, _i32]),
     "icx_hdr_save_to_memory": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, C.POINTER(_vp), C.POINTER(_sz)]),
     "icx_hdr_save_to_file": (_i32, [_vp, C.c_char_p, _vp, _i32, _i32, _i32, _i32]),
@@ -1129,6 +1130,17 @@ class HdrBatch(_ReadBatch):
     d_data[d_offsets[i] .. + d_sizes[i]); 4 floats per pixel at d_out + i*out_stride floats."""
 
     _prefix, _ok = "icx_hdr_batch", HDR_OK
+
+    def locate_stats(self) -> list:
+        """icx_hdr_batch_locate_stats: (mode, ncand) of each image of the last decode -- mode 0 failed
+        before locating, 1 all rows plain, 2 scanline starts linked in parallel, 3 walked serially;
+        ncand the new-style scanline start patterns found. Waits for that decode's work."""
+        cap = self.max_images
+        modes, ncand = (C.c_int32 * cap)(), (C.c_int32 * cap)()
+        n = lib().icx_hdr_batch_locate_stats(self._p, modes, ncand, cap)
+        if n < 0:
+            raise ICXError("icx_hdr_batch_locate_stats: " + _err(self.ctx.ptr))
+        return [(int(modes[i]), int(ncand[i])) for i in range(n)]
 
 
 class Image:

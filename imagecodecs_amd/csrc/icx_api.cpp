@@ -301,7 +301,13 @@ struct OneShot {
 }  // namespace
 
 
-struct icx_hdr_batch : ReadBatch<HdrFmt> {};
+struct icx_hdr_batch : ReadBatch<HdrFmt> {
+    hipEvent_t done = nullptr;  // recorded after the last decode call's work (locate_stats waits on it)
+    int last_n = 0;             // images of that call
+    ~icx_hdr_batch() {
+        if (done) (void)hipEventDestroy(done);
+    }
+};
 struct icx_png_batch : ReadBatch<PngFmt> {};
 struct icx_tga_batch : ReadBatch<TgaFmt> {};
 struct icx_bmp_batch : ReadBatch<BmpFmt> {};
@@ -1294,7 +1300,32 @@ void icx_hdr_batch_destroy(icx_hdr_batch* b) { read_batch_destroy(b); }
 
 int icx_hdr_batch_decode(icx_hdr_batch* b, int n, const uint8_t* d_data, const uint64_t* d_off, const uint64_t* d_size,
                          float* d_out, uint64_t out_stride, int32_t* d_status, int32_t* d_dims, void* stream) {
-    return read_batch_decode<HdrFmt>(b, n, d_data, d_off, d_size, d_out, out_stride, d_status, d_dims, stream);
+    const int rc = read_batch_decode<HdrFmt>(b, n, d_data, d_off, d_size, d_out, out_stride, d_status, d_dims, stream);
+    if (rc != ICX_HDR_OK) return rc;
+    b->last_n = n;
+    if (n == 0) return rc;
+    // owned by the batch: locate_stats waits on this event, never on the caller's stream (which
+    // the caller may destroy after the call)
+    if (!b->done) ICX_HIP(b->ctx, hipEventCreateWithFlags(&b->done, hipEventDisableTiming), ICX_HDR_INTERNAL_ERR);
+    ICX_HIP(b->ctx, hipEventRecord(b->done, stream ? (hipStream_t)stream : b->ctx->stream), ICX_HDR_INTERNAL_ERR);
+    return rc;
+}
+
+int icx_hdr_batch_locate_stats(const icx_hdr_batch* b, int32_t* modes, int32_t* ncand, int cap) {
+    if (!b) return ICX_HDR_INTERNAL_ERR;
+    const int n = b->last_n;
+    if (n <= 0) return 0;
+    // The decode may have run on a non-blocking stream, which the null stream does not order
+    // against: wait for the batch's own event recorded after it.
+    ICX_HIP(b->ctx, hipSetDevice(b->ctx->device), ICX_HDR_INTERNAL_ERR);
+    ICX_HIP(b->ctx, hipEventSynchronize(b->done), ICX_HDR_INTERNAL_ERR);
+    std::vector<HdrDesc> h((size_t)n);
+    ICX_HIP(b->ctx, hipMemcpy(h.data(), b->ws.desc, (size_t)n * sizeof(HdrDesc), hipMemcpyDeviceToHost), ICX_HDR_INTERNAL_ERR);
+    for (int i = 0; i < n && i < cap; ++i) {
+        if (modes) modes[i] = h[i].mode;
+        if (ncand) ncand[i] = h[i].ncand;
+    }
+    return n;
 }
 
 int icx_hdr_batch_stage_times(const icx_hdr_batch* b, const char** names, float* ms, int cap) {

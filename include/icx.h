@@ -331,6 +331,15 @@ int icx_hdr_batch_decode(icx_hdr_batch* b, int n, const uint8_t* d_data, const u
 /* Milliseconds per stage of the last icx_hdr_batch_decode ("parse", "locate", "unpack",
  * "convert"; synchronises). Returns the number of stages. */
 int icx_hdr_batch_stage_times(const icx_hdr_batch* b, const char** names, float* ms, int cap);
+/* How each image of the last icx_hdr_batch_decode was located (waits for that call's work, on
+ * whichever stream it ran). modes[i]: 0 the file failed before its scanlines were looked for (a
+ * header error, TOO_LARGE), 1 every row is a plain RGBE row at data start + 4*width*i, 2 the
+ * new-style scanline starts found in parallel chain from the data start over all rows, 3 one lane
+ * walked the scanlines serially (any other file; the same pixels). ncand[i]: the aligned or
+ * unaligned occurrences of "2 2 width>>8 width&255" in the pixel data (0 for widths outside
+ * 8..32767 and for mode 0). Either array may be NULL; at most cap entries are written. Returns the
+ * number of images of that call (0 before the first), or ICX_HDR_INTERNAL_ERR. */
+int icx_hdr_batch_locate_stats(const icx_hdr_batch* b, int32_t* modes, int32_t* ncand, int cap);
 
 /* ---- Radiance .hdr write (Image::writeHdr, codecs.cpp:779-818) ----------------------------------
  * The file: the reference's header bytes (:791),

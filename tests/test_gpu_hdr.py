@@ -10,6 +10,7 @@ import os
 import numpy as np
 import pytest
 
+import hdr_craft as K
 import hdrutil as H
 import imagecodecs_amd as icx
 from oracle import pyoracle as O
@@ -55,7 +56,8 @@ def test_hdr_edge_files_single(ctx):
         _same(ctx.hdr_decode(data), O.hdr_decode(data), name)
 
 
-def _batch(ctx, files, max_w, max_h, pad=0):
+def _batch(ctx, files, max_w, max_h, pad=0, stats=None):
+    """stats: a list that receives the batch's locate_stats(), (mode, ncand) per image."""
     import torch
     dev = torch.device("cuda", 0)
     n = len(files)
@@ -76,6 +78,8 @@ def _batch(ctx, files, max_w, max_h, pad=0):
                     st.data_ptr(), dims.data_ptr(), stream)
     torch.cuda.synchronize(dev)
     times = b.stage_times()
+    if stats is not None:
+        stats.extend(b.locate_stats())
     b.close()
     out, st, dims = out.cpu().numpy(), st.cpu().numpy(), dims.cpu().numpy()
     res = []
@@ -90,10 +94,13 @@ def test_hdr_batch_mixed_corpus(ctx):
     files = [open(os.path.join(GOLDEN, "test.hdr"), "rb").read()]
     files += [f for _, f, _ in H.valid_cases()] + [f for _, f in H.edge_cases()]
     names = ["test.hdr"] + [n for n, _, _ in H.valid_cases()] + [n for n, _ in H.edge_cases()]
-    res, times = _batch(ctx, files, 1000, 289)
+    stats = []
+    res, times = _batch(ctx, files, 1000, 289, stats=stats)
     assert set(times) == {"parse", "locate", "unpack", "convert"}
     for name, f, got in zip(names, files, res):
         _same(got, O.hdr_decode(f), name)
+    # each file was located the way the restated rule (hdr_craft.predict) says, not by a fallback
+    assert dict(zip(names, stats)) == {name: K.predict(f) for name, f in zip(names, files)}
 
 
 @pytest.mark.parametrize("mode", [H.RLE, H.FLAT, H.OLD])
@@ -103,11 +110,17 @@ def test_hdr_batch_large(ctx, mode):
     imgs = [H.S.rgbe(900 + k, w, h) for k, (w, h) in enumerate([(1024, 768), (640, 1100), (2000, 64)])]
     files = [H.S.hdr(px, mode) for px in imgs]
     files.append(H.mixed_file(77, 512, 300)[0])
-    res, _ = _batch(ctx, files, 2000, 1100)
+    stats = []
+    res, _ = _batch(ctx, files, 2000, 1100, stats=stats)
     for k, (f, got) in enumerate(zip(files, res)):
         ref = O.hdr_decode(f)
         assert ref[0] == O.HDR_OK
         _same(got, ref, f"large{k}")
+    # new-style files link (one start per row, no false ones), flat files are plain rows, the
+    # old-style and the mixed file are walked serially: as the restated rule says
+    want = {H.RLE: [(2, 768), (2, 1100), (2, 64)], H.FLAT: [(1, 0)] * 3, H.OLD: [(3, 0)] * 3}[mode] + [(3, 75)]
+    assert [K.predict(f) for f in files] == want
+    assert stats == want
 
 
 def test_hdr_many_rows_beyond_candidate_cap(ctx):
