@@ -36,6 +36,7 @@
 #include "icx_internal.h"
 #include "icx_mem.h"
 #include "icx_bmp_core.h"
+#include "icx_wave.h"
 
 namespace icx {
 
@@ -57,31 +58,6 @@ struct BmpDesc {
     int32_t last;      // the tile in which the walk ends (k_bmp_chain)
     int32_t short_ws;  // the stream is longer than the workspace's tiles cover
 };
-
-// win[0, len) = file bytes [base, base + len), zero outside [0, fsize). d + base is 16-byte
-// aligned, len a multiple of 16, win 16-byte aligned. Bytes outside the file are never read.
-__device__ __forceinline__ void bmp_fill(uint8_t* win, const uint8_t* d, int64_t fsize, int64_t base, int len, int tid,
-                                         int nthreads) {
-    for (int o = tid * 16; o < len; o += nthreads * 16) {
-        const int64_t a = base + o;
-        uint4 v = make_uint4(0, 0, 0, 0);
-        if (a >= 0 && a + 16 <= fsize) {
-            v = *reinterpret_cast<const uint4*>(d + a);
-        } else {
-            uint32_t t[4] = {0, 0, 0, 0};
-            for (int b = 0; b < 16; ++b)
-                if (a + b >= 0 && a + b < fsize) t[b >> 2] |= (uint32_t)d[a + b] << (8 * (b & 3));
-            v = make_uint4(t[0], t[1], t[2], t[3]);
-        }
-        *reinterpret_cast<uint4*>(win + o) = v;
-    }
-}
-
-__device__ __forceinline__ void bmp_wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 __global__ void k_bmp_parse(int n, const uint8_t* __restrict__ data, const uint64_t* __restrict__ off,
                             const uint64_t* __restrict__ size, BmpDesc* __restrict__ desc, int max_w, int max_h,
@@ -129,7 +105,7 @@ __global__ __launch_bounds__(256) void k_bmp_tiles(const uint8_t* __restrict__ d
     const int64_t n = dd.size, tile0 = dd.H.ds + (int64_t)t * kBmpTile;
     const int rle = dd.H.rle;
     const int mis = (int)(reinterpret_cast<uintptr_t>(d + tile0) & 15);
-    bmp_fill(win, d, n, tile0 - mis, kBmpTile + 32, threadIdx.x, 256);
+    fill_window(win, d, n, tile0 - mis, kBmpTile + 32, threadIdx.x, 256);
     __syncthreads();
     constexpr int kPer = kBmpSlots / 256;
     uint16_t nn[kPer];
@@ -292,8 +268,8 @@ __global__ __launch_bounds__(256) void k_bmp_expand(const uint8_t* __restrict__ 
     const int64_t n = dd.size, tile0 = H.ds + (int64_t)t * kBmpTile;
     uint8_t* win = win_all[wv];
     const int mis = (int)(reinterpret_cast<uintptr_t>(d + tile0) & 15);
-    bmp_fill(win, d, n, tile0 - mis, kBmpWin, lane, 64);
-    bmp_wave_sync();
+    fill_window(win, d, n, tile0 - mis, kBmpWin, lane, 64);
+    wave_sync();
     uint16_t* pk_pos = pk_pos_all[wv];
     uint32_t* pk_end = pk_end_all[wv];
     int32_t* pk_x = pk_x_all[wv];
@@ -330,7 +306,7 @@ __global__ __launch_bounds__(256) void k_bmp_expand(const uint8_t* __restrict__ 
             bmp_apply(k.move, &x, &y);
             pos += k.len;
         }
-        bmp_wave_sync();
+        wave_sync();
         // their pixels, one per lane: the packet of pixel q is the first whose end is past q
         for (uint32_t q = lane; q < cum; q += 64) {
             int lo = 0, hi = np - 1;
@@ -345,7 +321,7 @@ __global__ __launch_bounds__(256) void k_bmp_expand(const uint8_t* __restrict__ 
             const uint32_t idx = bmp_packet_index(win + mis + (pp & 0x7FFF), (pp & 0x8000) ? kBmpPkLiteral : kBmpPkRun, rle, k);
             bmp_put(o + ((int64_t)pk_row[lo] * w + pk_x[lo] + k) * d_out, s_pal[idx], d_out);
         }
-        bmp_wave_sync();  // the table is read before the next chunk overwrites it
+        wave_sync();  // the table is read before the next chunk overwrites it
     }
 }
 
@@ -386,9 +362,10 @@ __device__ __forceinline__ void bmp_stream_rows(const BmpHead& H, const uint8_t*
             const int64_t s0 = H.ds + (int64_t)fy * H.stride + ((int64_t)x0 * BITS >> 3);
             const int mis = (int)(reinterpret_cast<uintptr_t>(file + s0) & 15);
             __syncthreads();  // the previous segment's readers are done (and the tables are staged)
-            bmp_fill(win, file, fsize, s0 - mis, (mis + ns + 15) & ~15, tid, 256);
+            fill_window(win, file, fsize, s0 - mis, (mis + ns + 15) & ~15, tid, 256);
             __syncthreads();
             const uint8_t* seg = win + mis;
+            // (icx_wave.h's store_segment written out: x, c and the pixel are carried over the 16 bytes)
             uint8_t* optr = dst + ((int64_t)y * H.w + x0) * D;
             const int nb = nx * D;
             const int head = min(nb, (int)((16 - (reinterpret_cast<uintptr_t>(optr) & 15)) & 15));
@@ -545,7 +522,7 @@ __global__ __launch_bounds__(256) void k_bmpw_rows(const BmpJob* __restrict__ jo
             const int64_t s0 = ((int64_t)(h - 1 - r) * w + x0) * d;
             const int mis = (int)(reinterpret_cast<uintptr_t>(J.src + s0) & 15);
             __syncthreads();  // the previous segment's readers are done
-            bmp_fill(win, J.src, src_size, s0 - mis, (mis + nx * d + 15) & ~15, tid, 256);
+            fill_window(win, J.src, src_size, s0 - mis, (mis + nx * d + 15) & ~15, tid, 256);
             __syncthreads();
             const uint8_t* seg = win + mis;
             auto byte_at = [&](int q) -> uint32_t {  // byte q of the segment's part of the file row
@@ -554,22 +531,8 @@ __global__ __launch_bounds__(256) void k_bmpw_rows(const BmpJob* __restrict__ jo
                 const int x = q / d, c = q - x * d;
                 return c < 3 ? seg[x * d + 2 - c] : seg[x * d + 3];
             };
-            uint8_t* optr = dst + (int64_t)r * stride + (int64_t)x0 * d;
             const int nb = nx * d + (x0 + nx == w ? (int)(stride - (int64_t)w * d) : 0);
-            const int head = min(nb, (int)((16 - (reinterpret_cast<uintptr_t>(optr) & 15)) & 15));
-            const int nv = (nb - head) / 16;
-            for (int v = tid; v < nv; v += 256) {
-                const int b0 = head + 16 * v;
-                uint32_t wd[4] = {0, 0, 0, 0};
-#pragma unroll
-                for (int b = 0; b < 16; ++b) wd[b >> 2] |= byte_at(b0 + b) << (8 * (b & 3));
-                *reinterpret_cast<uint4*>(optr + b0) = make_uint4(wd[0], wd[1], wd[2], wd[3]);
-            }
-            const int tail0 = head + 16 * nv;
-            for (int b = tid; b < head + (nb - tail0); b += 256) {
-                const int q = b < head ? b : tail0 + (b - head);
-                optr[q] = (uint8_t)byte_at(q);
-            }
+            store_segment(dst + (int64_t)r * stride + (int64_t)x0 * d, nb, tid, byte_at);
         }
     }
 }
@@ -604,36 +567,35 @@ void launch_bmp_decode(const BmpWs& ws, int n, const uint8_t* d_data, const uint
                        uint8_t* d_out, uint64_t out_stride, int32_t* d_status, int32_t* d_dims, hipStream_t st,
                        StageHook* hook) {
     if (n <= 0) return;
-    auto B = [&](Stage s) { if (hook) hook->begin(s, st); };
-    auto E = [&](Stage s) { if (hook) hook->end(s, st); };
+    const Stages S{hook, st};
     const int nb = (n + 63) / 64;
     const unsigned tiles = (unsigned)ws.tiles_cap;
-    const int rows = std::max(1, std::min(ws.max_h, 16384 / std::min(n, 16384)));
-    B(kStParse);
+    const int rows = rows_grid(ws.max_h, n);
+    S.begin(kStParse);
     hipLaunchKernelGGL(k_bmp_parse, dim3(nb), dim3(64), 0, st, n, d_data, d_off, d_size, ws.desc, ws.max_w, ws.max_h,
                        ws.tiles_cap);
-    E(kStParse);
-    B(kStUnstuff);  // locating the packets
+    S.end(kStParse);
+    S.begin(kStUnstuff);  // locating the packets
     if (tiles) {
         hipLaunchKernelGGL(k_bmp_tiles, dim3(tiles, n), dim3(256), 0, st, d_data, d_off, ws.desc,
                            reinterpret_cast<uint4*>(ws.summary), ws.tiles_cap);
         hipLaunchKernelGGL(k_bmp_chain, dim3(n), dim3(256), 0, st, ws.desc, reinterpret_cast<const uint4*>(ws.summary),
                            ws.entry, ws.cur_x, ws.cur_y, ws.tiles_cap);
     }
-    E(kStUnstuff);
-    B(kStWrite);  // the background of run-length coded images
+    S.end(kStUnstuff);
+    S.begin(kStWrite);  // the background of run-length coded images
     if (tiles) hipLaunchKernelGGL(k_bmp_fill, dim3(rows, n), dim3(256), 0, st, d_data, d_off, ws.desc, d_out, out_stride);
-    E(kStWrite);
-    B(kStEntropy);  // run-length decoding
+    S.end(kStWrite);
+    S.begin(kStEntropy);  // run-length decoding
     if (tiles)
         hipLaunchKernelGGL(k_bmp_expand, dim3((tiles + 3) / 4, n), dim3(256), 0, st, d_data, d_off, ws.desc, ws.entry,
                            ws.cur_x, ws.cur_y, d_out, out_stride, ws.tiles_cap);
-    E(kStEntropy);
-    B(kStConvert);  // raw files
+    S.end(kStEntropy);
+    S.begin(kStConvert);  // raw files
     hipLaunchKernelGGL(k_bmp_raw24, dim3(rows, n), dim3(256), 0, st, d_data, d_off, ws.desc, d_out, out_stride);
     hipLaunchKernelGGL(k_bmp_raw, dim3(rows, n), dim3(256), 0, st, d_data, d_off, ws.desc, d_out, out_stride);
     hipLaunchKernelGGL(k_bmp_finish, dim3(nb), dim3(64), 0, st, n, ws.desc, d_status, d_dims);
-    E(kStConvert);
+    S.end(kStConvert);
 }
 
 struct BmpwWs {
@@ -656,24 +618,11 @@ int bmp_encode_batch(hipStream_t st, BmpwWs& ws, int n, const uint8_t* const* d_
         J.status = J.src && bmp_write_args_ok(J.w, J.h, d) ? kBmpOk : kBmpInvalidArgument;
         if (J.status == kBmpOk) max_h = std::max(max_h, J.h);
     }
-    auto fail = [&](const char* what) {
-        err = std::string(what) + ": " + hipGetErrorString(hipGetLastError());
-        return -1;
-    };
-    if (!ws.jobs.reserve(jobs.size() * sizeof(BmpJob))) return fail("bmp_encode_batch: allocation");
-    if (hipMemcpyAsync(ws.jobs.p, jobs.data(), jobs.size() * sizeof(BmpJob), hipMemcpyHostToDevice, st) != hipSuccess)
-        return fail("bmp_encode_batch: copy");
-    const int gy = std::max(1, std::min(max_h, 16384 / std::min(n, 16384)));
+    if (jobs_upload("bmp_encode_batch", ws.jobs, jobs, st, err)) return -1;
+    const int gy = rows_grid(max_h, n);
     hipLaunchKernelGGL(k_bmpw_head, dim3(n), dim3(64), 0, st, ws.jobs.p, d, d_out, out_stride, d_sizes, d_status);
     hipLaunchKernelGGL(k_bmpw_rows, dim3(gy, n), dim3(256), 0, st, ws.jobs.p, d, d_out, out_stride);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipStreamSynchronize(st);  // (the pageable job array is read before it goes)
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        err = std::string("bmp_encode_batch: ") + hipGetErrorString(e);
-        return -1;
-    }
-    return 0;
+    return encode_finish("bmp_encode_batch", st, err);
 }
 
 }  // namespace icx

@@ -14,6 +14,7 @@
 //                 first bytes): once the 64 codes' entries are in, the lanes walk their own chains
 //                 back to front and store the indices into the image's index plane, which is laid out
 //                 as the clipped frame rectangle (interlace map and clipping applied here, per row).
+//                 The round from the 64 codes to the stored bytes is icx_lzw_wave.h.
 //   k_gif_render  canvas rows: background, frame rectangle through the palette with the transparent
 //                 skip; pixels the stream did not reach read as the background index. A row segment
 //                 is assembled in LDS and leaves as 16-byte stores at the destination's alignment.
@@ -26,7 +27,7 @@
 #include "icx_internal.h"
 #include "icx_mem.h"
 #include "icx_gif_core.h"
-#include "icx_lzw_wave.h"  // gif_wave_sync, gif_fill, gif_wave_sum_scan
+#include "icx_lzw_wave.h"
 
 namespace icx {
 
@@ -57,8 +58,8 @@ __global__ void k_gif_parse(int n, const uint8_t* __restrict__ data, const uint6
 __global__ __launch_bounds__(64) void k_gif_lzw(const uint8_t* __restrict__ data, const uint64_t* __restrict__ off,
                                                 GifDesc* __restrict__ desc, uint8_t* __restrict__ plane,
                                                 uint64_t plane_stride) {
-    __shared__ uint32_t tab[4096];  // prefix code | suffix << 12 | string length << 20
-    __shared__ uint8_t first[4096];  // the string's first byte
+    __shared__ uint32_t tab[4096];  // the LZW table (icx_lzw_wave.h)
+    __shared__ uint8_t first[4096];
     __shared__ __attribute__((aligned(16))) uint8_t win[kGifWin];
     __shared__ uint8_t ring[kGifRing];
     const int i = blockIdx.x, lane = threadIdx.x;
@@ -78,18 +79,17 @@ __global__ __launch_bounds__(64) void k_gif_lzw(const uint8_t* __restrict__ data
     int ended = kGifEndNone;
     uint32_t wr = 0, rdbyte = 0, rdbit = 0;  // ring bytes written; read position (counters wrap; the ring's size divides 2^32)
     // decode state
-    uint32_t t0 = 0, base = 0;          // the next code's number after the last clear; index bytes produced
-    int prev_code = 0, prev_F = 0;      // of code t0 - 1 (t0 > 0)
-    uint32_t prev_L = 0;
+    uint32_t t0 = 0;                    // the next code's number after the last clear
+    LzwCarry C;                         // C.base: index bytes produced
     int status = kGifOk;
 
-    while (base < npix) {
+    while (C.base < npix) {
         while (ended == kGifEndNone && kGifRing - (wr - rdbyte) >= 255u) {
             if (p < wbase || p + 256 > wbase + kGifWin) {
                 wbase = p - (int64_t)(reinterpret_cast<uintptr_t>(d + p) & 15);
-                gif_wave_sync();  // the window's readers are done
-                gif_fill(win, d, n, wbase, kGifWin, lane);
-                gif_wave_sync();
+                wave_sync();  // the window's readers are done
+                fill_window(win, d, n, wbase, kGifWin, lane, 64);
+                wave_sync();
             }
             if (p >= n) { ended = kGifEndFile; break; }
             const int sz = __builtin_amdgcn_readfirstlane((int)win[p - wbase]);
@@ -100,7 +100,7 @@ __global__ __launch_bounds__(64) void k_gif_lzw(const uint8_t* __restrict__ data
             if (avail < sz) { ended = kGifEndFile; break; }
             p += 1 + sz;
         }
-        gif_wave_sync();
+        wave_sync();
 
         // 64 codes at once
         const uint32_t availbits = (wr - rdbyte) * 8 - rdbit;
@@ -119,73 +119,27 @@ __global__ __launch_bounds__(64) void k_gif_lzw(const uint8_t* __restrict__ data
         const int m0 = evmask ? __builtin_ctzll(evmask) : 64;
         const bool act = lane < m0;
 
-        // string length L and first byte F of every code before the event
-        uint32_t A = 0;
-        int D = -1, F = 0;
-        if (act) {
-            if (code < clear) { A = 1; F = code; }
-            else if ((uint32_t)j >= t0) { A = 1; D = (int)((uint32_t)j - t0); }  // made by this round's codes: a lower lane
-            else if ((uint32_t)j + 1 == t0) { A = prev_L + 1; F = prev_F; }        // made by lane 0 of this round
-            else { A = tab[code] >> 20; F = first[code]; }
-        }
-        while (__any(D >= 0)) {
-            const int src = D < 0 ? lane : D;
-            const uint32_t a2 = __shfl(A, src);
-            const int f2 = __shfl(F, src), d2 = __shfl(D, src);
-            if (D >= 0) { A += a2; F = f2; D = d2; }
-        }
-        const uint32_t L = A;
-        const uint32_t incl = gif_wave_sum_scan(L, lane), excl = incl - L;
-        const uint32_t rem = npix - base;
-        const bool need = act && excl < rem;  // the code starts before the last pixel: a prefix of the lanes
-        const int m = __popcll(__ballot(need));
-
-        // their table entries: code t >= 1 makes entry clear + 1 + t from code t - 1 and its own first byte
-        int pc = __shfl_up(code, 1), pF = __shfl_up(F, 1);
-        uint32_t pL = __shfl_up(L, 1);
-        if (lane == 0) { pc = prev_code; pF = prev_F; pL = prev_L; }
-        if (need && t >= 1 && (uint32_t)clear + 1 + t < 4096u) {
-            tab[clear + 1 + t] = (uint32_t)pc | (uint32_t)(F & 255) << 12 | (pL + 1) << 20;
-            first[clear + 1 + t] = (uint8_t)pF;
-        }
-        gif_wave_sync();
-
-        // every lane walks its own string back to front
-        if (need) {
-            const uint32_t Lcut = min(L, rem - excl);
-            const uint32_t pe = base + excl + L - 1;  // (< 2^32: npix <= 65535^2, L < 4096)
+        const LzwRound R = lzw_resolve(code, act, t0, clear, npix, C, tab, first, lane);
+        lzw_enter(R, code, t, clear, C, tab, first, lane);
+        if (R.need) {  // the index plane is the clipped frame rectangle: interlace map and clipping per row
+            const uint32_t Lcut = R.cut();
+            const uint32_t pe = C.base + R.excl + R.L - 1;  // (< 2^32: npix <= 65535^2, L < 4096)
             uint32_t y = pe / fw, x = pe - y * fw;
             uint32_t ym = H.interlace && y < (uint32_t)H.fh ? (uint32_t)gif_interlace_row(H.fh, (int)y) : y;
-            int c = code;
-            for (uint32_t k = L - 1;; --k) {
-                int s = c;
-                if (k > 0) {
-                    const uint32_t e = tab[c];
-                    s = (e >> 12) & 255;
-                    c = e & 0xFFF;
-                }
+            lzw_walk(R, code, tab, [&](uint32_t k, int s) {
                 if (k < Lcut && x < cw && ym < ch) pl[(uint64_t)ym * cw + x] = (uint8_t)s;
-                if (k == 0) break;
-                if (x == 0) {
+                if (k > 0 && x == 0) {  // on to the byte before
                     x = fw - 1;
                     --y;
                     ym = H.interlace && y < (uint32_t)H.fh ? (uint32_t)gif_interlace_row(H.fh, (int)y) : y;
                 } else {
                     --x;
                 }
-            }
+            });
         }
-        gif_wave_sync();  // the table is read before the next round's entries go in
-
-        if (m > 0) {
-            const uint32_t total = __shfl(incl, m - 1);
-            base = total >= rem ? npix : base + total;
-            prev_code = __shfl(code, m - 1);
-            prev_F = __shfl(F, m - 1);
-            prev_L = __shfl(L, m - 1);
-        }
-        if (base >= npix) break;
-        // (not complete: m == m0)
+        lzw_carry(C, R, code, npix);
+        if (C.base >= npix) break;
+        // (not complete: R.m == m0)
         uint32_t adv;
         if (m0 == 64) {
             adv = (uint32_t)gif_code_offset(mcs, t0 + 64) - off0;
@@ -216,7 +170,7 @@ __global__ __launch_bounds__(64) void k_gif_lzw(const uint8_t* __restrict__ data
         rdbit &= 7;
     }
     if (lane == 0) {
-        dd.produced = base;
+        dd.produced = C.base;
         dd.status = status;
     }
 }
@@ -263,22 +217,7 @@ __global__ __launch_bounds__(256) void k_gif_render(const uint8_t* __restrict__ 
                 seg[3 * x + 2] = (uint8_t)(rgb >> 16);
             }
             __syncthreads();
-            uint8_t* optr = dst + ((int64_t)y * H.w + x0) * 3;
-            const int nb = nx * 3;
-            const int head = min(nb, (int)((16 - (reinterpret_cast<uintptr_t>(optr) & 15)) & 15));
-            const int nv = (nb - head) / 16;
-            for (int v = tid; v < nv; v += 256) {
-                const int b0 = head + 16 * v;
-                uint32_t wd[4] = {0, 0, 0, 0};
-#pragma unroll
-                for (int b = 0; b < 16; ++b) wd[b >> 2] |= (uint32_t)seg[b0 + b] << (8 * (b & 3));
-                *reinterpret_cast<uint4*>(optr + b0) = make_uint4(wd[0], wd[1], wd[2], wd[3]);
-            }
-            const int tail0 = head + 16 * nv;
-            for (int b = tid; b < head + (nb - tail0); b += 256) {
-                const int q = b < head ? b : tail0 + (b - head);
-                optr[q] = seg[q];
-            }
+            store_segment(dst + ((int64_t)y * H.w + x0) * 3, nx * 3, tid, [&](int q) -> uint32_t { return seg[q]; });
         }
     }
 }
@@ -316,20 +255,19 @@ void launch_gif_decode(const GifWs& ws, int n, const uint8_t* d_data, const uint
                        uint8_t* d_out, uint64_t out_stride, int32_t* d_status, int32_t* d_dims, hipStream_t st,
                        StageHook* hook) {
     if (n <= 0) return;
-    auto B = [&](Stage s) { if (hook) hook->begin(s, st); };
-    auto E = [&](Stage s) { if (hook) hook->end(s, st); };
+    const Stages S{hook, st};
     const int nb = (n + 63) / 64;
-    B(kStParse);
+    S.begin(kStParse);
     hipLaunchKernelGGL(k_gif_parse, dim3(nb), dim3(64), 0, st, n, d_data, d_off, d_size, ws.desc, ws.max_w, ws.max_h);
-    E(kStParse);
-    B(kStEntropy);
+    S.end(kStParse);
+    S.begin(kStEntropy);
     hipLaunchKernelGGL(k_gif_lzw, dim3(n), dim3(64), 0, st, d_data, d_off, ws.desc, ws.plane, (uint64_t)ws.plane_stride);
-    E(kStEntropy);
-    B(kStConvert);
-    hipLaunchKernelGGL(k_gif_render, dim3(std::max(1, std::min(ws.max_h, 16384 / std::min(n, 16384))), n), dim3(256), 0, st,
+    S.end(kStEntropy);
+    S.begin(kStConvert);
+    hipLaunchKernelGGL(k_gif_render, dim3(rows_grid(ws.max_h, n), n), dim3(256), 0, st,
                        d_data, d_off, ws.desc, ws.plane, (uint64_t)ws.plane_stride, d_out, out_stride);
     hipLaunchKernelGGL(k_gif_finish, dim3(nb), dim3(64), 0, st, n, ws.desc, d_status, d_dims);
-    E(kStConvert);
+    S.end(kStConvert);
 }
 
 }  // namespace icx

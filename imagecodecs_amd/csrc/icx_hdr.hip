@@ -414,6 +414,7 @@ __global__ __launch_bounds__(256) void k_hdr_unpack(const uint8_t* __restrict__ 
                     lim = base + kHdrWin - 129;
                     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
                     __builtin_amdgcn_wave_barrier();
+                    // (icx_wave.h's fill_window written out: its loop came out rolled here, 411 instructions for 841)
 #pragma unroll
                     for (int q = 0; q < kHdrWin / (64 * 16); ++q) {
                         const int o = (q * 64 + lane) * 16;
@@ -556,14 +557,13 @@ void launch_hdr_decode(const HdrWs& ws, int n, const uint8_t* d_data, const uint
                        float* d_out, uint64_t out_stride, int32_t* d_status, int32_t* d_dims, hipStream_t st,
                        StageHook* hook) {
     if (n <= 0) return;
-    auto B = [&](Stage s) { if (hook) hook->begin(s, st); };
-    auto E = [&](Stage s) { if (hook) hook->end(s, st); };
+    const Stages S{hook, st};
     const int nb = (n + 63) / 64;
     const int gx = std::max(1, std::min(2048, 16384 / n));
-    B(kStParse);
+    S.begin(kStParse);
     hipLaunchKernelGGL(k_hdr_parse, dim3(nb), dim3(64), 0, st, n, d_data, d_off, d_size, ws.desc, ws.max_w, ws.max_h);
-    E(kStParse);
-    B(kStUnstuff);  // locating the scanlines
+    S.end(kStParse);
+    S.begin(kStUnstuff);  // locating the scanlines
     hipLaunchKernelGGL(k_hdr_scan, dim3(gx, n), dim3(256), 0, st, d_data, d_off, ws.desc, ws.cq, ws.ce);
     hipLaunchKernelGGL(k_hdr_candwalk, dim3(kHdrCandCap / 256, n), dim3(256), 0, st, d_data, d_off, ws.desc, ws.cq,
                        ws.ce);
@@ -572,16 +572,16 @@ void launch_hdr_decode(const HdrWs& ws, int n, const uint8_t* d_data, const uint
     hipLaunchKernelGGL(k_hdr_link, dim3(n), dim3(1024), 0, st, ws.desc, ws.cq, ws.ce, ws.start, ws.max_h);
     hipLaunchKernelGGL(k_hdr_walk, dim3(nb), dim3(64), 0, st, n, d_data, d_off, ws.desc, ws.start, ws.kind, ws.planes,
                        ws.max_w, ws.max_h);
-    E(kStUnstuff);
-    B(kStEntropy);  // run-length decoding
+    S.end(kStUnstuff);
+    S.begin(kStEntropy);  // run-length decoding
     hipLaunchKernelGGL(k_hdr_unpack, dim3(std::max(1, std::min(gx, (ws.max_h + 3) / 4)), n), dim3(256), 0, st, d_data,
                        d_off, ws.desc, ws.start, ws.kind, ws.planes, ws.max_w, ws.max_h);
-    E(kStEntropy);
-    B(kStConvert);
+    S.end(kStEntropy);
+    S.begin(kStConvert);
     hipLaunchKernelGGL(k_hdr_convert, dim3(std::max(1, std::min(gx, ws.max_h)), n), dim3(256), 0, st, d_data, d_off,
                        ws.desc, ws.start, ws.kind, ws.planes, d_out, out_stride, ws.max_w, ws.max_h);
     hipLaunchKernelGGL(k_hdr_finish, dim3(nb), dim3(64), 0, st, n, ws.desc, d_status, d_dims);
-    E(kStConvert);
+    S.end(kStConvert);
 }
 
 }  // namespace icx

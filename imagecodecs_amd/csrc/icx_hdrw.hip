@@ -25,6 +25,7 @@
 #include "icx_hdrw_core.h"
 #include "icx_internal.h"
 #include "icx_mem.h"
+#include "icx_wave.h"
 
 namespace icx {
 
@@ -249,12 +250,7 @@ __global__ __launch_bounds__(64) void k_hdrw_prefix(HdrwJob* __restrict__ jobs, 
 #pragma unroll
                 for (int c = 0; c < 4; ++c) s[c] = psz[4 * (J.row0 + y) + c];
             const uint64_t v = y < J.h ? 4ull + s[0] + s[1] + s[2] + s[3] : 0;
-            uint64_t incl = v;
-#pragma unroll
-            for (int d = 1; d < 64; d <<= 1) {
-                const uint64_t t = __shfl_up(incl, d);
-                if (lane >= d) incl += t;
-            }
+            const uint64_t incl = wave_sum_scan(v, lane);
             if (y < J.h) {
                 uint64_t at = total + incl - v + 4;
 #pragma unroll
@@ -328,15 +324,8 @@ int hdr_encode_batch(hipStream_t st, HdrwWs& ws, int n, const float* const* d_sr
         plane_bytes += 4ull * J.wp * J.h;
         max_h_packed = std::max(max_h_packed, J.h);
     }
-    auto fail = [&](const char* what) {
-        err = std::string(what) + ": " + hipGetErrorString(hipGetLastError());
-        return -1;
-    };
-    if (!ws.jobs.reserve(jobs.size() * sizeof(HdrwJob)) || !ws.planes.reserve(plane_bytes) || !ws.psz.reserve(rows * 16) ||
-        !ws.poff.reserve(rows * 32))
-        return fail("hdr_encode_batch: allocation");
-    if (hipMemcpyAsync(ws.jobs.p, jobs.data(), jobs.size() * sizeof(HdrwJob), hipMemcpyHostToDevice, st) != hipSuccess)
-        return fail("hdr_encode_batch: copy");
+    const bool rest = ws.planes.reserve(plane_bytes) && ws.psz.reserve(rows * 16) && ws.poff.reserve(rows * 32);
+    if (jobs_upload("hdr_encode_batch", ws.jobs, jobs, st, err, rest)) return -1;
     const int cap = std::max(1, 16384 / std::min(n, 16384));  // blocks per image
     const dim3 g_rows(std::max(1, std::min(max_h_packed, cap)), n), g_planes(std::max(1, std::min(max_h_packed, cap)), n);
     if (max_h_packed) {
@@ -354,14 +343,7 @@ int hdr_encode_batch(hipStream_t st, HdrwWs& ws, int n, const float* const* d_sr
         if (d == 4) hipLaunchKernelGGL(k_hdrw_flat<4>, g_flat, dim3(256), 0, st, ws.jobs.p, d_out, out_stride);
         else hipLaunchKernelGGL(k_hdrw_flat<3>, g_flat, dim3(256), 0, st, ws.jobs.p, d_out, out_stride);
     }
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        err = std::string("hdr_encode_batch: ") + hipGetErrorString(e);
-        return -1;
-    }
-    return 0;
+    return encode_finish("hdr_encode_batch", st, err);
 }
 
 }  // namespace icx

@@ -215,6 +215,44 @@ struct StageHook {
     virtual void end(Stage s, hipStream_t st) = 0;
     virtual ~StageHook() = default;
 };
+// A launcher's hook (may be null) and stream.
+struct Stages {
+    StageHook* h;
+    hipStream_t st;
+    void begin(Stage s) const { if (h) h->begin(s, st); }
+    void end(Stage s) const { if (h) h->end(s, st); }
+};
+// Workgroups per image of a kernel that takes rows in turn: at most max_h, about 16384 in all:
+// max(1, min(max_h, 16384 / min(n, 16384))).
+inline int rows_grid(int max_h, int n) {
+    const int cap = n < 16384 ? 16384 / n : 1;
+    return max_h < 1 ? 1 : max_h < cap ? max_h : cap;
+}
+
+// The two ends of a *_encode_batch (name: the entry's, for err); 0, or -1 with err set.
+// jobs_upload: room for the job array in buf (a Buf<J>, icx_mem.h) and its copy to the device on st
+// (the pageable array is read until encode_finish has synchronised). rest_ok: the writer's other
+// buffers are reserved.
+template <class B, class J>
+int jobs_upload(const char* name, B& buf, const std::vector<J>& jobs, hipStream_t st, std::string& err, bool rest_ok = true) {
+    const size_t bytes = jobs.size() * sizeof(J);
+    const char* what = !rest_ok || !buf.reserve(bytes) ? ": allocation: " : nullptr;
+    if (!what && hipMemcpyAsync(buf.p, jobs.data(), bytes, hipMemcpyHostToDevice, st) != hipSuccess) what = ": copy: ";
+    if (!what) return 0;
+    (err = name) += what;
+    err += hipGetErrorString(hipGetLastError());
+    return -1;
+}
+// encode_finish: the launches' error, or the stream's once everything queued on it has run.
+inline int encode_finish(const char* name, hipStream_t st, std::string& err) {
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e == hipSuccess) return 0;
+    (void)hipGetLastError();
+    (err = name) += ": ";
+    err += hipGetErrorString(e);
+    return -1;
+}
 // The encoders' stage-time read-out: k = min(cap, n) names and accumulated ms copied out, every
 // accumulator zeroed; returns k.
 inline int stage_times_out(const char* const* stage, float* acc, int n, const char** names, float* ms, int cap) {

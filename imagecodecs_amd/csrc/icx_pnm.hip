@@ -35,6 +35,7 @@
 #include "icx_internal.h"
 #include "icx_mem.h"
 #include "icx_pnm_core.h"
+#include "icx_wave.h"
 
 namespace icx {
 
@@ -67,31 +68,6 @@ struct PnmDesc {
     int64_t last_start;  // k_pnm_convert: file offset of the last needed sample's token
     PnmStream S;         // binary types
 };
-
-// win[0, len) = file bytes [base, base + len), zero outside [0, fsize). d + base is 16-byte
-// aligned, len a multiple of 16, win 16-byte aligned. Bytes outside the file are never read.
-__device__ __forceinline__ void pnm_fill(uint8_t* win, const uint8_t* d, int64_t fsize, int64_t base, int len, int tid,
-                                         int nthreads) {
-    for (int o = tid * 16; o < len; o += nthreads * 16) {
-        const int64_t a = base + o;
-        uint4 v = make_uint4(0, 0, 0, 0);
-        if (a >= 0 && a + 16 <= fsize) {
-            v = *reinterpret_cast<const uint4*>(d + a);
-        } else {
-            uint32_t t[4] = {0, 0, 0, 0};
-            for (int b = 0; b < 16; ++b)
-                if (a + b >= 0 && a + b < fsize) t[b >> 2] |= (uint32_t)d[a + b] << (8 * (b & 3));
-            v = make_uint4(t[0], t[1], t[2], t[3]);
-        }
-        *reinterpret_cast<uint4*>(win + o) = v;
-    }
-}
-
-__device__ __forceinline__ void pnm_wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 __global__ void k_pnm_parse(int n, const uint8_t* __restrict__ data, const uint64_t* __restrict__ off,
                             const uint64_t* __restrict__ size, PnmDesc* __restrict__ desc, uint8_t* __restrict__ out,
@@ -182,9 +158,9 @@ __global__ __launch_bounds__(256) void k_pnm_tiles(const uint8_t* __restrict__ d
     for (int t = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6)); t < ntiles; t += gridDim.x * 4) {
         const int64_t tile0 = dd.H.rs + (int64_t)t * kPnmTile;
         const int mis = (int)(reinterpret_cast<uintptr_t>(d + tile0) & 15);
-        pnm_wave_sync();  // the previous tile's readers are done
-        pnm_fill(win, d, n, tile0 - mis, kPnmTile + 16, lane, 64);
-        pnm_wave_sync();
+        wave_sync();  // the previous tile's readers are done
+        fill_window(win, d, n, tile0 - mis, kPnmTile + 16, lane, 64);
+        wave_sync();
         const int avail = (int)min<int64_t>(n - tile0, kPnmTile);
         const int prev0 = t > 0 ? d[tile0 - 1] : ' ';
         bool carry = false, seen_nl = false;  // as if the tile started outside a comment
@@ -280,9 +256,9 @@ __global__ __launch_bounds__(256) void k_pnm_convert(const uint8_t* __restrict__
     for (int t = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6)); t <= last; t += gridDim.x * 4) {
         const int64_t tile0 = H.rs + (int64_t)t * kPnmTile;
         const int mis = (int)(reinterpret_cast<uintptr_t>(d + tile0) & 15);
-        pnm_wave_sync();  // the previous tile's readers are done
-        pnm_fill(win, d, n, tile0 - mis, kPnmTile + 32, lane, 64);
-        pnm_wave_sync();
+        wave_sync();  // the previous tile's readers are done
+        fill_window(win, d, n, tile0 - mis, kPnmTile + 32, lane, 64);
+        wave_sync();
         const int avail = (int)min<int64_t>(n - tile0, kPnmTile);
         const int wlen = kPnmTile + 32 - mis;  // tile bytes [0, wlen) are in the window (zero past the file's end)
         const int prev0 = t > 0 ? d[tile0 - 1] : ' ';
@@ -377,7 +353,7 @@ __device__ __forceinline__ void pnm_stream_mode(const PnmStream& J, uint8_t* win
         const int64_t s0 = J.src_off + sy * J.row_src + sg * kSegSrc;
         const int mis = (int)(reinterpret_cast<uintptr_t>(J.src + s0) & 15);
         __syncthreads();  // the previous segment's readers are done
-        pnm_fill(win, J.src, J.src_size, s0 - mis, (mis + ns + 15) & ~15, tid, 256);
+        fill_window(win, J.src, J.src_size, s0 - mis, (mis + ns + 15) & ~15, tid, 256);
         __syncthreads();
         const uint8_t* seg = win + mis;
         constexpr int kOut = MODE == kPnmPack ? kPnmCopy : MODE;
@@ -387,21 +363,7 @@ __device__ __forceinline__ void pnm_stream_mode(const PnmStream& J, uint8_t* win
             __syncthreads();
             seg = aux;
         }
-        uint8_t* optr = J.dst + y * J.row_out + sg * kSegOut;
-        const int head = min(nb, (int)((16 - (reinterpret_cast<uintptr_t>(optr) & 15)) & 15));
-        const int nv = (nb - head) / 16;
-        for (int v = tid; v < nv; v += 256) {
-            const int q0 = head + 16 * v;
-            uint32_t wd[4] = {0, 0, 0, 0};
-#pragma unroll
-            for (int b = 0; b < 16; ++b) wd[b >> 2] |= pnm_byte_at<kOut>(seg, q0 + b, ns) << (8 * (b & 3));
-            *reinterpret_cast<uint4*>(optr + q0) = make_uint4(wd[0], wd[1], wd[2], wd[3]);
-        }
-        const int tail0 = head + 16 * nv;
-        for (int b = tid; b < head + (nb - tail0); b += 256) {
-            const int q = b < head ? b : tail0 + (b - head);
-            optr[q] = (uint8_t)pnm_byte_at<kOut>(seg, q, ns);
-        }
+        store_segment(J.dst + y * J.row_out + sg * kSegOut, nb, tid, [&](int q) { return pnm_byte_at<kOut>(seg, q, ns); });
     }
 }
 
@@ -495,32 +457,31 @@ void launch_pnm_decode(const PnmWs& ws, int n, const uint8_t* d_data, const uint
                        uint8_t* d_out, uint64_t out_stride, int32_t* d_status, int32_t* d_dims, hipStream_t st,
                        StageHook* hook) {
     if (n <= 0) return;
-    auto B = [&](Stage s) { if (hook) hook->begin(s, st); };
-    auto E = [&](Stage s) { if (hook) hook->end(s, st); };
+    const Stages S{hook, st};
     const int nb = (n + 63) / 64;
     // (few images: a workgroup per 4 tiles; many: each workgroup takes several groups in turn, so
     // that a batch without text files does not pay for a grid of empty workgroups)
     const unsigned tiles = (unsigned)std::min<int64_t>((ws.tiles_cap + 3) / 4, 16384 / std::min(n, 16384));
-    B(kStParse);
+    S.begin(kStParse);
     hipLaunchKernelGGL(k_pnm_parse, dim3(nb), dim3(64), 0, st, n, d_data, d_off, d_size, ws.desc, d_out, out_stride, ws.max_w,
                        ws.max_h, ws.tiles_cap);
-    E(kStParse);
-    B(kStUnstuff);  // locating the samples of text files
+    S.end(kStParse);
+    S.begin(kStUnstuff);  // locating the samples of text files
     if (tiles) {
         hipLaunchKernelGGL(k_pnm_tiles, dim3(tiles, n), dim3(256), 0, st, d_data, d_off, ws.desc, ws.summary,
                            ws.tiles_cap);
         hipLaunchKernelGGL(k_pnm_chain, dim3(n), dim3(256), 0, st, ws.desc, ws.summary, ws.tbase, ws.tiles_cap);
     }
-    E(kStUnstuff);
-    B(kStEntropy);  // text -> samples
+    S.end(kStUnstuff);
+    S.begin(kStEntropy);  // text -> samples
     if (tiles)
         hipLaunchKernelGGL(k_pnm_convert, dim3(tiles, n), dim3(256), 0, st, d_data, d_off, ws.desc, ws.tbase, d_out,
                            out_stride, ws.tiles_cap);
-    E(kStEntropy);
-    B(kStConvert);  // binary rasters
+    S.end(kStEntropy);
+    S.begin(kStConvert);  // binary rasters
     hipLaunchKernelGGL(k_pnm_stream, dim3(pnm_stream_blocks((int64_t)ws.max_w * ws.max_h * 12, n), n), dim3(256), 0, st, ws.desc);
     hipLaunchKernelGGL(k_pnm_finish, dim3(nb), dim3(64), 0, st, n, ws.desc, d_status, d_dims);
-    E(kStConvert);
+    S.end(kStConvert);
 }
 
 struct PnmwWs {
@@ -573,23 +534,10 @@ int pnm_encode_batch(hipStream_t st, PnmwWs& ws, int n, const uint8_t* const* d_
         }
         max_bytes = std::max(max_bytes, std::max(payload, S.src_size));
     }
-    auto fail = [&](const char* what) {
-        err = std::string(what) + ": " + hipGetErrorString(hipGetLastError());
-        return -1;
-    };
-    if (!ws.jobs.reserve(jobs.size() * sizeof(PnmwJob))) return fail("pnm_encode_batch: allocation");
-    if (hipMemcpyAsync(ws.jobs.p, jobs.data(), jobs.size() * sizeof(PnmwJob), hipMemcpyHostToDevice, st) != hipSuccess)
-        return fail("pnm_encode_batch: copy");
+    if (jobs_upload("pnm_encode_batch", ws.jobs, jobs, st, err)) return -1;
     hipLaunchKernelGGL(k_pnmw_head, dim3((n + 63) / 64), dim3(64), 0, st, n, ws.jobs.p, d_out, out_stride, d_sizes, d_status);
     hipLaunchKernelGGL(k_pnmw_stream, dim3(pnm_stream_blocks(max_bytes, n), n), dim3(256), 0, st, ws.jobs.p);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipStreamSynchronize(st);  // (jobs is read by the copy until here)
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        err = std::string("pnm_encode_batch: ") + hipGetErrorString(e);
-        return -1;
-    }
-    return 0;
+    return encode_finish("pnm_encode_batch", st, err);
 }
 
 }  // namespace icx

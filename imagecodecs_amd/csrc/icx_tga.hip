@@ -37,6 +37,7 @@
 #include "icx_internal.h"
 #include "icx_mem.h"
 #include "icx_tga_core.h"
+#include "icx_wave.h"
 
 namespace icx {
 
@@ -59,25 +60,6 @@ struct TgaDesc {
                      // kTgaPending until k_tga_finish folds it in, so no kernel reads a field
                      // that another workgroup of the same launch writes
 };
-
-// win[0, len) = file bytes [base, base + len), zero outside [0, fsize). d + base is 16-byte
-// aligned, len a multiple of 16, win 16-byte aligned. Bytes outside the file are never read.
-__device__ __forceinline__ void tga_fill(uint8_t* win, const uint8_t* d, int64_t fsize, int64_t base, int len, int tid,
-                                         int nthreads) {
-    for (int o = tid * 16; o < len; o += nthreads * 16) {
-        const int64_t a = base + o;
-        uint4 v = make_uint4(0, 0, 0, 0);
-        if (a >= 0 && a + 16 <= fsize) {
-            v = *reinterpret_cast<const uint4*>(d + a);
-        } else {
-            uint32_t t[4] = {0, 0, 0, 0};
-            for (int b = 0; b < 16; ++b)
-                if (a + b >= 0 && a + b < fsize) t[b >> 2] |= (uint32_t)d[a + b] << (8 * (b & 3));
-            v = make_uint4(t[0], t[1], t[2], t[3]);
-        }
-        *reinterpret_cast<uint4*>(win + o) = v;
-    }
-}
 
 __global__ void k_tga_parse(int n, const uint8_t* __restrict__ data, const uint64_t* __restrict__ off,
                             const uint64_t* __restrict__ size, TgaDesc* __restrict__ desc, int max_w, int max_h,
@@ -116,7 +98,7 @@ __global__ __launch_bounds__(256) void k_tga_tiles(const uint8_t* __restrict__ d
     const int64_t n = dd.size, tile0 = dd.H.ds + (int64_t)t * kTgaTile;
     const int bpp = dd.H.bpp;
     const int mis = (int)(reinterpret_cast<uintptr_t>(d + tile0) & 15);
-    tga_fill(win, d, n, tile0 - mis, kTgaTile + 16, threadIdx.x, 256);
+    fill_window(win, d, n, tile0 - mis, kTgaTile + 16, threadIdx.x, 256);
     __syncthreads();
     constexpr int kPer = kTgaTile / 256;
     constexpr uint16_t kFail = 0xFFFF;
@@ -243,10 +225,8 @@ __global__ __launch_bounds__(256) void k_tga_expand(const uint8_t* __restrict__ 
     const int64_t n = dd.size, tile0 = H.ds + (int64_t)t * kTgaTile, npix = (int64_t)H.w * H.h;
     uint8_t* win = win_all[threadIdx.x >> 6];
     const int mis = (int)(reinterpret_cast<uintptr_t>(d + tile0) & 15);
-    tga_fill(win, d, n, tile0 - mis, kTgaWin, lane, 64);
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    fill_window(win, d, n, tile0 - mis, kTgaWin, lane, 64);
+    wave_sync();
     uint16_t* pk_pos = pk_pos_all[threadIdx.x >> 6];
     uint32_t* pk_end = pk_end_all[threadIdx.x >> 6];
     int pos = __builtin_amdgcn_readfirstlane(entry[(int64_t)i * tiles_cap + t]);
@@ -273,9 +253,7 @@ __global__ __launch_bounds__(256) void k_tga_expand(const uint8_t* __restrict__ 
             ++np;
             pos += 1 + payload;
         }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wave_sync();
         // their pixels, one per lane: the packet of pixel q is the first whose end is past q
         for (uint32_t q = lane; q < cum; q += 64) {
             int lo = 0, hi = np - 1;
@@ -290,9 +268,7 @@ __global__ __launch_bounds__(256) void k_tga_expand(const uint8_t* __restrict__ 
             tga_store_px(H, map, src, o + tga_out_index(H, P + q) * H.d);
         }
         P += cum;
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();  // the table is read before the next chunk overwrites it
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wave_sync();  // the table is read before the next chunk overwrites it
     }
     if (t == dd.last && lane == 0) dd.verdict = over ? kTgaMalformed : P == npix ? kTgaOk : kTgaTruncated;
 }
@@ -321,9 +297,10 @@ __device__ __forceinline__ void tga_stream_rows(const TgaHead& H, const uint8_t*
             const int64_t s0 = H.ds + ((int64_t)fy * H.w + x0) * bpp;
             const int mis = (int)(reinterpret_cast<uintptr_t>(file + s0) & 15);
             __syncthreads();  // the previous segment's readers are done
-            tga_fill(win, file, fsize, s0 - mis, (mis + nx * bpp + 15) & ~15, tid, 256);
+            fill_window(win, file, fsize, s0 - mis, (mis + nx * bpp + 15) & ~15, tid, 256);
             __syncthreads();
             const uint8_t* seg = win + mis;
+            // (icx_wave.h's store_segment written out: b0 / d once per 16 bytes, not once per byte)
             uint8_t* optr = dst + ((int64_t)y * H.w + x0) * d;
             const int nb = nx * d;
             const int head = min(nb, (int)((16 - (reinterpret_cast<uintptr_t>(optr) & 15)) & 15));
@@ -382,23 +359,6 @@ struct TgaJob {
     int32_t status, pad_;
     uint64_t row0;  // the image's first row in TgawWs::rowoff
 };
-
-__device__ __forceinline__ int wave_max_scan(int v, int lane) {
-#pragma unroll
-    for (int s = 1; s < 64; s <<= 1) {
-        const int t = __shfl_up(v, s);
-        if (lane >= s) v = max(v, t);
-    }
-    return v;
-}
-__device__ __forceinline__ uint32_t wave_sum_scan(uint32_t v, int lane) {
-#pragma unroll
-    for (int s = 1; s < 64; s <<= 1) {
-        const uint32_t t = __shfl_up(v, s);
-        if (lane >= s) v += t;
-    }
-    return v;
-}
 
 // tga_pack_row in parallel form, one wave per row, 64 pixels at a time. With o = a pixel's offset in
 // its stretch of equal pixels and eq = "equals its right neighbour": a pixel is in a run packet
@@ -476,12 +436,7 @@ __global__ __launch_bounds__(64) void k_tgaw_prefix(TgaJob* __restrict__ jobs, i
         total = 0;
         for (int y0 = 0; y0 < J.h; y0 += 64) {
             const int y = y0 + lane;
-            uint64_t v = y < J.h ? rowoff[J.row0 + y] : 0, incl = v;
-#pragma unroll
-            for (int s = 1; s < 64; s <<= 1) {
-                const uint64_t t = __shfl_up(incl, s);
-                if (lane >= s) incl += t;
-            }
+            const uint64_t v = y < J.h ? rowoff[J.row0 + y] : 0, incl = wave_sum_scan(v, lane);
             if (y < J.h) rowoff[J.row0 + y] = 18 + total + incl - v;
             total += __shfl(incl, 63);
         }
@@ -542,30 +497,29 @@ void launch_tga_decode(const TgaWs& ws, int n, const uint8_t* d_data, const uint
                        uint8_t* d_out, uint64_t out_stride, int32_t* d_status, int32_t* d_dims, hipStream_t st,
                        StageHook* hook) {
     if (n <= 0) return;
-    auto B = [&](Stage s) { if (hook) hook->begin(s, st); };
-    auto E = [&](Stage s) { if (hook) hook->end(s, st); };
+    const Stages S{hook, st};
     const int nb = (n + 63) / 64;
     const unsigned tiles = (unsigned)ws.tiles_cap;
-    B(kStParse);
+    S.begin(kStParse);
     hipLaunchKernelGGL(k_tga_parse, dim3(nb), dim3(64), 0, st, n, d_data, d_off, d_size, ws.desc, ws.max_w, ws.max_h,
                        ws.tiles_cap);
-    E(kStParse);
-    B(kStUnstuff);  // locating the packets
+    S.end(kStParse);
+    S.begin(kStUnstuff);  // locating the packets
     if (tiles) {
         hipLaunchKernelGGL(k_tga_tiles, dim3(tiles, n), dim3(256), 0, st, d_data, d_off, ws.desc, ws.summary, ws.tiles_cap);
         hipLaunchKernelGGL(k_tga_chain, dim3(n), dim3(256), 0, st, ws.desc, ws.summary, ws.entry, ws.pbase, ws.tiles_cap);
     }
-    E(kStUnstuff);
-    B(kStEntropy);  // run-length decoding
+    S.end(kStUnstuff);
+    S.begin(kStEntropy);  // run-length decoding
     if (tiles)
         hipLaunchKernelGGL(k_tga_expand, dim3((tiles + 3) / 4, n), dim3(256), 0, st, d_data, d_off, ws.desc, ws.entry,
                            ws.pbase, d_out, out_stride, ws.tiles_cap);
-    E(kStEntropy);
-    B(kStConvert);  // raw files
-    hipLaunchKernelGGL(k_tga_raw, dim3(std::max(1, std::min(ws.max_h, 16384 / std::min(n, 16384))), n), dim3(256), 0, st,
+    S.end(kStEntropy);
+    S.begin(kStConvert);  // raw files
+    hipLaunchKernelGGL(k_tga_raw, dim3(rows_grid(ws.max_h, n), n), dim3(256), 0, st,
                        d_data, d_off, ws.desc, d_out, out_stride);
     hipLaunchKernelGGL(k_tga_finish, dim3(nb), dim3(64), 0, st, n, ws.desc, d_status, d_dims);
-    E(kStConvert);
+    S.end(kStConvert);
 }
 
 struct TgawWs {
@@ -593,14 +547,8 @@ int tga_encode_batch(hipStream_t st, TgawWs& ws, int n, const uint8_t* const* d_
         rows += (uint64_t)J.h;
         max_h = std::max(max_h, J.h);
     }
-    auto fail = [&](const char* what) {
-        err = std::string(what) + ": " + hipGetErrorString(hipGetLastError());
-        return -1;
-    };
-    if (!ws.jobs.reserve(jobs.size() * sizeof(TgaJob)) || !ws.rowoff.reserve((rows + 1) * 8)) return fail("tga_encode_batch: allocation");
-    if (hipMemcpyAsync(ws.jobs.p, jobs.data(), jobs.size() * sizeof(TgaJob), hipMemcpyHostToDevice, st) != hipSuccess)
-        return fail("tga_encode_batch: copy");
-    const int gy = std::max(1, std::min(max_h, 16384 / std::min(n, 16384)));
+    if (jobs_upload("tga_encode_batch", ws.jobs, jobs, st, err, ws.rowoff.reserve((rows + 1) * 8))) return -1;
+    const int gy = rows_grid(max_h, n);
     if (rle) {
         const int gx = std::max(1, std::min((max_h + 3) / 4, 16384));
         hipLaunchKernelGGL(k_tgaw_rows, dim3(gx, n), dim3(256), 0, st, ws.jobs.p, d, ws.rowoff.p);
@@ -612,14 +560,7 @@ int tga_encode_batch(hipStream_t st, TgawWs& ws, int n, const uint8_t* const* d_
                            d_status);
         hipLaunchKernelGGL(k_tgaw_raw, dim3(gy, n), dim3(256), 0, st, ws.jobs.p, d, d_out, out_stride);
     }
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        err = std::string("tga_encode_batch: ") + hipGetErrorString(e);
-        return -1;
-    }
-    return 0;
+    return encode_finish("tga_encode_batch", st, err);
 }
 
 }  // namespace icx

@@ -32,7 +32,7 @@
 #include "icx_mem.h"
 #include "icx_tiff_core.h"
 #include "icx_inflate_wave.h"
-#include "icx_lzw_wave.h"
+#include "icx_wave.h"
 
 namespace icx {
 
@@ -107,9 +107,9 @@ __device__ __forceinline__ int tiff_lzw_wave(const uint8_t* __restrict__ s, int6
         const int64_t b_lo = (int64_t)(rd >> 3);
         if (b_lo < wbase || b_lo + kTiffWinNeed > wbase + kTiffWin) {
             wbase = b_lo - (int64_t)(reinterpret_cast<uintptr_t>(s + b_lo) & 15);
-            gif_wave_sync();  // the window's readers are done
-            gif_fill(win, s, cnt, wbase, kTiffWin, lane);
-            gif_wave_sync();
+            wave_sync();  // the window's readers are done
+            fill_window(win, s, cnt, wbase, kTiffWin, lane, 64);
+            wave_sync();
         }
         // 64 codes at once
         const uint32_t t = t0 + lane;
@@ -129,6 +129,7 @@ __device__ __forceinline__ int tiff_lzw_wave(const uint8_t* __restrict__ s, int6
         const int m0 = evmask ? __builtin_ctzll(evmask) : 64;
         const bool act = lane < m0;
 
+        // (icx_lzw_wave.h's round written out: shared, it moved this kernel's deflate path by 1.1 %)
         // string length L and first byte F of every code before the event
         uint32_t A = 0;
         int D = -1, F = 0;
@@ -145,7 +146,7 @@ __device__ __forceinline__ int tiff_lzw_wave(const uint8_t* __restrict__ s, int6
             if (D >= 0) { A += a2; F = f2; D = d2; }
         }
         const uint32_t L = A;
-        const uint32_t incl = gif_wave_sum_scan(L, lane), excl = incl - L;
+        const uint32_t incl = wave_sum_scan(L, lane), excl = incl - L;
         const uint32_t rem = want - base;
         const bool need = act && excl < rem;  // the code starts before the last byte: a prefix of the lanes
         const int m = __popcll(__ballot(need));
@@ -158,7 +159,7 @@ __device__ __forceinline__ int tiff_lzw_wave(const uint8_t* __restrict__ s, int6
             tab[clear + 1 + t] = (uint32_t)pc | (uint32_t)(F & 255) << 12 | (pL + 1) << 20;
             first[clear + 1 + t] = (uint8_t)pF;
         }
-        gif_wave_sync();
+        wave_sync();
 
         // every lane walks its own string back to front
         if (need) {
@@ -176,7 +177,7 @@ __device__ __forceinline__ int tiff_lzw_wave(const uint8_t* __restrict__ s, int6
                 if (k == 0) break;
             }
         }
-        gif_wave_sync();  // the table is read before the next round's entries go in
+        wave_sync();  // the table is read before the next round's entries go in
 
         if (m > 0) {
             const uint32_t total = __shfl(incl, m - 1);
@@ -258,12 +259,12 @@ __global__ __launch_bounds__(64) void k_tiff_unpack(int n, const uint8_t* __rest
         } else if (comp == 1) {
             if (cnt < (int64_t)c.want) rc = kTiffBadData;
         } else if (comp == 5) {
-            gif_wave_sync();  // the previous item's LDS readers are done
+            wave_sync();  // the previous item's LDS readers are done
             rc = tiff_lzw_wave(f + coff, cnt, dst, c.want, reinterpret_cast<uint32_t*>(lds), lds + 4096 * 4, lds + 4096 * 5, lane);
         } else if (comp == 32773) {
             rc = tiff_packbits_wave(f + coff, cnt, dst, c.want, lane);
         } else {
-            gif_wave_sync();
+            wave_sync();
             int64_t m = 0;
             const bool ok = exr_inflate_wave<kTiffInfWin>(f + coff, cnt, dst, (int64_t)c.want, &m, *reinterpret_cast<InfState*>(lds + kTiffInfWin),
                                                           lds);
@@ -353,22 +354,7 @@ __global__ __launch_bounds__(256) void k_tiff_render(const uint8_t* __restrict__
                     if (d == 4) seg[d * p + 3] = (uint8_t)(v >> 24);
                 }
                 __syncthreads();
-                uint8_t* optr = dst + ((int64_t)y * H.w + c.x0 + xs) * d;
-                const int nb = nx * d;
-                const int head = min(nb, (int)((16 - (reinterpret_cast<uintptr_t>(optr) & 15)) & 15));
-                const int nv = (nb - head) / 16;
-                for (int v = tid; v < nv; v += 256) {
-                    const int b0 = head + 16 * v;
-                    uint32_t wd[4] = {0, 0, 0, 0};
-#pragma unroll
-                    for (int b = 0; b < 16; ++b) wd[b >> 2] |= (uint32_t)seg[b0 + b] << (8 * (b & 3));
-                    *reinterpret_cast<uint4*>(optr + b0) = make_uint4(wd[0], wd[1], wd[2], wd[3]);
-                }
-                const int tail0 = head + 16 * nv;
-                for (int b = tid; b < head + (nb - tail0); b += 256) {
-                    const int q = b < head ? b : tail0 + (b - head);
-                    optr[q] = seg[q];
-                }
+                store_segment(dst + ((int64_t)y * H.w + c.x0 + xs) * d, nx * d, tid, [&](int q) -> uint32_t { return seg[q]; });
             }
         }
     }
@@ -418,23 +404,22 @@ void launch_tiff_decode(const TiffWs& ws, int n, const uint8_t* d_data, const ui
                         uint8_t* d_out, uint64_t out_stride, int32_t* d_status, int32_t* d_dims, hipStream_t st,
                         StageHook* hook) {
     if (n <= 0) return;
-    auto B = [&](Stage s) { if (hook) hook->begin(s, st); };
-    auto E = [&](Stage s) { if (hook) hook->end(s, st); };
+    const Stages S{hook, st};
     const int nb = (n + 63) / 64;
-    B(kStParse);
+    S.begin(kStParse);
     hipLaunchKernelGGL(k_tiff_parse, dim3(nb), dim3(64), 0, st, n, d_data, d_off, d_size, ws.desc, ws.count, ws.max_w, ws.max_h,
                        (uint64_t)ws.slot);
     hipLaunchKernelGGL(k_tiff_scan, dim3(1), dim3(256), 0, st, n, ws.count, ws.first, ws.next);
-    E(kStParse);
-    B(kStEntropy);
+    S.end(kStParse);
+    S.begin(kStEntropy);
     hipLaunchKernelGGL(k_tiff_unpack, dim3(ws.unpack_grid), dim3(64), 0, st, n, d_data, d_off, ws.desc, ws.first, ws.next, ws.scratch,
                        (uint64_t)ws.slot);
-    E(kStEntropy);
-    B(kStConvert);
-    hipLaunchKernelGGL(k_tiff_render, dim3(std::max(1, std::min(ws.max_h, 16384 / std::min(n, 16384))), n), dim3(256), 0, st,
+    S.end(kStEntropy);
+    S.begin(kStConvert);
+    hipLaunchKernelGGL(k_tiff_render, dim3(rows_grid(ws.max_h, n), n), dim3(256), 0, st,
                        d_data, d_off, ws.desc, ws.scratch, (uint64_t)ws.slot, d_out, out_stride);
     hipLaunchKernelGGL(k_tiff_finish, dim3(nb), dim3(64), 0, st, n, ws.desc, d_status, d_dims);
-    E(kStConvert);
+    S.end(kStConvert);
 }
 
 }  // namespace icx

@@ -19,6 +19,7 @@ pytestmark = pytest.mark.gpu
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 FIXTURE = open(os.path.join(GOLDEN, "bmp", "test.bmp"), "rb").read()
 KBMP_TILE = 4096  # icx_bmp.hip kBmpTile: stream bytes per tile of k_bmp_tiles / k_bmp_expand
+KBMP_SEG = 1024   # kBmpSeg: pixels per row segment of the streaming kernels
 STAGES = {"parse", "locate", "fill", "expand", "raw"}
 
 
@@ -308,6 +309,40 @@ def test_bmp_encode_device_batch(ctx, d):
         assert sizes[i] == len(want) and slot[:len(want)].tobytes() == want, i
         assert (slot[len(want):] == 0xA5).all(), i
     assert (out[3 * stride:] == 0xA5).all()
+
+
+@pytest.mark.parametrize("pad", [1, 2, 3])
+def test_bmp_segment_edges_write_and_read(ctx, pad):
+    """1 x 1, 5 x 2 and (KBMP_SEG + 1) x 2, every channel count, the pixels at an odd device address
+    and the files' stride padded by 1, 2 or 3 bytes: file rows shorter than 16 bytes that start off
+    alignment, a ragged head before the 16-byte stores and a tail after them, a second row segment
+    of one pixel, and window loads whose first and last 16 bytes straddle the source's ends. The
+    files are then read back in one batch behind an odd number of bytes, slots padded the same."""
+    import torch
+    dev = torch.device("cuda", 0)
+    shapes = ((1, 1), (5, 2), (KBMP_SEG + 1, 2))
+    off = 2 * pad + 1
+    cases = [("odd", b"\xEE" * off)]  # (not a BMP: it only moves the files after it)
+    for d in (1, 3, 4):
+        imgs = [B.synth(30 * d + w, w, h, d) for w, h in shapes]
+        bufs = [torch.from_numpy(np.frombuffer(bytes(off) + p.tobytes(), np.uint8).copy()).to(dev) for p in imgs]
+        stride = B.encode_bound(KBMP_SEG + 1, 2, d) + pad
+        n = len(imgs)
+        out = torch.full((n * stride + 64,), 0xA5, dtype=torch.uint8, device=dev)
+        sizes = torch.zeros((n,), dtype=torch.int64, device=dev)
+        status = torch.full((n,), -9, dtype=torch.int32, device=dev)
+        torch.cuda.synchronize(dev)  # (the fills above are done before the context's stream writes)
+        rc = ctx.bmp_encode_device_batch([b.data_ptr() + off for b in bufs], [w for w, _ in shapes], [h for _, h in shapes], d,
+                                         out.data_ptr(), stride, sizes.data_ptr(), status.data_ptr())
+        assert rc == icx.BMP_OK and list(status.cpu().numpy()) == [icx.BMP_OK] * n
+        o = out.cpu().numpy()
+        for i, px in enumerate(imgs):
+            want = B.encode(px)
+            slot = o[i * stride:(i + 1) * stride]
+            assert slot[:len(want)].tobytes() == want and (slot[len(want):] == 0xA5).all(), (d, i)
+            cases.append((f"d{d}_{px.shape[1]}x{px.shape[0]}", want))
+        assert (o[n * stride:] == 0xA5).all()
+    _check_batch(ctx, cases, KBMP_SEG + 1, 2, pad)
 
 
 # ------------------------------------------------------------------------------------ icx.Image

@@ -190,6 +190,17 @@ def test_gif_batch_start_residues(ctx, shift):
     assert sum(r[0] != G.OK for r in res) > 10
 
 
+@pytest.mark.parametrize("pad", [1, 2, 3])
+def test_gif_batch_segment_edges(ctx, pad):
+    """1 x 1, 5 x 2 and (KGIF_SEG + 1) x 2, twice, the slots' stride padded by 1, 2 or 3 bytes, the data
+    an odd number of bytes into the buffer: rows shorter than 16 bytes that start off alignment, a
+    ragged head before the 16-byte stores and a tail after them, and a second row segment of one
+    pixel; the window load's first and last 16 bytes straddle the file's ends."""
+    files = [(f"{w}x{h}", G.simple_gif(G.noise(70 + w, h, w, 256), G.palette(256, 1))) for w, h in ((1, 1), (5, 2), (KGIF_SEG + 1, 2))]
+    res = _check_batch(ctx, files + files, KGIF_SEG + 1, 2, pad=pad, shift=2 * pad + 1)
+    assert all(r[0] == G.OK for r in res)
+
+
 def test_gif_too_large(ctx):
     data = G.simple_gif(G.noise(1, 9, 33, 4), G.palette(4))
     for mw, mh, want in ((33, 9, G.OK), (32, 9, G.TOO_LARGE), (33, 8, G.TOO_LARGE)):

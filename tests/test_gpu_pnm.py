@@ -316,6 +316,45 @@ def test_pnm_encode_unaligned_source(ctx):
             assert o[i * stride:i * stride + len(want)].tobytes() == want and (o[i * stride + len(want):(i + 1) * stride] == 0xA5).all(), (fmt, i)
 
 
+@pytest.mark.parametrize("pad", [1, 2, 3])
+def test_pnm_segment_edges_write_and_read(ctx, pad):
+    """1 x 1, 5 x 2 and 1025 x 2 in every index map of the streaming kernel, the pixels an odd number of
+    elements into their device buffer and the files' stride padded by 1, 2 or 3 bytes: payloads shorter than 16 bytes
+    that start off alignment, a ragged head before the 16-byte stores and a tail after them, a PFM
+    row whose second segment is one pixel (1025 floats, 4096 bytes per segment), and window loads
+    whose first and last 16 bytes straddle the source's ends. The files are then read back in one
+    batch behind an odd number of bytes (the read's slots are 16-byte aligned by contract)."""
+    import torch
+    dev = torch.device("cuda", 0)
+    shapes = ((1, 1), (5, 2), (1025, 2))
+    off = 2 * pad + 1
+    files = [b"\xEE" * off]  # (not a Netpbm file: it only moves the files after it)
+    for name, fmt, d, typ in WRITE_KINDS:
+        imgs = [U.bitmap(w + h, w, h) if fmt == U.P4 else U.synth(7 * w + h, w, h, d, typ) for w, h in shapes]
+        at = off * imgs[0].itemsize  # (an odd number of elements in)
+        bufs = [torch.from_numpy(np.frombuffer(bytes(at) + p.tobytes(), np.uint8).copy()).to(dev) for p in imgs]
+        want = [U.encode(p, fmt) for p in imgs]
+        stride = max(len(f) for f in want) + pad
+        n = len(imgs)
+        out = torch.full((n * stride + 64,), 0xA5, dtype=torch.uint8, device=dev)
+        sizes = torch.zeros((n,), dtype=torch.int64, device=dev)
+        status = torch.full((n,), -9, dtype=torch.int32, device=dev)
+        torch.cuda.synchronize(dev)  # (the fills above are done before the context's stream writes)
+        rc = ctx.pnm_encode_device_batch([b.data_ptr() + at for b in bufs], [w for w, _ in shapes], [h for _, h in shapes], d, typ,
+                                         fmt, out.data_ptr(), stride, sizes.data_ptr(), status.data_ptr())
+        assert rc == icx.PNM_OK and list(status.cpu().numpy()) == [0] * n, name
+        o = out.cpu().numpy()
+        for i, f in enumerate(want):
+            slot = o[i * stride:(i + 1) * stride]
+            assert slot[:len(f)].tobytes() == f and (slot[len(f):] == 0xA5).all(), (name, i)
+        assert (o[n * stride:] == 0xA5).all(), name
+        files += want
+    res, _ = _batch(ctx, files, 1025, 2)
+    for k, (f, got) in enumerate(zip(files, res)):
+        _same(got, f, f"edges{k}")
+    assert sum(r[0] == icx.PNM_OK for r in res) == len(files) - 1
+
+
 def test_pnm_fixture_ppm_written_back(ctx):
     f = FIXTURES["test.ppm"]
     got = ctx.pnm_decode(f)

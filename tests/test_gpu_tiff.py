@@ -258,6 +258,18 @@ def test_tiff_predictor_across_tile_edges(ctx):
     assert all(r[0] == T.OK for r in res)
 
 
+@pytest.mark.parametrize("pad", [1, 2, 3])
+def test_tiff_batch_segment_edges(ctx, pad):
+    """1 x 1, 5 x 2 and (KTIFF_SEG + 1) x 2, uncompressed and LZW, the slots' stride padded by 1, 2 or
+    3 bytes, the data an odd number of bytes into the buffer: rows shorter than 16 bytes that start
+    off alignment, a ragged head before the 16-byte stores and a tail after them, and a second row
+    segment of one pixel; the LZW window's first and last 16 bytes straddle the chunk's ends."""
+    files = [(f"{w}x{h}_{comp}", T.make_tiff(T.noise(w + comp, h, w, 3), comp=comp, rps=1))
+             for comp in (1, 5) for w, h in ((1, 1), (5, 2), (KTIFF_SEG + 1, 2))]
+    res = _check_batch(ctx, files, KTIFF_SEG + 1, 2, pad=pad, shift=2 * pad + 1)
+    assert all(r[0] == T.OK for r in res)
+
+
 def test_tiff_one_bad_chunk_fails_its_image_alone(ctx):
     a = T.smooth(5, 12, 40, 3)
     files = []
