@@ -861,8 +861,9 @@ __global__ __launch_bounds__(NL) void k_spec_write(int want, int n, const Desc* 
         // coefficient store and prefetch in flight -- on every DC code.
         asm volatile("" : "+v"(dc0), "+v"(dc1), "+v"(dc2));
         r.phase();  // the prelude above ran a lane-dependent number of lookups
-        // Wave-uniform loop: one lookup (one symbol or a pair) per active lane per iteration,
-        // then the wave flushes the blocks its lanes completed together -- eight 128-byte blocks
+        // Wave-uniform loop: one refill and one lookup (one symbol or a pair) per active lane per
+        // iteration, up to two further lookups of the same block while the window stays full, then
+        // the wave flushes the blocks its lanes completed together -- eight 128-byte blocks
         // per round, each lane moving one 16-byte chunk LDS -> HBM and zeroing it (coalesced
         // full-line stores, no divergent per-lane flush).
         // Active lanes as a wave mask (as in k_gw_lane): the loop test and the block counter's
@@ -885,9 +886,8 @@ __global__ __launch_bounds__(NL) void k_spec_write(int want, int n, const Desc* 
             // Bookkeeping by selects, not per-lane branches (each divergent `if` cost its exec-mask
             // save / restore and a branch in every iteration).
             const bool fail = (int32_t)u0 > err_peek || o.err || r.used > err_rel;
-            bad = bad || (act && fail);
-            const uint64_t okm = am & ~wave_ballot(fail);
-            const bool ok = lane_in(okm);
+            const uint64_t okm1 = am & ~wave_ballot(fail);
+            const bool ok = lane_in(okm1);
             const bool okdc = ok && dc;
             const int32_t pc = wadd(dc0, o.v1);
             dc0 = okdc ? pc : dc0;
@@ -904,6 +904,29 @@ __global__ __launch_bounds__(NL) void k_spec_write(int want, int n, const Desc* 
             // is never stored)
             sv[slot_elem(threadIdx.x, o.n2)] = (int16_t)(o.w2 ? o.v2 : 0);
             sv[slot_elem(threadIdx.x, o.n1)] = (int16_t)(dc ? cell : o.v1);
+            // Up to two further AC lookups of the same block out of a window that needs no refill
+            // (write_step_more: nb > 32, so one refill per iteration stays the reader's slot rule),
+            // each under the error-byte bounds, each decoded in a region of its own (as k_gw_lane's
+            // CHK instance does). A failure is noted in a VGPR, so no bool is merged across the
+            // regions; the block's DC, bcur and bi are the first lookup's.
+            int32_t fail2 = 0;
+            if (z != 0 && r.nb > 32) {
+                const uint32_t u1 = r.used;
+                const WriteOut o2 = write_step_more(r, T, H, S, b, z, (int32_t)u1 > err_pair);
+                fail2 = ((int32_t)u1 > err_peek || o2.err || r.used > err_rel) ? 1 : 0;
+                sv[slot_elem(threadIdx.x, o2.n2)] = (int16_t)(o2.w2 ? o2.v2 : 0);
+                sv[slot_elem(threadIdx.x, o2.n1)] = (int16_t)o2.v1;
+                if (z != 0 && r.nb > 32) {
+                    const uint32_t u2 = r.used;
+                    const WriteOut o3 = write_step_more(r, T, H, S, b, z, (int32_t)u2 > err_pair);
+                    fail2 |= ((int32_t)u2 > err_peek || o3.err || r.used > err_rel) ? 1 : 0;
+                    sv[slot_elem(threadIdx.x, o3.n2)] = (int16_t)(o3.w2 ? o3.v2 : 0);
+                    sv[slot_elem(threadIdx.x, o3.n1)] = (int16_t)o3.v1;
+                }
+            }
+            const uint64_t f2m = wave_ballot(fail2 != 0);
+            bad = bad || (act && (fail || lane_in(f2m)));
+            const uint64_t okm = okm1 & ~f2m;
             const uint64_t m = wave_ballot(z == 0) & okm;
             const bool done = lane_in(m);
             const int32_t bdone = bi;
@@ -983,8 +1006,8 @@ __global__ __launch_bounds__(NL) void k_spec_write(int want, int n, const Desc* 
 //     the start (g0), with the scan tables (runs of symbols per lookup; nothing is stored). The
 //     scan tables sit in the LDS the slots use later, so they cost no occupancy.
 //  2. k_spec_write's loop from g0 -- one refill and one lookup per lane per iteration, and a second
-//     lookup of the same block for lanes whose window holds the bits it uses without a refill
-//     (write_step_short; with the error-byte bounds, write_step_more's full windows alone); completed
+//     and a third lookup of the same block for lanes whose window holds the bits they use without a
+//     refill (write_step_short; the CHK instance: one further lookup, out of a full window alone); completed
 //     blocks assembled in LDS slots and flushed by the whole wave -- storing every block until the
 //     first block start at or after the lane's end (the exit), recording MCU starts for the
 //     count lanes' splice.
@@ -1163,10 +1186,12 @@ __global__ __launch_bounds__(NL, ICX_GW_MINW) void k_gw_lane(int n, const Desc* 
             // A second lookup of the same block where the block did not end and the window holds
             // every bit the lookup uses (no refill, so one refill per iteration stays the reader's
             // slot rule): more than 32 bits (write_step_more), or, without the error-byte bounds,
-            // fewer that still cover the entry's symbols (write_step_short) -- 1.94 lookups per
-            // iteration on photographic streams (1.75 with full windows alone) for one iteration's
-            // masks, refill, DC rotation and flush. Block starts stay at the top of an iteration;
-            // k and bcur are those of the first lookup (the same block).
+            // fewer that still cover the entry's symbols (write_step_short), and then a third under
+            // the same rule -- 2.81 lookups per iteration on photographic streams (1.94 with two,
+            // 1.75 with two out of full windows alone) for one iteration's masks, refill, DC
+            // rotation and flush. Block starts stay at the top of an iteration; k and bcur are
+            // those of the first lookup (the same block); the window may be drained to nb == 0,
+            // and the next iteration's refill then gives 32 bits.
             if (CHK) {
                 if (z != 0 && r.nb > 32) {
                     const uint32_t u1 = r.used;
@@ -1183,6 +1208,20 @@ __global__ __launch_bounds__(NL, ICX_GW_MINW) void k_gw_lane(int n, const Desc* 
                     err = lane_in(lm) && o2.err && err == INT32_MAX ? k : err;
                     sv[slot_elem(threadIdx.x, o2.n2)] = (int16_t)(o2.w2 ? o2.v2 : 0);
                     sv[slot_elem(threadIdx.x, o2.n1)] = (int16_t)o2.v1;
+                    // A third lookup under the same rule, for the lanes that took the second and are
+                    // still inside the block (87 % of iterations on photographic streams): a region
+                    // of its own inside the second's, so no WriteOut bool is merged across regions.
+                    // (A wave-uniform loop of two rounds over one region came to 3 VALU and 29 SALU
+                    // more per iteration in the ISA; a fourth lookup costs as many VALU as it saves.)
+                    if (z != 0) {
+                        uint32_t x3, e3;
+                        if (lane_in(short_entry(r, T, H, S, b, x3, e3))) {
+                            const WriteOut o3 = write_decode(r, e3, x3, S, b, z, false);
+                            err = lane_in(lm) && o3.err && err == INT32_MAX ? k : err;
+                            sv[slot_elem(threadIdx.x, o3.n2)] = (int16_t)(o3.w2 ? o3.v2 : 0);
+                            sv[slot_elem(threadIdx.x, o3.n1)] = (int16_t)o3.v1;
+                        }
+                    }
                 }
             }
             const uint64_t m = wave_ballot(z == 0) & lm;

@@ -576,7 +576,9 @@ ICX_HD WriteOut write_step_more(Reader& r, const Tab& T, const Huff* H, const Se
 // the branch split in two -- measured, 25 % more SALU per wave and a third of the kernel's gain.)
 // Reader invariants: consume(n) only with n <= nb; after a short lookup nb may be 0, and the next
 // refill() then gives nb = 32, exactly what step_entry's 32-bit peek needs; still one refill per
-// iteration and at most one word per refill, so the slot rule (tick, phase()) is unchanged.
+// iteration and at most one word per refill, so the slot rule (tick, phase()) is unchanged. All of
+// this holds for any number of short lookups between two refills: k_gw_lane takes two (the second
+// and the third lookup of an iteration; tests/emu/gw4_emu.cpp walks scans with the number a parameter).
 // The lane conditions are wave masks (ballots ANDed in SGPRs, read back by lane_in).
 constexpr uint32_t kStErr1 = 1u << 15;  // st_err1's bit
 template <class Tab>
