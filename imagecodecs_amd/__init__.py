@@ -26,8 +26,11 @@ callers (tests, bench): it binds the C ABI with ctypes and offers
   * ``TiffBatch``                 -- device-resident batched .tif decode
   * ``Context.pnm_decode`` / ``pnm_encode`` -- Image::readPbm / writePbm (codecs.cpp:1034-1167): P1-P6, Pf, PF
   * ``PnmBatch``                  -- device-resident batched Netpbm decode
+  * ``Context.dds_decode`` / ``dds_save_to_memory`` -- Image::readDds / writeDds: BC1-BC5 decode, masked and copied
+                                     forms; uncompressed and range-fit BC (DXT1 / DXT5 / BC4U / BC5U) write
+  * ``DdsBatch``                  -- device-resident batched .dds decode
   * ``Image``                     -- ImageCodecs::Image (codecs.h:16-103) for .jpg/.jpeg/.png/.hdr/.exr/.tga/.bmp/.gif/.tif
-                                     and .pbm/.pgm/.ppm/.pnm/.pfm
+                                     and .pbm/.pgm/.ppm/.pnm/.pfm, .dds
 
 There is deliberately no CPU fallback: if libicx.so is missing or no GPU is visible every
 entry point raises ``ICXError``.
@@ -55,7 +58,8 @@ __all__ = ["ICXError", "Context", "Batch", "HdrBatch", "Image", "lib", "build", 
            "TIFF_TOO_LARGE", "TIFF_INTERNAL_ERR", "PnmBatch", "pnm_probe", "pnm_encode_bound", "PNM_OK", "PNM_NOT_PNM",
            "PNM_BAD_HEADER", "PNM_UNSUPPORTED", "PNM_BAD_DATA", "PNM_TRUNCATED", "PNM_TOO_LARGE", "PNM_INVALID_ARGUMENT",
            "PNM_INTERNAL_ERR", "PNM_UBYTE", "PNM_USHORT", "PNM_FLOAT", "PNM_P4", "PNM_P5", "PNM_P6", "PNM_PF",
-           "PNM_ASCII_TILE"]
+           "PNM_ASCII_TILE", "DdsBatch", "dds_probe", "dds_encode_bound", "DDS_OK", "DDS_NOT_DDS", "DDS_BAD_HEADER",
+           "DDS_UNSUPPORTED", "DDS_TRUNCATED", "DDS_TOO_LARGE", "DDS_INVALID_ARGUMENT", "DDS_INTERNAL_ERR", "DDS_RAW", "DDS_BC"]
 
 OK, NO_JPEG, UNSUPPORTED, OUT_OF_MEM, INTERNAL_ERR, SYNTAX_ERROR = range(6)  # nj_result_t
 RESULT_NAMES = ["NJ_OK", "NJ_NO_JPEG", "NJ_UNSUPPORTED", "NJ_OUT_OF_MEM", "NJ_INTERNAL_ERR", "NJ_SYNTAX_ERROR"]
@@ -188,6 +192,16 @@ _SIGS = {
     "icx_bmp_save_to_memory": (_i32, [_vp, _vp, _i32, _i32, _i32, C.POINTER(_vp), C.POINTER(_sz)]),
     "icx_bmp_save_to_file": (_i32, [_vp, C.c_char_p, _vp, _i32, _i32, _i32]),
     "icx_bmp_encode_device_batch": (_i32, [_vp, _i32, _vp, _vp, _vp, _i32, _vp, _u64, _vp, _vp, _vp]),
+    "icx_dds_probe": (_i32, [_vp, _sz] + [C.POINTER(_i32)] * 4),
+    "icx_dds_decode": (_i32, [_vp, _vp, _sz, C.POINTER(_vp)] + [C.POINTER(_i32)] * 4),
+    "icx_dds_batch_create": (_vp, [_vp, _i32, _i32, _i32]),
+    "icx_dds_batch_destroy": (None, [_vp]),
+    "icx_dds_batch_decode": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _vp]),
+    "icx_dds_batch_stage_times": (_i32, [_vp, _vp, _vp, _i32]),
+    "icx_dds_encode_bound": (_sz, [_i32, _i32, _i32, _i32]),
+    "icx_dds_save_to_memory": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, C.POINTER(_vp), C.POINTER(_sz)]),
+    "icx_dds_save_to_file": (_i32, [_vp, C.c_char_p, _vp, _i32, _i32, _i32, _i32]),
+    "icx_dds_encode_device_batch": (_i32, [_vp, _i32, _vp, _vp, _vp, _i32, _i32, _vp, _u64, _vp, _vp, _vp]),
     "icx_pnm_probe": (_i32, [_vp, _sz] + [C.POINTER(_i32)] * 5),
     "icx_pnm_decode": (_i32, [_vp, _vp, _sz, C.POINTER(_vp)] + [C.POINTER(_i32)] * 5),
     "icx_pnm_batch_create": (_vp, [_vp, _i32, _i32, _i32]),
@@ -239,6 +253,10 @@ PNM_UBYTE, PNM_USHORT, PNM_FLOAT = range(3)  # icx_pnm_type = ImageCodecs::Type
 PNM_P4, PNM_P5, PNM_P6, PNM_PF = 4, 5, 6, 8  # icx_pnm_format
 PNM_ASCII_TILE = 4096  # icx_pnm_core.h kPnmTile: bytes of raster text per tile of the P1 / P2 / P3 read
 _PNM_DTYPES = (np.uint8, np.uint16, np.float32)
+# icx_dds_result (include/icx.h): Image::readDds / writeDds outcomes
+(DDS_OK, DDS_NOT_DDS, DDS_BAD_HEADER, DDS_UNSUPPORTED, DDS_TRUNCATED, DDS_TOO_LARGE, DDS_INVALID_ARGUMENT) = range(7)
+DDS_INTERNAL_ERR = -1
+DDS_RAW, DDS_BC = 0, 1  # icx_dds_format
 
 WRITE_FUNC = C.CFUNCTYPE(None, C.c_void_p, C.c_void_p, C.c_int)
 
@@ -667,6 +685,61 @@ class Context:
             raise ICXError("icx_pnm_encode_device_batch: " + _err(self._p))
         return rc
 
+    def dds_decode(self, data: bytes):
+        """Image::readDds (contract in include/icx.h) on the GPU: BC1-BC5, masked and copied forms ->
+        (code, w, h, channels, type, array (h, w, channels) of uint8 / uint16 / float32 or None); code
+        is an icx_dds_result."""
+        buf = C.create_string_buffer(bytes(data), max(1, len(data)))
+        out = C.c_void_p()
+        v = [C.c_int() for _ in range(4)]
+        code = lib().icx_dds_decode(self._p, buf, len(data), C.byref(out), *[C.byref(x) for x in v])
+        if code == DDS_INTERNAL_ERR:
+            raise ICXError("icx_dds_decode: " + _err(self._p))
+        w, h, d, t = (x.value for x in v)
+        arr = None
+        if out.value:
+            dt = np.dtype(_PNM_DTYPES[t])
+            arr = np.frombuffer(C.string_at(out.value, w * h * d * dt.itemsize), dt).reshape(h, w, d).copy()
+            lib().icx_free(out)
+        return code, w, h, d, t, arr
+
+    def dds_save_to_memory(self, px, fmt: int = DDS_RAW):
+        """Image::writeDds on the GPU: uint8 (h, w) or (h, w, d), d in 1..4, rows top-down; fmt is
+        DDS_RAW (uncompressed) or DDS_BC (DXT1 / DXT5 / BC4U / BC5U by d) -> (code, the file's bytes
+        or None)."""
+        a = np.ascontiguousarray(px)
+        if a.dtype != np.uint8:
+            return DDS_INVALID_ARGUMENT, None
+        if a.ndim == 2:
+            a = a[:, :, None]
+        if a.ndim != 3:
+            return DDS_INVALID_ARGUMENT, None
+        h, w, d = a.shape
+        out, size = C.c_void_p(), C.c_size_t()
+        code = lib().icx_dds_save_to_memory(self._p, a.ctypes.data if a.size else None, w, h, d, fmt, C.byref(out),
+                                            C.byref(size))
+        if code == DDS_INTERNAL_ERR:
+            raise ICXError("icx_dds_save_to_memory: " + _err(self._p))
+        if code != DDS_OK:
+            return code, None
+        data = C.string_at(out.value, size.value)
+        lib().icx_free(out)
+        return code, data
+
+    def dds_encode_device_batch(self, d_srcs, widths, heights, d: int, fmt: int, d_out: int, out_stride: int, d_sizes: int,
+                                d_status: int, stream=0) -> int:
+        """icx_dds_encode_device_batch: image i's pixels at device address d_srcs[i], its file to
+        d_out + i*out_stride, size (uint64) and status (int32) to the device arrays -> the call's code."""
+        n = len(d_srcs)
+        sp = (C.c_void_p * max(1, n))(*d_srcs)
+        ws = np.ascontiguousarray(widths, np.int32)
+        hs = np.ascontiguousarray(heights, np.int32)
+        rc = lib().icx_dds_encode_device_batch(self._p, n, sp, ws.ctypes.data, hs.ctypes.data, d, fmt, d_out, out_stride,
+                                               d_sizes, d_status, stream or None)
+        if rc == DDS_INTERNAL_ERR:
+            raise ICXError("icx_dds_encode_device_batch: " + _err(self._p))
+        return rc
+
     def png_encode(self, width: int, height: int, d: int, src: bytes):
         """PNG bytes of an RGB8 (d=3) / RGBA8 (d=4) image (png_encoder::saveToFile), or None."""
         chunks = []
@@ -1021,6 +1094,19 @@ def pnm_encode_bound(width: int, height: int, d: int, type_: int, fmt: int) -> i
     return int(lib().icx_pnm_encode_bound(width, height, d, type_, fmt))
 
 
+def dds_probe(data: bytes):
+    """Host header walk of the DDS read -> (code, width, height, channels, type)."""
+    v = [C.c_int() for _ in range(4)]
+    buf = C.create_string_buffer(bytes(data), max(1, len(data)))
+    code = lib().icx_dds_probe(buf, len(data), *[C.byref(x) for x in v])
+    return (code, *(x.value for x in v))
+
+
+def dds_encode_bound(width: int, height: int, d: int, fmt: int) -> int:
+    """icx_dds_encode_bound: the file's length, or 0 for arguments the write refuses."""
+    return int(lib().icx_dds_encode_bound(width, height, d, fmt))
+
+
 class _ReadBatch:
     """What the read batches share (icx_<fmt>_batch_*); a subclass names its entries and codes."""
 
@@ -1073,6 +1159,19 @@ class PnmBatch(_ReadBatch):
 
     def decode_device(self, n, d_data, d_offsets, d_sizes, d_out, out_stride, d_status, d_dims, stream=0) -> int:
         """-> PNM_OK, or PNM_INVALID_ARGUMENT for a d_out or out_stride that is not 16-byte aligned."""
+        return self._decode(n, d_data, d_offsets, d_sizes, d_out, out_stride, d_status, d_dims, stream)
+
+
+class DdsBatch(_ReadBatch):
+    """Device-resident batched DDS decode (icx_dds_batch_*): image i is
+    d_data[d_offsets[i] .. + d_sizes[i]); its elements at d_out + i*out_stride (d_out 16-byte aligned,
+    out_stride a multiple of 16), status in d_status[i], {width, height, channels, type} in
+    d_dims[4i..]."""
+
+    _prefix, _ok, _returned = "icx_dds_batch", DDS_OK, (DDS_INVALID_ARGUMENT,)
+
+    def decode_device(self, n, d_data, d_offsets, d_sizes, d_out, out_stride, d_status, d_dims, stream=0) -> int:
+        """-> DDS_OK, or DDS_INVALID_ARGUMENT for a d_out or out_stride that is not 16-byte aligned."""
         return self._decode(n, d_data, d_offsets, d_sizes, d_out, out_stride, d_status, d_dims, stream)
 
 
@@ -1154,7 +1253,8 @@ class Image:
     .tga (uncompressed) and .hdr (flat RGBE; d = 4 only). .bmp is read (readBmp: d = 1, 3 or 4, type
     UBYTE; raw, RLE4 / RLE8 and bitfields files) and written (writeBmp: 8-bit grey, 24-bit or 32-bit). .pbm/.pgm/.ppm/.pnm/.pfm are read by
     their magic (readPbm: d = 1 or 3; UBYTE, USHORT or FLOAT) and written as P4 / P5 / P6 / P5 or P6
-    by d / PF or Pf (writePbm). Other extensions raise ValueError (the reference's
+    by d / PF or Pf (writePbm). .dds is read (readDds: BC1-BC5 decoded, masked and copied forms; d = 1..4; UBYTE,
+    USHORT or FLOAT) and written uncompressed (writeDds; UBYTE only). Other extensions raise ValueError (the reference's
     std::invalid_argument for unknown types)."""
 
     _PNM_EXT = (".pbm", ".pgm", ".ppm", ".pnm", ".pfm")
@@ -1198,6 +1298,9 @@ class Image:
             return
         if ext in Image._PNM_EXT:
             self._read_pnm(filepath)
+            return
+        if ext == ".dds":
+            self._read_dds(filepath)
             return
         if ext not in (".jpg", ".jpeg"):
             raise ValueError("Cannot parse filetype")
@@ -1268,6 +1371,17 @@ class Image:
         self.pixels_ = px.reshape(-1).view(np.uint8).copy()
         self.type_ = t
 
+    def _read_dds(self, filepath: str):
+        """readDds (contract in include/icx.h): BC1-BC5 decoded, masked and copied forms; d = 1..4, type
+        UBYTE, USHORT or FLOAT, rows top-down. Every failure is Image::read's RuntimeError("Could not
+        read image data")."""
+        code, w, h, d, t, px = self.context().dds_decode(open(filepath, "rb").read())
+        if code != DDS_OK:
+            raise RuntimeError("Could not read image data")
+        self.w_, self.h_, self.d_ = w, h, d
+        self.pixels_ = px.reshape(-1).view(np.uint8).copy()
+        self.type_ = t
+
     def _read_exr(self, filepath: str):
         """readExr (codecs.cpp:464-493): LoadEXRFromMemory -> d = 4, type FLOAT, the floats' bytes in
         pixels_; a failure raises RuntimeError("Could not load .exr") (:489). (The reference reads
@@ -1308,6 +1422,16 @@ class Image:
             except (ICXError, ValueError, AttributeError):
                 return
             if code != BMP_OK:
+                return
+        elif ext == ".dds":  # writeDds: uncompressed, UBYTE only; nothing is thrown on failure
+            if self.type_ != Image.UBYTE:
+                return
+            try:
+                px = np.frombuffer(self.pixels_.tobytes(), np.uint8, self.w_ * self.h_ * self.d_)
+                code, out = self.context().dds_save_to_memory(px.reshape(self.h_, self.w_, self.d_), DDS_RAW)
+            except (ICXError, ValueError, AttributeError):
+                return
+            if code != DDS_OK:
                 return
         elif ext == ".hdr":  # writeHdr (codecs.cpp:779-818): flat RGBE; d != 4 throws (:781-784)
             if self.d_ != 4:

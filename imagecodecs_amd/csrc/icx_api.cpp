@@ -23,6 +23,7 @@
 #include "icx_tga_core.h"
 #include "icx_bmp_core.h"
 #include "icx_pnm_core.h"
+#include "icx_dds_core.h"
 #include "icx_hdrw_core.h"
 #include "icx_gif_core.h"
 
@@ -42,6 +43,7 @@ struct icx_ctx {
     BmpwWs* bmpw = nullptr;  // grow-only BMP write buffers (icx_bmp.hip)
     HdrwWs* hdrw = nullptr;  // grow-only Radiance write buffers (icx_hdrw.hip)
     PnmwWs* pnmw = nullptr;  // grow-only Netpbm write buffers (icx_pnm.hip)
+    DdswWs* ddsw = nullptr;  // grow-only DDS write buffers (icx_dds.hip)
 };
 
 struct EventHook;
@@ -255,6 +257,24 @@ struct PnmFmt : ReadFmtDefaults {
     }
 };
 
+struct DdsFmt : ReadFmtDefaults {
+    using Ws = DdsWs;
+    using Px = uint8_t;
+    using Batch = icx_dds_batch;
+    static constexpr int kOk = ICX_DDS_OK, kInternal = ICX_DDS_INTERNAL_ERR;
+    static constexpr const char *kCreate = "icx_dds_batch_create", *kDecode = "icx_dds_batch_decode", *kOne = "icx_dds_decode";
+    static constexpr Stage kOrder[] = {kStParse, kStEntropy, kStConvert};
+    static constexpr const char* kLabel[] = {"parse", "blocks", "raw"};
+    // (images are one grid dimension)
+    static bool over_limit(int n, int w, int h) { return n > 65535 || (int64_t)w * h > ((int64_t)1 << 30); }
+    static bool alloc(Ws& ws, Blocks& mem, icx_ctx*, int n, int w, int h) { return dds_ws_alloc(ws, mem, n, w, h); }
+    static constexpr auto launch = &launch_dds_decode;
+    static constexpr int kStridePx = 0;  // (a slot holds what the caller sized it for: TOO_LARGE per image)
+    static int out_refused(icx_ctx*, const void* d_out, uint64_t out_stride) {  // (sets no message)
+        return (reinterpret_cast<uintptr_t>(d_out) & 15) || (out_stride & 15) ? ICX_DDS_INVALID_ARGUMENT : 0;
+    }
+};
+
 struct GifFmt : ReadFmtDefaults {
     using Ws = GifWs;
     using Px = uint8_t;
@@ -312,6 +332,7 @@ struct icx_png_batch : ReadBatch<PngFmt> {};
 struct icx_tga_batch : ReadBatch<TgaFmt> {};
 struct icx_bmp_batch : ReadBatch<BmpFmt> {};
 struct icx_pnm_batch : ReadBatch<PnmFmt> {};
+struct icx_dds_batch : ReadBatch<DdsFmt> {};
 struct icx_gif_batch : ReadBatch<GifFmt> {};
 struct icx_tiff_batch : ReadBatch<TiffFmt> {};
 
@@ -553,6 +574,7 @@ void icx_destroy(icx_ctx* c) {
     if (c->bmpw) bmpw_ws_destroy(c->bmpw);
     if (c->hdrw) hdrw_ws_destroy(c->hdrw);
     if (c->pnmw) pnmw_ws_destroy(c->pnmw);
+    if (c->ddsw) ddsw_ws_destroy(c->ddsw);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
 }
@@ -1849,6 +1871,99 @@ int icx_pnm_save_to_file(icx_ctx* ctx, const char* path, const void* pixels, int
     const int rc = icx_pnm_save_to_memory(ctx, pixels, width, height, d, type, format, &mem, &size);
     if (rc != ICX_PNM_OK) return rc;
     return write_file(ctx, "icx_pnm_save_to_file", path, mem, size, ICX_PNM_OK, ICX_PNM_INTERNAL_ERR);
+}
+
+// --------------------------------------------------------- DDS (Image::readDds / writeDds)
+static int dds_probe_all(const uint8_t* data, size_t size, int* w, int* h, int* d, int* type) {
+    int v[4] = {0, 0, 0, 0};
+    const int rc = data ? dds_probe(data, (int64_t)size, &v[0], &v[1], &v[2], &v[3]) : ICX_DDS_NOT_DDS;
+    int* const dst[4] = {w, h, d, type};
+    for (int k = 0; k < 4; ++k)
+        if (dst[k]) *dst[k] = rc == ICX_DDS_OK ? v[k] : 0;
+    return rc;
+}
+
+int icx_dds_probe(const uint8_t* data, size_t size, int* w, int* h, int* channels, int* type) {
+    return dds_probe_all(data, size, w, h, channels, type);
+}
+
+icx_dds_batch* icx_dds_batch_create(icx_ctx* ctx, int max_images, int max_w, int max_h) {
+    return read_batch_new<DdsFmt>(ctx, max_images, max_w, max_h);
+}
+
+void icx_dds_batch_destroy(icx_dds_batch* b) { read_batch_destroy(b); }
+
+int icx_dds_batch_decode(icx_dds_batch* b, int n, const uint8_t* d_data, const uint64_t* d_off, const uint64_t* d_size,
+                         void* d_out, uint64_t out_stride, int32_t* d_status, int32_t* d_dims, void* stream) {
+    return read_batch_decode<DdsFmt>(b, n, d_data, d_off, d_size, d_out, out_stride, d_status, d_dims, stream);
+}
+
+int icx_dds_batch_stage_times(const icx_dds_batch* b, const char** names, float* ms, int cap) {
+    return b ? read_stage_times(*b->hook, DdsFmt::kOrder, DdsFmt::kLabel, names, ms, cap) : 0;
+}
+
+// (the two halves of read_one, as icx_pnm_decode: a five-int record and a slot rounded up to 16 bytes)
+int icx_dds_decode(icx_ctx* ctx, const uint8_t* data, size_t size, void** out, int* w, int* h, int* channels, int* type) {
+    if (out) *out = nullptr;
+    zero_out({w, h, channels, type});
+    if (!ctx || !out) return ICX_DDS_INTERNAL_ERR;
+    int ww = 0, hh = 0, dd = 0, tt = 0;
+    const int prc = dds_probe_all(data, size, &ww, &hh, &dd, &tt);
+    if (prc != ICX_DDS_OK) return prc;  // header errors and a short top level need no device work
+    ICX_HIP(ctx, hipSetDevice(ctx->device), ICX_DDS_INTERNAL_ERR);
+    std::unique_ptr<icx_dds_batch, void (*)(icx_dds_batch*)> b(read_batch_new<DdsFmt>(ctx, 1, ww, hh), icx_dds_batch_destroy);
+    if (!b) return ICX_DDS_INTERNAL_ERR;
+    const uint64_t nout = (uint64_t)ww * hh * dd * dds_elem_bytes(tt), stride = (nout + 15) & ~(uint64_t)15;
+    OneShot io;
+    if (!one_shot_run(ctx, io, data, size, size, stride, 5, launch_direct<DdsFmt>(b->ws, stride))) {
+        const hipError_t e = hipGetLastError();
+        ctx->err = std::string("icx_dds_decode: HIP failure: ") + hipGetErrorString(e);
+        return ICX_DDS_INTERNAL_ERR;
+    }
+    return io.rec[0] == ICX_DDS_OK ? one_shot_take<DdsFmt>(ctx, io, nout, out, {w, h, channels, type}) : io.rec[0];
+}
+
+size_t icx_dds_encode_bound(int width, int height, int d, int format) { return (size_t)dds_encode_bound(width, height, d, format); }
+
+int icx_dds_encode_device_batch(icx_ctx* ctx, int n, const uint8_t* const* d_src, const int32_t* widths,
+                                const int32_t* heights, int d, int format, uint8_t* d_out, uint64_t out_stride,
+                                uint64_t* d_sizes, int32_t* d_status, void* stream) {
+    if (!ctx) return ICX_DDS_INTERNAL_ERR;
+    // (1, 1: whether this d and format are known at all)
+    if (n < 0 || n > 65535 || !dds_write_args_ok(1, 1, d, format) ||
+        (n > 0 && (!d_src || !widths || !heights || !d_out || !d_sizes || !d_status)))
+        return ICX_DDS_INVALID_ARGUMENT;
+    if (n == 0) return ICX_DDS_OK;
+    return encode_batch_guarded(ctx, "icx_dds_encode_device_batch", ctx->ddsw, ddsw_ws_create, ICX_DDS_OK,
+                                ICX_DDS_INTERNAL_ERR, [&](DdswWs& ws, std::string& err) {
+                                    return dds_encode_batch(stream ? (hipStream_t)stream : ctx->stream, ws, n, d_src, widths,
+                                                            heights, d, format, d_out, out_stride, d_sizes, d_status, err);
+                                });
+}
+
+int icx_dds_save_to_memory(icx_ctx* ctx, const uint8_t* pixels, int width, int height, int d, int format, uint8_t** out,
+                           size_t* size) {
+    if (out) *out = nullptr;
+    if (size) *size = 0;
+    if (!ctx) return ICX_DDS_INTERNAL_ERR;
+    const uint64_t bound = dds_encode_bound(width, height, d, format);
+    if (!pixels || !out || !size || bound == 0) return ICX_DDS_INVALID_ARGUMENT;
+    const int32_t w = width, h = height;
+    return save_one<uint8_t>(ctx, "icx_dds_save_to_memory", pixels, (uint64_t)width * height * d, bound, out, size, ICX_DDS_OK,
+                             ICX_DDS_INTERNAL_ERR,
+                             [&](const uint8_t* const* src, uint8_t* d_file, uint64_t* d_size, int32_t* d_status, hipStream_t st) {
+                                 return icx_dds_encode_device_batch(ctx, 1, src, &w, &h, d, format, d_file, bound, d_size, d_status, st);
+                             });
+}
+
+int icx_dds_save_to_file(icx_ctx* ctx, const char* path, const uint8_t* pixels, int width, int height, int d, int format) {
+    if (!ctx) return ICX_DDS_INTERNAL_ERR;
+    if (!path) return ICX_DDS_INVALID_ARGUMENT;
+    uint8_t* mem = nullptr;
+    size_t size = 0;
+    const int rc = icx_dds_save_to_memory(ctx, pixels, width, height, d, format, &mem, &size);
+    if (rc != ICX_DDS_OK) return rc;
+    return write_file(ctx, "icx_dds_save_to_file", path, mem, size, ICX_DDS_OK, ICX_DDS_INTERNAL_ERR);
 }
 
 // --------------------------------------------------------- Radiance .hdr write (Image::writeHdr)

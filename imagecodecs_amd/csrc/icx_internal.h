@@ -454,6 +454,26 @@ int bmp_encode_batch(hipStream_t st, BmpwWs& ws, int n, const uint8_t* const* d_
                      const int32_t* heights, int d, uint8_t* d_out, uint64_t out_stride, uint64_t* d_sizes,
                      int32_t* d_status, std::string& err);
 
+// DDS read and write (icx_dds.hip; Image::readDds / writeDds). Status codes: icx_dds_core.h
+// kDds* = include/icx.h ICX_DDS_*.
+struct DdsDesc;
+struct DdsWs {
+    int max_images = 0, max_w = 0, max_h = 0;
+    DdsDesc* desc = nullptr;  // [max_images]
+};
+int dds_probe(const uint8_t* data, int64_t size, int* w, int* h, int* d, int* type);
+bool dds_ws_alloc(DdsWs& ws, Blocks& mem, int max_images, int max_w, int max_h);
+void launch_dds_decode(const DdsWs& ws, int n, const uint8_t* d_data, const uint64_t* d_off, const uint64_t* d_size,
+                       uint8_t* d_out, uint64_t out_stride, int32_t* d_status, int32_t* d_dims, hipStream_t st,
+                       StageHook* hook);
+struct DdswWs;  // grow-only buffers of the write
+DdswWs* ddsw_ws_create();
+void ddsw_ws_destroy(DdswWs* w);
+// 0, or -1 for a HIP failure (err says which). Synchronises with `st`.
+int dds_encode_batch(hipStream_t st, DdswWs& ws, int n, const uint8_t* const* d_src, const int32_t* widths,
+                     const int32_t* heights, int d, int format, uint8_t* d_out, uint64_t out_stride, uint64_t* d_sizes,
+                     int32_t* d_status, std::string& err);
+
 struct TgawWs;  // grow-only buffers of the write
 TgawWs* tgaw_ws_create();
 void tgaw_ws_destroy(TgawWs* w);

@@ -691,6 +691,121 @@ int icx_bmp_encode_device_batch(icx_ctx* ctx, int n, const uint8_t* const* d_src
                                 const int32_t* heights, int d, uint8_t* d_out, uint64_t out_stride,
                                 uint64_t* d_sizes, int32_t* d_status, void* hip_stream);
 
+/* ---- DDS read and write (Image::readDds / writeDds over nv_dds) -------------------------------------
+ * The reference never decompresses: for a DXT file it copies width*height*d bytes out of a buffer
+ * of compressed blocks. The contract is therefore written out here and pinned by an independent
+ * restatement (tests/ddsutil.py) and by PIL, not by the reference's output.
+ * Output: rows top-down (the file's order; the reference's two flips cancel), channels R,G,B(,A),
+ * `type` UBYTE, USHORT or FLOAT with the values of icx_pnm_type.
+ * Container: "DDS ", a 124-byte header (dwSize 124, ddspf.dwSize 32, width and height nonzero), then
+ * a 20-byte DX10 header when ddspf.dwFlags & 4 and the FourCC is "DX10". dwFlags,
+ * dwPitchOrLinearSize and dwMipMapCount are not trusted: rows and blocks are tightly packed, only
+ * the top level is read, and it must lie wholly inside the file; bytes after it are ignored.
+ * Block formats (UBYTE), by FourCC or DXGI format:
+ *     DXT1                 71, 72   BC1   3 channels (the count nv_dds reports; the transparent entry
+ *                                         of a 3-colour block gives 0,0,0)
+ *     DXT2, DXT3           74, 75   BC2   4
+ *     DXT4, DXT5, BC3U     77, 78   BC3   4
+ *     ATI1, BC4U           80       BC4   1
+ *     ATI2, BC5U           83       BC5   2 (the red block first)
+ * Block arithmetic, all integer with truncating divisions. Colour: c0, c1 little-endian 5-6-5,
+ * r8 = r<<3 | r>>2, g8 = g<<2 | g>>4, b8 = b<<3 | b>>2; with c0 > c1 (BC2, BC3: always) the palette
+ * is p0, p1, (2p0+p1)/3, (p0+2p1)/3, otherwise p0, p1, (p0+p1)/2, 0; pixel i = 4y + x takes bits
+ * 2i..2i+1 of the 32-bit index word. BC2 alpha: the first 8 bytes hold 4-bit values, little-endian,
+ * a = a4 * 17. BC3 alpha, BC4 and each half of BC5: bytes a0, a1, then 48 bits of 3-bit indices,
+ * little-endian; with a0 > a1 entries 2..7 are ((7-k)a0 + k a1)/7 for k = 1..6, otherwise entries
+ * 2..5 are ((5-k)a0 + k a1)/5 for k = 1..4, entry 6 is 0 and entry 7 is 255. Blocks cover
+ * ceil(w/4) x ceil(h/4); pixels outside the image are dropped.
+ * Uncompressed files (no FourCC flag): dwRGBBitCount 8, 16, 24 or 32; each of the masks R, G, B, A
+ * zero or contiguous, inside the bit count and disjoint from the others. With ddspf.dwFlags &
+ * 0x20000 (luminance): 1 channel from the R mask, 2 with a nonzero A mask. Otherwise by the masks:
+ * only A: 1 channel, the alpha; only R: 1; R and G: 2; R, G, B: 3, or 4 with A (an X8 form gives 3,
+ * the fourth byte dropped; nv_dds says 4). Field scaling is BMP's, above.
+ * Copied forms, samples as stored (little-endian, the host's order): FLOAT DXGI 2 / FourCC number
+ * 116 (4 channels), 6 (3), 16 / 115 (2), 41 / 114 (1); USHORT 11 / 36 (4), 35 (2), 56 (1).
+ * DX10 8-bit forms: 28, 29 R,G,B,A; 87, 91 B,G,R,A -> 4 channels; 88, 93 B,G,R,X -> 3; 61 -> 1; 49 -> 2. */
+enum icx_dds_result {
+    ICX_DDS_OK = 0,
+    ICX_DDS_NOT_DDS = 1,           /* fewer than 4 bytes, or no "DDS "                                */
+    ICX_DDS_BAD_HEADER = 2,        /* fewer than 128 bytes (148 with a DX10 header); dwSize not 124;
+                                      ddspf.dwSize not 32; width or height 0; an uncompressed file's
+                                      bit count not 8, 16, 24 or 32                                  */
+    ICX_DDS_UNSUPPORTED = 3,       /* cubemap (dwCaps2 & 0x200) or volume (0x200000); DX10 arraySize
+                                      not 1, the cube flag, a resourceDimension other than 3; BC4S,
+                                      BC5S, BC6H, BC7, RGBG, GRGB, half floats and any other FourCC or
+                                      DXGI value; masks not contiguous, past the bit count, overlapping
+                                      or in a combination not listed                                 */
+    ICX_DDS_TRUNCATED = 4,         /* the top level ends past the file's end                         */
+    ICX_DDS_TOO_LARGE = 5,         /* more than 2^30 pixels; larger than the batch's maxima or slot  */
+    ICX_DDS_INVALID_ARGUMENT = 6,  /* write: d not 1..4, width / height not 1..65535, a type other
+                                      than UBYTE, an unknown format, null; batch read: d_out or
+                                      out_stride not a multiple of 16                                */
+    ICX_DDS_INTERNAL_ERR = -1      /* HIP failure (see icx_last_error)                               */
+};
+enum icx_dds_format { ICX_DDS_RAW = 0, ICX_DDS_BC = 1 };
+/* Header only (host): size, channels and type, or the code, checked in the order NOT_DDS,
+ * BAD_HEADER, UNSUPPORTED, TOO_LARGE, TRUNCATED. Null data is NOT_DDS. */
+int icx_dds_probe(const uint8_t* data, size_t size, int* width, int* height, int* channels, int* type);
+/* One image, host in / host out: *out receives a malloc()'d buffer of width*height*channels
+ * elements of `type` (free with icx_free), null unless ICX_DDS_OK. A code the probe gives returns
+ * without touching the GPU. */
+int icx_dds_decode(icx_ctx* ctx, const uint8_t* data, size_t size, void** out, int* width, int* height, int* channels,
+                   int* type);
+/* Device-resident batch: image i = d_data[d_offsets[i] .. + d_sizes[i]) (any alignment), its
+ * elements at d_out + i*out_stride bytes (d_out 16-byte aligned and out_stride a multiple of 16,
+ * else the call returns ICX_DDS_INVALID_ARGUMENT), per-image status in d_status[i] and {width,
+ * height, channels, type} in d_dims[4i..] (zero for a failed image). An image wider or taller than
+ * the batch's maxima, or whose elements take more than out_stride bytes, is ICX_DDS_TOO_LARGE. A
+ * failed image leaves the others alone; nothing is written outside the slots, nor inside a slot
+ * past its image's last byte, and nothing at all for a failed image. Asynchronous on hip_stream
+ * (NULL = the context's stream), no host read-back. */
+typedef struct icx_dds_batch icx_dds_batch;
+icx_dds_batch* icx_dds_batch_create(icx_ctx* ctx, int max_images, int max_width, int max_height);
+void icx_dds_batch_destroy(icx_dds_batch* b);
+int icx_dds_batch_decode(icx_dds_batch* b, int n, const uint8_t* d_data, const uint64_t* d_offsets,
+                         const uint64_t* d_sizes, void* d_out, uint64_t out_stride, int32_t* d_status,
+                         int32_t* d_dims, void* hip_stream);
+/* Milliseconds per stage of the last icx_dds_batch_decode ("parse", "blocks", "raw"; synchronises).
+ * Returns the number of stages. */
+int icx_dds_batch_stage_times(const icx_dds_batch* b, const char** names, float* ms, int cap);
+
+/* DDS write: `pixels` is width*height*d bytes, rows top-down, d = 1..4, width and height 1..65535.
+ * Header, both formats: dwFlags 0x1007, dwCaps 0x1000, mip count, depth and the reserved words 0.
+ * ICX_DDS_RAW is what writeDds does, made well formed: dwFlags |= 0x8 with pitch width*d (the
+ * reference stores a dword-aligned pitch for rows it writes unpadded);
+ *     d = 3   24 bits, ddspf flags 0x40, masks FF0000, FF00, FF: rows B,G,R
+ *     d = 4   32 bits, flags 0x41, plus A FF000000: rows B,G,R,A
+ *     d = 1   8 bits, flags 0x20000 (luminance), R mask FF (the reference writes d = 1 under RGB
+ *             masks that cannot hold it)
+ *     d = 2   16 bits, flags 0x20001, R 00FF, A FF00
+ * and the read returns each of these with the same d. ICX_DDS_BC is an extension: dwFlags |=
+ * 0x80000 with linear size = blocks x block bytes, ddspf flags 4, d = 3 -> DXT1, 4 -> DXT5,
+ * 1 -> BC4U, 2 -> BC5U. The encoder is deterministic and integer. A block's 16 pixels are taken
+ * with coordinates clamped to the image. Colour: hi[c], lo[c] the per-channel maximum and minimum
+ * (no inset), q5(v) = (31v+127)/255, q6(v) = (63v+127)/255, c0 = 565(q(hi)), c1 = 565(q(lo)); each
+ * pixel takes the entry of the decoder's 4-entry palette of least squared R,G,B distance, ties to
+ * the lowest index; with c0 == c1 all indices are 0 (a DXT1 block is then in 3-colour mode with
+ * every pixel on entry 0, so it stays opaque). Alpha, BC4 and the halves of BC5: a0 = maximum,
+ * a1 = minimum; equal: all indices 0; otherwise the nearest of the 8-entry palette by absolute
+ * difference, ties to the lowest index. */
+/* The file's size, 128 + the top level; 0 for arguments the writes refuse. Host only. */
+size_t icx_dds_encode_bound(int width, int height, int d, int format);
+/* Host pixels in, *out receives the malloc()'d file (free with icx_free). Returns an icx_dds_result. */
+int icx_dds_save_to_memory(icx_ctx* ctx, const uint8_t* pixels, int width, int height, int d, int format, uint8_t** out,
+                           size_t* size);
+/* The same file written to `path` (ICX_DDS_INTERNAL_ERR when it cannot be written). */
+int icx_dds_save_to_file(icx_ctx* ctx, const char* path, const uint8_t* pixels, int width, int height, int d, int format);
+/* n writes with pixels and files resident on the device, as icx_bmp_encode_device_batch: image i's
+ * pixels at d_src[i] (any alignment), its file to d_out + i*out_stride (any alignment), the file's
+ * length to d_sizes[i] and an icx_dds_result to d_status[i]: INVALID_ARGUMENT for a bad size or null
+ * source, TOO_LARGE (nothing of the file written, d_sizes[i] says what it needs) when it is longer
+ * than out_stride. d not in 1..4, an unknown format, n < 0, n > 65535 or a null array with n > 0 ->
+ * the call returns ICX_DDS_INVALID_ARGUMENT. Runs on hip_stream (NULL = the context's stream) and
+ * synchronises with it. */
+int icx_dds_encode_device_batch(icx_ctx* ctx, int n, const uint8_t* const* d_src, const int32_t* widths,
+                                const int32_t* heights, int d, int format, uint8_t* d_out, uint64_t out_stride,
+                                uint64_t* d_sizes, int32_t* d_status, void* hip_stream);
+
 /* ---- Netpbm read (Image::readPbm, codecs.cpp:1034-1100; PNM::load, pnm.h) ---------------------------
  * PBM, PGM, PPM and PFM. The type comes from the magic, never from a file name:
  *     P1, P4   channels 1, UBYTE: bit 0 -> 255, bit 1 -> 0 (codecs.cpp:1078-1079); maxval reads 255

@@ -43,6 +43,14 @@
  *               big-endian files byte-swapped, bits otherwise untouched). Samples are not rescaled.
  *               A file the read refuses (codes in include/icx.h) leaves pixels_ null and read()
  *               throws "Could not read image data".
+ *               ".dds" decodes DDS on the GPU (readDds -> icx_dds_decode; contract in include/icx.h,
+ *               where the reference copies compressed blocks out as if they were pixels): BC1 .. BC5
+ *               (DXT1 .. DXT5, ATI1 / ATI2, BC4U / BC5U and their DXGI formats) to 8-bit pixels,
+ *               uncompressed files by their masks, float and 16-bit forms as stored. channels() is
+ *               1 .. 4 (3 for BC1 and for an X8 form); type() is UBYTE, USHORT or FLOAT; rows are
+ *               top-down. Cubemaps, volumes, arrays, BC6H, BC7, signed and half-float forms are
+ *               refused; a file the read refuses leaves pixels_ null and read() throws "Could not
+ *               read image data".
  *   write(path) -- ".jpg"/".jpeg" encode with tiny_jpeg quality 3 semantics (writeJpg,
  *                  codecs.cpp:851-854 -> icx_tje_encode_to_file, byte-identical stream).
  *               ".png" encodes with png_encoder::saveToFile semantics (writePng,
@@ -75,6 +83,11 @@
  *               std::runtime_error("Cannot write non-float data to .pfm") (:1149-1152); any other
  *               failure -- a d or type the format does not take included -- throws nothing
  *               (lastWriteOk() tells).
+ *               ".dds" writes an uncompressed file, rows top-down and unpadded (writeDds ->
+ *               icx_dds_save_to_file, ICX_DDS_RAW): d = 3 as 24-bit B,G,R, d = 4 as 32-bit B,G,R,A,
+ *               d = 1 as 8-bit luminance, d = 2 as luminance and alpha, each read back with the
+ *               same d; UBYTE only; nothing is thrown (lastWriteOk() tells). The public extension
+ *               writeDds(path, ICX_DDS_BC) writes DXT1 / DXT5 / BC4U / BC5U by d.
  *   pixels_ is new[]-owned and delete[]-d by ~Image (codecs.h:102); load() adopts a buffer;
  *   load(pixels, w, h, channels, Type) is an extension that also states the element type.
  * Every other extension is outside this path: it throws std::invalid_argument exactly like the
@@ -153,6 +166,13 @@
  * rows are written bottom-to-top (the reference writes them unflipped but flips on read, so its own
  * round trip turns the picture over); ".pnm" of a d = 1 image is P5 (the reference writes "P6" over
  * one sample per pixel); USHORT and d = 4 are accepted as described above.
+ *
+ * DDS (contract in include/icx.h): block-compressed files are decoded (the reference's readDds hands
+ * out w*h*d bytes of the compressed blocks); the pixels are R,G,B(,A) by the file's masks (the
+ * reference copies stored bytes) and an X8 file has 3 channels (nv_dds says 4); rows are top-down
+ * (the reference's two flips cancel). The write stores the pitch of the unpadded rows it writes (the
+ * reference stores a dword-aligned one) and d = 1 as luminance (the reference writes it under RGB
+ * masks that cannot hold it).
  *
  * Header-only; link with -L<repo>/imagecodecs_amd/lib -licx. One icx context per process
  * (device ICX_DEVICE, default 0), created on first use and serialised by a mutex -- the
@@ -454,6 +474,33 @@ class Image {
         type_ = t;
     }
 
+    // readDds (contract in include/icx.h): BC1 .. BC5 decoded, masked and copied uncompressed forms;
+    // d = 1 .. 4, Type::UBYTE, USHORT or FLOAT, rows top-down, decoded on the GPU (icx_dds_decode). A
+    // failure leaves pixels_ null, and read() throws "Could not read image data".
+    void readDds(const std::string& path) {
+        std::vector<uint8_t> buf;
+        detail::read_file(path, buf);
+        auto& P = detail::icx_process();
+        std::lock_guard<std::mutex> lock(P.mu);
+        void* out = nullptr;
+        int w = 0, h = 0, d = 0, type = 0;
+        const int rc = icx_dds_decode(P.get(), buf.data(), buf.size(), &out, &w, &h, &d, &type);
+        delete[] pixels_;
+        pixels_ = nullptr;
+        w_ = h_ = d_ = 0;
+        if (rc == ICX_DDS_INTERNAL_ERR) throw std::runtime_error(std::string("icx_dds_decode: ") + icx_last_error(P.get()));
+        if (rc != ICX_DDS_OK) return;
+        const Type t = type == ICX_PNM_FLOAT ? Type::FLOAT : type == ICX_PNM_USHORT ? Type::USHORT : Type::UBYTE;
+        const size_t n = (size_t)w * h * d * byteSize(t);
+        pixels_ = new unsigned char[n ? n : 1];
+        if (n) std::memcpy(pixels_, out, n);
+        icx_free(out);
+        w_ = w;
+        h_ = h;
+        d_ = d;
+        type_ = t;
+    }
+
     // writePbm (codecs.cpp:1102-1167): ".pbm" P4, ".pgm" P5, ".ppm" P6, ".pnm" P5 for d = 1 and P6
     // otherwise, ".pfm" PF / Pf. ".pfm" of non-float data throws (:1149-1152); as for the other
     // writers any other failure -- no usable GPU included -- only prints the message; the result
@@ -533,6 +580,30 @@ public:
         last_write_ok_ = rc == ICX_BMP_OK;
         if (!last_write_ok_) std::fprintf(stderr, "icx_bmp_save_to_file -> %d %s\n", rc, icx_last_error(c));
     }
+    // writeDds (private in the reference) called by name, whatever the path's extension: d = 1 .. 4,
+    // Type::UBYTE only. ICX_DDS_RAW is what write(".dds") writes; ICX_DDS_BC is an extension: DXT1,
+    // DXT5, BC4U or BC5U by d, from the range-fit encoder of include/icx.h. Nothing is thrown: a
+    // failure -- no usable GPU, another element type or a path that cannot be opened included -- only
+    // prints the message; lastWriteOk() tells.
+    void writeDds(const std::string& path, int format = ICX_DDS_RAW) {
+        auto& P = detail::icx_process();
+        std::lock_guard<std::mutex> lock(P.mu);
+        last_write_ok_ = false;
+        if (type_ != Type::UBYTE) {
+            std::fprintf(stderr, "writeDds: only UBYTE images are written\n");
+            return;
+        }
+        icx_ctx* c = nullptr;
+        try {
+            c = P.get();
+        } catch (const std::runtime_error& e) {
+            std::fprintf(stderr, "%s\n", e.what());
+            return;
+        }
+        const int rc = icx_dds_save_to_file(c, path.c_str(), pixels_, w_, h_, d_, format);
+        last_write_ok_ = rc == ICX_DDS_OK;
+        if (!last_write_ok_) std::fprintf(stderr, "icx_dds_save_to_file -> %d %s\n", rc, icx_last_error(c));
+    }
     // flip (codecs.h:80, codecs.cpp:162-196): reverse the row order in place.
     void flip() {
         if (empty()) return;
@@ -590,6 +661,7 @@ public:
         else if (ext == ".gif") readGif(filepath);
         else if (ext == ".tif" || ext == ".tiff") readTiff(filepath);
         else if (detail::is_pnm_ext(ext)) readPnm(filepath);
+        else if (ext == ".dds") readDds(filepath);
         else throw std::invalid_argument("Cannot parse filetype");
         if (pixels_ == nullptr) throw std::runtime_error("Could not read image data");
     }
@@ -602,6 +674,7 @@ public:
         else if (ext == ".tga") writeTga(filepath);
         else if (ext == ".hdr") writeHdr(filepath);
         else if (detail::is_pnm_ext(ext)) writePnm(filepath, ext);
+        else if (ext == ".dds") writeDds(filepath, ICX_DDS_RAW);
         else throw std::invalid_argument("Cannot parse filetype");
     }
 };
