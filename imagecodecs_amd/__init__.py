@@ -23,6 +23,8 @@ callers (tests, bench): it binds the C ABI with ctypes and offers
   * ``Context.gif_decode``        -- Image::readGif (codecs.cpp:507-542): first frame, wave LZW decode
   * ``GifBatch``                  -- device-resident batched .gif decode
   * ``Context.tiff_decode``       -- Image::readTiff (codecs.cpp:1439-1484): strips / tiles, one wave per chunk
+  * ``Context.tiff_save_to_memory`` / ``tiff_encode_device_batch`` -- Image::writeTiff (codecs.cpp:1485-1513):
+    uncompressed, PackBits, LZW or Deflate strips
   * ``TiffBatch``                 -- device-resident batched .tif decode
   * ``Context.pnm_decode`` / ``pnm_encode`` -- Image::readPbm / writePbm (codecs.cpp:1034-1167): P1-P6, Pf, PF
   * ``PnmBatch``                  -- device-resident batched Netpbm decode
@@ -40,6 +42,7 @@ from __future__ import annotations
 import ctypes as C
 import os
 import subprocess
+import sys
 
 import numpy as np
 
@@ -55,7 +58,8 @@ __all__ = ["ICXError", "Context", "Batch", "HdrBatch", "Image", "lib", "build", 
            "BMP_UNSUPPORTED", "BMP_TRUNCATED", "BMP_TOO_LARGE", "BMP_INVALID_ARGUMENT", "BMP_INTERNAL_ERR", "GifBatch", "gif_probe", "GIF_OK", "GIF_NOT_GIF", "GIF_BAD_HEADER", "GIF_MALFORMED",
            "GIF_BAD_DATA", "GIF_TRUNCATED", "GIF_TOO_LARGE", "GIF_INTERNAL_ERR", "TiffBatch", "tiff_probe", "TIFF_OK",
            "TIFF_NOT_TIFF", "TIFF_BAD_HEADER", "TIFF_UNSUPPORTED", "TIFF_MALFORMED", "TIFF_BAD_DATA", "TIFF_TRUNCATED",
-           "TIFF_TOO_LARGE", "TIFF_INTERNAL_ERR", "PnmBatch", "pnm_probe", "pnm_encode_bound", "PNM_OK", "PNM_NOT_PNM",
+           "TIFF_TOO_LARGE", "TIFF_INVALID_ARGUMENT", "TIFF_INTERNAL_ERR", "TIFF_COMPRESSION_NONE", "TIFF_COMPRESSION_LZW",
+           "TIFF_COMPRESSION_DEFLATE", "TIFF_COMPRESSION_PACKBITS", "tiff_encode_bound", "PnmBatch", "pnm_probe", "pnm_encode_bound", "PNM_OK", "PNM_NOT_PNM",
            "PNM_BAD_HEADER", "PNM_UNSUPPORTED", "PNM_BAD_DATA", "PNM_TRUNCATED", "PNM_TOO_LARGE", "PNM_INVALID_ARGUMENT",
            "PNM_INTERNAL_ERR", "PNM_UBYTE", "PNM_USHORT", "PNM_FLOAT", "PNM_P4", "PNM_P5", "PNM_P6", "PNM_PF",
            "PNM_ASCII_TILE", "DdsBatch", "dds_probe", "dds_encode_bound", "DDS_OK", "DDS_NOT_DDS", "DDS_BAD_HEADER",
@@ -178,6 +182,10 @@ _SIGS = {
     "icx_tiff_batch_destroy": (None, [_vp]),
     "icx_tiff_batch_decode": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _vp]),
     "icx_tiff_batch_stage_times": (_i32, [_vp, _vp, _vp, _i32]),
+    "icx_tiff_encode_bound": (_sz, [_i32, _i32, _i32, _i32, _i32, _i32]),
+    "icx_tiff_save_to_memory": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, C.POINTER(_vp), C.POINTER(_sz)]),
+    "icx_tiff_save_to_file": (_i32, [_vp, C.c_char_p, _vp, _i32, _i32, _i32, _i32, _i32, _i32]),
+    "icx_tiff_encode_device_batch": (_i32, [_vp, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _u64, _vp, _vp, _vp]),
     "icx_tga_encode_bound": (_sz, [_i32, _i32, _i32]),
     "icx_tga_save_to_memory": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, C.POINTER(_vp), C.POINTER(_sz)]),
     "icx_tga_save_to_file": (_i32, [_vp, C.c_char_p, _vp, _i32, _i32, _i32, _i32]),
@@ -241,10 +249,12 @@ BMP_INTERNAL_ERR = -1
 # icx_gif_result (include/icx.h): Image::readGif outcomes
 GIF_OK, GIF_NOT_GIF, GIF_BAD_HEADER, GIF_MALFORMED, GIF_BAD_DATA, GIF_TRUNCATED, GIF_TOO_LARGE = range(7)
 GIF_INTERNAL_ERR = -1
-# icx_tiff_result (include/icx.h): Image::readTiff outcomes
+# icx_tiff_result (include/icx.h): Image::readTiff / writeTiff outcomes
 (TIFF_OK, TIFF_NOT_TIFF, TIFF_BAD_HEADER, TIFF_UNSUPPORTED, TIFF_MALFORMED, TIFF_BAD_DATA, TIFF_TRUNCATED,
- TIFF_TOO_LARGE) = range(8)
+ TIFF_TOO_LARGE, TIFF_INVALID_ARGUMENT) = range(9)
 TIFF_INTERNAL_ERR = -1
+# icx_tiff_compression: what writeTiff can write
+TIFF_COMPRESSION_NONE, TIFF_COMPRESSION_LZW, TIFF_COMPRESSION_DEFLATE, TIFF_COMPRESSION_PACKBITS = 1, 5, 8, 32773
 # icx_pnm_result (include/icx.h): Image::readPbm / writePbm outcomes
 (PNM_OK, PNM_NOT_PNM, PNM_BAD_HEADER, PNM_UNSUPPORTED, PNM_BAD_DATA, PNM_TRUNCATED, PNM_TOO_LARGE,
  PNM_INVALID_ARGUMENT) = range(8)
@@ -590,6 +600,43 @@ class Context:
                                                out_stride, d_sizes, d_status, stream or None)
         if rc == TGA_INTERNAL_ERR:
             raise ICXError("icx_tga_encode_device_batch: " + _err(self._p))
+        return rc
+
+    def tiff_save_to_memory(self, px, compression: int = TIFF_COMPRESSION_DEFLATE, predictor: int = 1, rows_per_strip: int = 0):
+        """Image::writeTiff on the GPU (contract in include/icx.h, "TIFF write"): uint8 (h, w) or
+        (h, w, d), d in 1, 3, 4, rows top-down -> (code, the file's bytes or None)."""
+        a = np.ascontiguousarray(px)
+        if a.dtype != np.uint8:
+            return TIFF_INVALID_ARGUMENT, None
+        if a.ndim == 2:
+            a = a[:, :, None]
+        if a.ndim != 3:
+            return TIFF_INVALID_ARGUMENT, None
+        h, w, d = a.shape
+        out, size = C.c_void_p(), C.c_size_t()
+        code = lib().icx_tiff_save_to_memory(self._p, a.ctypes.data if a.size else None, w, h, d, compression, predictor,
+                                             rows_per_strip, C.byref(out), C.byref(size))
+        if code == TIFF_INTERNAL_ERR:
+            raise ICXError("icx_tiff_save_to_memory: " + _err(self._p))
+        if code != TIFF_OK:
+            return code, None
+        data = C.string_at(out.value, size.value)
+        lib().icx_free(out)
+        return code, data
+
+    def tiff_encode_device_batch(self, d_srcs, widths, heights, d: int, compression: int, predictor: int,
+                                 rows_per_strip: int, d_out: int, out_stride: int, d_sizes: int, d_status: int,
+                                 stream=0) -> int:
+        """icx_tiff_encode_device_batch: image i's pixels at device address d_srcs[i], its file to
+        d_out + i*out_stride, size (uint64) and status (int32) to the device arrays -> the call's code."""
+        n = len(d_srcs)
+        sp = (C.c_void_p * max(1, n))(*d_srcs)
+        ws = np.ascontiguousarray(widths, np.int32)
+        hs = np.ascontiguousarray(heights, np.int32)
+        rc = lib().icx_tiff_encode_device_batch(self._p, n, sp, ws.ctypes.data, hs.ctypes.data, d, compression, predictor,
+                                                rows_per_strip, d_out, out_stride, d_sizes, d_status, stream or None)
+        if rc == TIFF_INTERNAL_ERR:
+            raise ICXError("icx_tiff_encode_device_batch: " + _err(self._p))
         return rc
 
     def bmp_decode(self, data: bytes):
@@ -1076,6 +1123,13 @@ def tiff_probe(data: bytes):
     return code, w.value, h.value, d.value
 
 
+def tiff_encode_bound(width: int, height: int, d: int, compression: int = TIFF_COMPRESSION_DEFLATE, predictor: int = 1,
+                      rows_per_strip: int = 0) -> int:
+    """icx_tiff_encode_bound: an upper bound of the written file's size, or 0 for arguments the
+    write refuses."""
+    return int(lib().icx_tiff_encode_bound(width, height, d, compression, predictor, rows_per_strip))
+
+
 def tga_encode_bound(width: int, height: int, d: int) -> int:
     """icx_tga_encode_bound: 18 + w*h*(d+1), or 0 for arguments the write refuses."""
     return int(lib().icx_tga_encode_bound(width, height, d))
@@ -1459,6 +1513,27 @@ class Image:
         with open(filepath, "wb") as f:
             if out is not None:
                 f.write(out)
+
+    def writeTiff(self, filepath: str, compression: int = TIFF_COMPRESSION_DEFLATE, predictor: int = 1,
+                  rows_per_strip: int = 0):
+        """writeTiff (private in the reference, codecs.cpp:1485-1513) called by name, whatever the
+        path's extension; write(".tif") does not dispatch to it yet. UBYTE only. Nothing is thrown:
+        a failure prints a line and writes nothing."""
+        if self.type_ != Image.UBYTE:
+            print("writeTiff: only UBYTE images are written", file=sys.stderr)
+            return
+        try:
+            px = np.frombuffer(self.pixels_.tobytes(), np.uint8, self.w_ * self.h_ * self.d_)
+            code, out = self.context().tiff_save_to_memory(px.reshape(self.h_, self.w_, self.d_), compression, predictor,
+                                                           rows_per_strip)
+        except (ICXError, ValueError, AttributeError) as e:
+            print("writeTiff:", e, file=sys.stderr)
+            return
+        if code != TIFF_OK:
+            print("icx_tiff_save_to_memory ->", code, file=sys.stderr)
+            return
+        with open(filepath, "wb") as f:
+            f.write(out)
 
     def load(self, pixels, w: int, h: int, channels: int, type_: int = None):
         """load(pixels, w, h, channels): UBYTE, as the reference's. With a fifth argument the pixels

@@ -26,6 +26,7 @@
 #include "icx_dds_core.h"
 #include "icx_hdrw_core.h"
 #include "icx_gif_core.h"
+#include "icx_tiffw_core.h"
 
 using namespace icx;
 
@@ -44,6 +45,7 @@ struct icx_ctx {
     HdrwWs* hdrw = nullptr;  // grow-only Radiance write buffers (icx_hdrw.hip)
     PnmwWs* pnmw = nullptr;  // grow-only Netpbm write buffers (icx_pnm.hip)
     DdswWs* ddsw = nullptr;  // grow-only DDS write buffers (icx_dds.hip)
+    TiffwWs* tiffw = nullptr;  // grow-only TIFF write buffers (icx_tiffw.hip)
 };
 
 struct EventHook;
@@ -575,6 +577,7 @@ void icx_destroy(icx_ctx* c) {
     if (c->hdrw) hdrw_ws_destroy(c->hdrw);
     if (c->pnmw) pnmw_ws_destroy(c->pnmw);
     if (c->ddsw) ddsw_ws_destroy(c->ddsw);
+    if (c->tiffw) tiffw_ws_destroy(c->tiffw);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
 }
@@ -2081,6 +2084,55 @@ int icx_tiff_decode(icx_ctx* ctx, const uint8_t* data, size_t size, uint8_t** ou
     if (!b) return ICX_TIFF_INTERNAL_ERR;
     const uint64_t nout = (uint64_t)ww * hh * dd;
     return read_one<TiffFmt>(ctx, data, size, nout, out, {w, h, d}, launch_direct<TiffFmt>(b->ws, nout));
+}
+
+// ------------------------------------------------------------ TIFF write (Image::writeTiff)
+size_t icx_tiff_encode_bound(int width, int height, int d, int compression, int predictor, int rows_per_strip) {
+    return (size_t)tiffw_bound(width, height, d, compression, predictor, rows_per_strip);
+}
+
+int icx_tiff_encode_device_batch(icx_ctx* ctx, int n, const uint8_t* const* d_src, const int32_t* widths,
+                                 const int32_t* heights, int d, int compression, int predictor, int rows_per_strip,
+                                 uint8_t* d_out, uint64_t out_stride, uint64_t* d_sizes, int32_t* d_status, void* stream) {
+    if (!ctx) return ICX_TIFF_INTERNAL_ERR;
+    TiffwGeom g;  // (a 1 x 1 image tells whether d, the compression, the predictor and the rows go together)
+    if (n < 0 || n > 65535 || !tiffw_geom(1, 1, d, compression, predictor, rows_per_strip, &g) ||
+        (n > 0 && (!d_src || !widths || !heights || !d_out || !d_sizes || !d_status)))
+        return ICX_TIFF_INVALID_ARGUMENT;
+    if (n == 0) return ICX_TIFF_OK;
+    return encode_batch_guarded(ctx, "icx_tiff_encode_device_batch", ctx->tiffw, tiffw_ws_create, ICX_TIFF_OK,
+                                ICX_TIFF_INTERNAL_ERR, [&](TiffwWs& ws, std::string& err) {
+                                    return tiffw_encode_batch(stream ? (hipStream_t)stream : ctx->stream, ws, n, d_src, widths,
+                                                              heights, d, compression, predictor, rows_per_strip, d_out,
+                                                              out_stride, d_sizes, d_status, err);
+                                });
+}
+
+int icx_tiff_save_to_memory(icx_ctx* ctx, const uint8_t* pixels, int width, int height, int d, int compression,
+                            int predictor, int rows_per_strip, uint8_t** out, size_t* size) {
+    if (out) *out = nullptr;
+    if (size) *size = 0;
+    if (!ctx) return ICX_TIFF_INTERNAL_ERR;
+    const uint64_t bound = tiffw_bound(width, height, d, compression, predictor, rows_per_strip);
+    if (!pixels || !out || !size || bound == 0) return ICX_TIFF_INVALID_ARGUMENT;
+    const int32_t w = width, h = height;
+    return save_one<uint8_t>(ctx, "icx_tiff_save_to_memory", pixels, (uint64_t)width * height * d, bound, out, size,
+                             ICX_TIFF_OK, ICX_TIFF_INTERNAL_ERR,
+                             [&](const uint8_t* const* src, uint8_t* d_file, uint64_t* d_size, int32_t* d_status, hipStream_t st) {
+                                 return icx_tiff_encode_device_batch(ctx, 1, src, &w, &h, d, compression, predictor,
+                                                                     rows_per_strip, d_file, bound, d_size, d_status, st);
+                             });
+}
+
+int icx_tiff_save_to_file(icx_ctx* ctx, const char* path, const uint8_t* pixels, int width, int height, int d,
+                          int compression, int predictor, int rows_per_strip) {
+    if (!ctx) return ICX_TIFF_INTERNAL_ERR;
+    if (!path) return ICX_TIFF_INVALID_ARGUMENT;
+    uint8_t* mem = nullptr;
+    size_t size = 0;
+    const int rc = icx_tiff_save_to_memory(ctx, pixels, width, height, d, compression, predictor, rows_per_strip, &mem, &size);
+    if (rc != ICX_TIFF_OK) return rc;
+    return write_file(ctx, "icx_tiff_save_to_file", path, mem, size, ICX_TIFF_OK, ICX_TIFF_INTERNAL_ERR);
 }
 
 }  // extern "C"

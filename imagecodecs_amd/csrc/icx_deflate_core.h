@@ -1,14 +1,16 @@
 // icx_deflate_core.h -- the serial part of the device deflate writer, host and device: the RFC 1951
 // tables, a block's code tables (BlockCodes), length-limited Huffman code lengths, canonical codes,
-// the header's bit writer, and a token slot's bits. One text for the PNG encoder (icx_png.hip) and
-// the OpenEXR ZIP write (icx_exrw.hip); the wave-level part is icx_deflate_wave.h. Plain C++: the
+// the header's bit writer, and a token slot's bits. One text for the PNG encoder (icx_png.hip),
+// the OpenEXR ZIP write (icx_exrw.hip) and the TIFF Deflate strips (icx_tiffw.hip); the wave-level
+// part is icx_deflate_wave.h. Plain C++: the
 // CPU test builds it with g++ (tests/test_deflate_core.py), the two writers with hipcc. Their bytes
 // are pinned by tests/test_gpu_deflate_pin.py.
 //
-// Not here: the sequence that calls these for one block (thread 0 of k_png_huff / k_exrw_huff: both
-// codes, the run-length coded lengths, the 7-bit code, the header bits). As a function of its own
-// it is simplified before it is inlined, with pointers of unknown address space, and both kernels
-// compiled to other code (one or two more VGPRs, 14 % more instructions), so it stays in them.
+// Not here: the sequence that calls these for one block (thread 0 of k_png_huff / k_exrw_huff /
+// k_tiffw_huff: both codes, the run-length coded lengths, the 7-bit code, the header bits). As a
+// function of its own it is simplified before it is inlined, with pointers of unknown address
+// space, and the PNG and EXR kernels compiled to other code (one or two more VGPRs, 14 % more
+// instructions), so it stays in them, and the TIFF kernel carries the same text.
 //
 // Token slots (uint16): a literal is its byte value (< 256); a match is a length slot
 // 0x4000 | (len - 3) followed by a distance slot 0x8000 | (dist - 1).

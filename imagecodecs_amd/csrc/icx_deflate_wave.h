@@ -1,9 +1,9 @@
 // icx_deflate_wave.h -- the wave-level part of the device deflate writer (gfx950, wave64), the write
 // side's counterpart of icx_inflate_wave.h: staging a view of the stream in LDS, the 64-position
 // window parse (ballot, one-step lazy evaluation, tokens + symbol counts), the workgroup's rank
-// count for the Huffman sort, and the bit packing of a segment's tokens. Shared by icx_png.hip and
-// icx_exrw.hip, which keep their own views, candidate scoring, seams and layout; the serial part is
-// icx_deflate_core.h.
+// count for the Huffman sort, and the bit packing of a segment's tokens. Shared by icx_png.hip,
+// icx_exrw.hip and icx_tiffw.hip, which keep their own views, candidate scoring, seams and layout;
+// the serial part is icx_deflate_core.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>

@@ -526,6 +526,15 @@ void launch_tiff_decode(const TiffWs& ws, int n, const uint8_t* d_data, const ui
                         uint8_t* d_out, uint64_t out_stride, int32_t* d_status, int32_t* d_dims, hipStream_t st,
                         StageHook* hook);
 
+// ---- TIFF write (icx_tiffw.hip; contract in include/icx.h, serial part in icx_tiffw_core.h) ----
+struct TiffwWs;
+TiffwWs* tiffw_ws_create();
+void tiffw_ws_destroy(TiffwWs* w);
+// 0, or -1 with err set
+int tiffw_encode_batch(hipStream_t st, TiffwWs& ws, int n, const uint8_t* const* d_src, const int32_t* widths,
+                       const int32_t* heights, int d, int comp, int pred, int rows_per_strip, uint8_t* d_out,
+                       uint64_t out_stride, uint64_t* d_sizes, int32_t* d_status, std::string& err);
+
 // ---- OpenEXR read (icx_exr.hip) ----
 // tinyexr's LoadEXRFromMemory; returns its code (-100: HIP failure, err says which).
 struct ExrWs;

@@ -1042,6 +1042,7 @@ enum icx_tiff_result {
     ICX_TIFF_TOO_LARGE = 7,   /* larger than the batch workspace; more than 4096 chunks; more than
                                  2^30 pixels (also when padded to whole chunks); a chunk of 2^31
                                  bytes or more                                                        */
+    ICX_TIFF_INVALID_ARGUMENT = 8, /* the write only: see "TIFF write" below                          */
     ICX_TIFF_INTERNAL_ERR = -1 /* HIP failure (see icx_last_error)                                    */
 };
 /* The IFD walk (host only, no GPU touched): width, height and channels, or the code the walk gives
@@ -1072,6 +1073,73 @@ int icx_tiff_batch_decode(icx_tiff_batch* b, int n, const uint8_t* d_data, const
 /* Milliseconds per stage of the last icx_tiff_batch_decode ("parse", "unpack", "render";
  * synchronises). Returns the number of stages. */
 int icx_tiff_batch_stage_times(const icx_tiff_batch* b, const char** names, float* ms, int cap);
+
+/* ---- TIFF write (Image::writeTiff, codecs.cpp:1485-1513: libtiff, one ADOBE_DEFLATE strip) ---------
+ * pixels: width*height*d bytes, rows top-down, d = 1 (grey), 3 (R,G,B) or 4 (R,G,B,A): the shapes the
+ * read returns. A file written here reads back, through icx_tiff_decode, to the same d and bytes.
+ * compression: ICX_TIFF_COMPRESSION_NONE (1), _LZW (5), _DEFLATE (8, the reference's) or _PACKBITS
+ * (32773). predictor: 1, or 2 with LZW or Deflate only (the read, like libtiff, ignores the tag
+ * elsewhere). rows_per_strip: 0 is the image height (one strip, the reference's layout); a positive
+ * value is clamped to the height. ICX_TIFF_INVALID_ARGUMENT (and a bound of 0): any other
+ * compression, predictor or combination; rows_per_strip < 0; more than 4096 strips; d outside
+ * {1, 3, 4}; width or height < 1; more than 2^30 pixels; a strip of 2^31 bytes or more; a null
+ * pointer; a worst-case file of 2^32 bytes or more (the offsets are 32-bit).
+ * File layout, little-endian ("II*\0"): the strips' data from offset 8, in order, each strip at an
+ * even offset (one zero byte after a strip of odd length); then the out-of-line arrays in tag
+ * order, each at an even offset: BitsPerSample when d >= 3, StripOffsets and StripByteCounts when
+ * there is more than one strip; then the IFD at the next even offset: the entry count, the entries
+ * sorted by tag, next-IFD 0. Nothing follows the IFD. Entries: 256 ImageWidth LONG; 257
+ * ImageLength LONG; 258 BitsPerSample SHORT x d, all 8; 259 Compression SHORT; 262 Photometric
+ * SHORT, 1 for d = 1 and 2 otherwise (the reference sets RGB for every d); 273 StripOffsets LONG x
+ * n; 277 SamplesPerPixel SHORT; 278 RowsPerStrip LONG, the clamped value; 279 StripByteCounts LONG
+ * x n; 284 PlanarConfiguration SHORT 1; 317 Predictor SHORT 2, only when predictor 2 was asked
+ * for; 338 ExtraSamples SHORT 2 (unassociated alpha), only when d = 4.
+ * Strip payloads: the raw bytes of strip k are its rows x width*d; with predictor 2 every sample
+ * after the first pixel of a row is stored minus the sample d bytes before it, mod 256.
+ *   None      the raw bytes.
+ *   PackBits  rows are coded row by row, no packet crosses a row. Each maximal run of equal bytes
+ *             is cut into pieces of 128 from its start; a piece of 3 or more bytes is a repeat
+ *             packet (257 - n, the byte); everything else joins the neighbouring literal stretch;
+ *             literal stretches are cut into packets of 128 from their start (n - 1, the bytes).
+ *   LZW       libtiff's stream: MSB first, early change (widths as under the read), a leading
+ *             Clear, greedy longest match, a Clear after the 3836th code since the last Clear, EOI,
+ *             then zero bits to the byte. One stream per strip.
+ *   Deflate   an RFC 1950 stream of our own (78 01, dynamic blocks, big-endian Adler-32) that
+ *             inflates to exactly the strip's (differenced) bytes: as with PNG and EXR only the
+ *             tokenisation is ours. Matches never cross a multiple of 4096 bytes of the strip; a
+ *             block covers at most 65536 bytes.
+ * icx_tiff_encode_bound: an upper bound of the file's size (0: refused arguments): the layout
+ * above with each strip at its payload's bound -- none: exact; PackBits: n + ceil(n / 128) per row
+ * of n bytes; LZW: 12 bits per byte, per Clear and for the EOI; Deflate: 9 bits per byte (a
+ * Huffman-optimal code costs no more than a flat 9-bit code over 286 symbols and a flat 5-bit
+ * distance code, under which no token the parse keeps costs more than 9 bits a byte) times
+ * 1 + 1/1024 for the length limiter (its documented worst ratio is 1.000036), 384 bytes and an
+ * end-of-block code per block, and 6 bytes of zlib framing. The proof is in icx_tiffw_core.h. */
+enum icx_tiff_compression {
+    ICX_TIFF_COMPRESSION_NONE = 1,
+    ICX_TIFF_COMPRESSION_LZW = 5,
+    ICX_TIFF_COMPRESSION_DEFLATE = 8,
+    ICX_TIFF_COMPRESSION_PACKBITS = 32773
+};
+size_t icx_tiff_encode_bound(int width, int height, int d, int compression, int predictor, int rows_per_strip);
+/* One image, host in / host out: *out receives the file (malloc()'d, free with icx_free). */
+int icx_tiff_save_to_memory(icx_ctx* ctx, const uint8_t* pixels, int width, int height, int d, int compression,
+                            int predictor, int rows_per_strip, uint8_t** out, size_t* size);
+/* The same bytes written to path; ICX_TIFF_INTERNAL_ERR when the file cannot be written. */
+int icx_tiff_save_to_file(icx_ctx* ctx, const char* path, const uint8_t* pixels, int width, int height, int d,
+                          int compression, int predictor, int rows_per_strip);
+/* Device-resident batch: image i's pixels at d_src[i] (device, any alignment), its file at
+ * d_out + i*out_stride (any alignment), its size in d_sizes[i] and its code in d_status[i]: OK;
+ * INVALID_ARGUMENT (a null d_src[i] or a refused size; size 0); ICX_TIFF_TOO_LARGE when the file is
+ * longer than out_stride (nothing of it is written; d_sizes[i] says what it needs). The call
+ * returns ICX_TIFF_INVALID_ARGUMENT for n < 0, n > 65535, a refused d / compression / predictor /
+ * rows_per_strip or a null array with n > 0, otherwise ICX_TIFF_OK or ICX_TIFF_INTERNAL_ERR. All
+ * strips of all images go through each kernel in one launch; the call synchronises hip_stream
+ * (NULL = the context's stream) and reads nothing back. */
+int icx_tiff_encode_device_batch(icx_ctx* ctx, int n, const uint8_t* const* d_src, const int32_t* widths,
+                                 const int32_t* heights, int d, int compression, int predictor, int rows_per_strip,
+                                 uint8_t* d_out, uint64_t out_stride, uint64_t* d_sizes, int32_t* d_status,
+                                 void* hip_stream);
 
 #ifdef __cplusplus
 }

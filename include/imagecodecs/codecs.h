@@ -35,7 +35,10 @@
  *               uncompressed, LZW, zlib or PackBits, predictor 2, grey (either polarity), palette,
  *               RGB and RGBA. channels() is 1, 3 or 4. A file the read refuses (codes in
  *               include/icx.h) leaves pixels_ null and read() throws "Could not read image data".
- *               write(".tif") stays outside this path.
+ *               writeTiff(path, compression, predictor, rows_per_strip) writes strips on the GPU
+ *               (writeTiff, codecs.cpp:1485-1513 -> icx_tiff_save_to_file; contract in include/icx.h),
+ *               called by name. write(".tif") still throws: the dispatch by extension is left to a
+ *               follow-up.
  *               ".pbm"/".pgm"/".ppm"/".pnm"/".pfm" decode Netpbm on the GPU (readPbm, codecs.cpp:1034-1100
  *               -> icx_pnm_decode): P1 .. P6, Pf and PF, told apart by the magic, not by the name.
  *               channels() is 1 or 3; type() is UBYTE (bitmaps: 0 -> 255, 1 -> 0; maxval <= 255),
@@ -603,6 +606,32 @@ public:
         const int rc = icx_dds_save_to_file(c, path.c_str(), pixels_, w_, h_, d_, format);
         last_write_ok_ = rc == ICX_DDS_OK;
         if (!last_write_ok_) std::fprintf(stderr, "icx_dds_save_to_file -> %d %s\n", rc, icx_last_error(c));
+    }
+    // writeTiff (private in the reference, codecs.cpp:1485-1513) called by name, whatever the path's
+    // extension: d = 1, 3, 4, Type::UBYTE only. The defaults are the reference's layout: one Deflate
+    // strip; more strips (rows_per_strip) give the GPU more to do at once. write() does not dispatch
+    // ".tif" to it yet: that name still throws there. Nothing is thrown here: a failure -- no usable
+    // GPU, another element type or a path that cannot be opened included -- only prints the
+    // message; lastWriteOk() tells.
+    void writeTiff(const std::string& path, int compression = ICX_TIFF_COMPRESSION_DEFLATE, int predictor = 1,
+                   int rows_per_strip = 0) {
+        auto& P = detail::icx_process();
+        std::lock_guard<std::mutex> lock(P.mu);
+        last_write_ok_ = false;
+        if (type_ != Type::UBYTE) {
+            std::fprintf(stderr, "writeTiff: only UBYTE images are written\n");
+            return;
+        }
+        icx_ctx* c = nullptr;
+        try {
+            c = P.get();
+        } catch (const std::runtime_error& e) {
+            std::fprintf(stderr, "%s\n", e.what());
+            return;
+        }
+        const int rc = icx_tiff_save_to_file(c, path.c_str(), pixels_, w_, h_, d_, compression, predictor, rows_per_strip);
+        last_write_ok_ = rc == ICX_TIFF_OK;
+        if (!last_write_ok_) std::fprintf(stderr, "icx_tiff_save_to_file -> %d %s\n", rc, icx_last_error(c));
     }
     // flip (codecs.h:80, codecs.cpp:162-196): reverse the row order in place.
     void flip() {
