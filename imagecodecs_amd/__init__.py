@@ -22,6 +22,8 @@ callers (tests, bench): it binds the C ABI with ctypes and offers
   * ``BmpBatch``                  -- device-resident batched .bmp decode
   * ``Context.gif_decode``        -- Image::readGif (codecs.cpp:507-542): first frame, wave LZW decode
   * ``GifBatch``                  -- device-resident batched .gif decode
+  * ``Context.gif_save_to_memory`` / ``gif_encode_device_batch`` -- Image::writeGif: exact palette or a 6x7x6
+    cube, the code stream cut into segments of one wave each
   * ``Context.tiff_decode``       -- Image::readTiff (codecs.cpp:1439-1484): strips / tiles, one wave per chunk
   * ``Context.tiff_save_to_memory`` / ``tiff_encode_device_batch`` -- Image::writeTiff (codecs.cpp:1485-1513):
     uncompressed, PackBits, LZW or Deflate strips
@@ -56,7 +58,7 @@ __all__ = ["ICXError", "Context", "Batch", "HdrBatch", "Image", "lib", "build", 
            "TGA_UNSUPPORTED", "TGA_NO_IMAGE", "TGA_MALFORMED", "TGA_TRUNCATED", "TGA_TOO_LARGE", "TGA_INVALID_ARGUMENT",
            "TGA_INTERNAL_ERR", "BmpBatch", "bmp_probe", "bmp_encode_bound", "BMP_OK", "BMP_NOT_BMP", "BMP_BAD_HEADER",
            "BMP_UNSUPPORTED", "BMP_TRUNCATED", "BMP_TOO_LARGE", "BMP_INVALID_ARGUMENT", "BMP_INTERNAL_ERR", "GifBatch", "gif_probe", "GIF_OK", "GIF_NOT_GIF", "GIF_BAD_HEADER", "GIF_MALFORMED",
-           "GIF_BAD_DATA", "GIF_TRUNCATED", "GIF_TOO_LARGE", "GIF_INTERNAL_ERR", "TiffBatch", "tiff_probe", "TIFF_OK",
+           "GIF_BAD_DATA", "GIF_TRUNCATED", "GIF_TOO_LARGE", "GIF_INVALID_ARGUMENT", "GIF_INTERNAL_ERR", "GIF_PALETTE_AUTO", "GIF_PALETTE_CUBE", "gif_encode_bound", "TiffBatch", "tiff_probe", "TIFF_OK",
            "TIFF_NOT_TIFF", "TIFF_BAD_HEADER", "TIFF_UNSUPPORTED", "TIFF_MALFORMED", "TIFF_BAD_DATA", "TIFF_TRUNCATED",
            "TIFF_TOO_LARGE", "TIFF_INVALID_ARGUMENT", "TIFF_INTERNAL_ERR", "TIFF_COMPRESSION_NONE", "TIFF_COMPRESSION_LZW",
            "TIFF_COMPRESSION_DEFLATE", "TIFF_COMPRESSION_PACKBITS", "tiff_encode_bound", "PnmBatch", "pnm_probe", "pnm_encode_bound", "PNM_OK", "PNM_NOT_PNM",
@@ -182,6 +184,10 @@ _SIGS = {
     "icx_tiff_batch_destroy": (None, [_vp]),
     "icx_tiff_batch_decode": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _vp]),
     "icx_tiff_batch_stage_times": (_i32, [_vp, _vp, _vp, _i32]),
+    "icx_gif_encode_bound": (_sz, [_i32, _i32, _i32]),
+    "icx_gif_save_to_memory": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, C.POINTER(_vp), C.POINTER(_sz)]),
+    "icx_gif_save_to_file": (_i32, [_vp, C.c_char_p, _vp, _i32, _i32, _i32, _i32, _i32, _i32]),
+    "icx_gif_encode_device_batch": (_i32, [_vp, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _u64, _vp, _vp, _vp]),
     "icx_tiff_encode_bound": (_sz, [_i32, _i32, _i32, _i32, _i32, _i32]),
     "icx_tiff_save_to_memory": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, C.POINTER(_vp), C.POINTER(_sz)]),
     "icx_tiff_save_to_file": (_i32, [_vp, C.c_char_p, _vp, _i32, _i32, _i32, _i32, _i32, _i32]),
@@ -248,7 +254,9 @@ TGA_INTERNAL_ERR = -1
 BMP_INTERNAL_ERR = -1
 # icx_gif_result (include/icx.h): Image::readGif outcomes
 GIF_OK, GIF_NOT_GIF, GIF_BAD_HEADER, GIF_MALFORMED, GIF_BAD_DATA, GIF_TRUNCATED, GIF_TOO_LARGE = range(7)
+GIF_INVALID_ARGUMENT = 7  # the write only
 GIF_INTERNAL_ERR = -1
+GIF_PALETTE_AUTO, GIF_PALETTE_CUBE = 0, 1
 # icx_tiff_result (include/icx.h): Image::readTiff / writeTiff outcomes
 (TIFF_OK, TIFF_NOT_TIFF, TIFF_BAD_HEADER, TIFF_UNSUPPORTED, TIFF_MALFORMED, TIFF_BAD_DATA, TIFF_TRUNCATED,
  TIFF_TOO_LARGE, TIFF_INVALID_ARGUMENT) = range(9)
@@ -637,6 +645,42 @@ class Context:
                                                 rows_per_strip, d_out, out_stride, d_sizes, d_status, stream or None)
         if rc == TIFF_INTERNAL_ERR:
             raise ICXError("icx_tiff_encode_device_batch: " + _err(self._p))
+        return rc
+
+    def gif_save_to_memory(self, px, segment_pixels: int = 0, dither: bool = False, palette_mode: int = GIF_PALETTE_AUTO):
+        """Image::writeGif on the GPU (contract in include/icx.h, "GIF write"): uint8 (h, w) or
+        (h, w, d), d in 1, 3, 4, rows top-down -> (code, the file's bytes or None)."""
+        a = np.ascontiguousarray(px)
+        if a.dtype != np.uint8:
+            return GIF_INVALID_ARGUMENT, None
+        if a.ndim == 2:
+            a = a[:, :, None]
+        if a.ndim != 3:
+            return GIF_INVALID_ARGUMENT, None
+        h, w, d = a.shape
+        out, size = C.c_void_p(), C.c_size_t()
+        code = lib().icx_gif_save_to_memory(self._p, a.ctypes.data if a.size else None, w, h, d, segment_pixels, int(dither),
+                                            palette_mode, C.byref(out), C.byref(size))
+        if code == GIF_INTERNAL_ERR:
+            raise ICXError("icx_gif_save_to_memory: " + _err(self._p))
+        if code != GIF_OK:
+            return code, None
+        data = C.string_at(out.value, size.value)
+        lib().icx_free(out)
+        return code, data
+
+    def gif_encode_device_batch(self, d_srcs, widths, heights, d: int, segment_pixels: int, dither: int, palette_mode: int,
+                                d_out: int, out_stride: int, d_sizes: int, d_status: int, stream=0) -> int:
+        """icx_gif_encode_device_batch: image i's pixels at device address d_srcs[i], its file to
+        d_out + i*out_stride, size (uint64) and status (int32) to the device arrays -> the call's code."""
+        n = len(d_srcs)
+        sp = (C.c_void_p * max(1, n))(*d_srcs)
+        ws = np.ascontiguousarray(widths, np.int32)
+        hs = np.ascontiguousarray(heights, np.int32)
+        rc = lib().icx_gif_encode_device_batch(self._p, n, sp, ws.ctypes.data, hs.ctypes.data, d, segment_pixels, int(dither),
+                                               palette_mode, d_out, out_stride, d_sizes, d_status, stream or None)
+        if rc == GIF_INTERNAL_ERR:
+            raise ICXError("icx_gif_encode_device_batch: " + _err(self._p))
         return rc
 
     def bmp_decode(self, data: bytes):
@@ -1123,6 +1167,12 @@ def tiff_probe(data: bytes):
     return code, w.value, h.value, d.value
 
 
+def gif_encode_bound(width: int, height: int, segment_pixels: int = 0) -> int:
+    """icx_gif_encode_bound: an upper bound of the written file's size, or 0 for arguments the
+    write refuses."""
+    return int(lib().icx_gif_encode_bound(width, height, segment_pixels))
+
+
 def tiff_encode_bound(width: int, height: int, d: int, compression: int = TIFF_COMPRESSION_DEFLATE, predictor: int = 1,
                       rows_per_strip: int = 0) -> int:
     """icx_tiff_encode_bound: an upper bound of the written file's size, or 0 for arguments the
@@ -1531,6 +1581,25 @@ class Image:
             return
         if code != TIFF_OK:
             print("icx_tiff_save_to_memory ->", code, file=sys.stderr)
+            return
+        with open(filepath, "wb") as f:
+            f.write(out)
+
+    def writeGif(self, filepath: str, segment_pixels: int = 0, dither: bool = False):
+        """writeGif (private in the reference, codecs.cpp:544-594) called by name, whatever the
+        path's extension; write(".gif") does not dispatch to it. UBYTE only. Nothing is thrown: a
+        failure prints a line and writes nothing."""
+        if self.type_ != Image.UBYTE:
+            print("writeGif: only UBYTE images are written", file=sys.stderr)
+            return
+        try:
+            px = np.frombuffer(self.pixels_.tobytes(), np.uint8, self.w_ * self.h_ * self.d_)
+            code, out = self.context().gif_save_to_memory(px.reshape(self.h_, self.w_, self.d_), segment_pixels, dither)
+        except (ICXError, ValueError, AttributeError) as e:
+            print("writeGif:", e, file=sys.stderr)
+            return
+        if code != GIF_OK:
+            print("icx_gif_save_to_memory ->", code, file=sys.stderr)
             return
         with open(filepath, "wb") as f:
             f.write(out)

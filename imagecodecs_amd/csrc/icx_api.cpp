@@ -27,6 +27,7 @@
 #include "icx_hdrw_core.h"
 #include "icx_gif_core.h"
 #include "icx_tiffw_core.h"
+#include "icx_gifw_core.h"
 
 using namespace icx;
 
@@ -46,6 +47,7 @@ struct icx_ctx {
     PnmwWs* pnmw = nullptr;  // grow-only Netpbm write buffers (icx_pnm.hip)
     DdswWs* ddsw = nullptr;  // grow-only DDS write buffers (icx_dds.hip)
     TiffwWs* tiffw = nullptr;  // grow-only TIFF write buffers (icx_tiffw.hip)
+    GifwWs* gifw = nullptr;  // grow-only GIF write buffers (icx_gifw.hip)
 };
 
 struct EventHook;
@@ -578,6 +580,7 @@ void icx_destroy(icx_ctx* c) {
     if (c->pnmw) pnmw_ws_destroy(c->pnmw);
     if (c->ddsw) ddsw_ws_destroy(c->ddsw);
     if (c->tiffw) tiffw_ws_destroy(c->tiffw);
+    if (c->gifw) gifw_ws_destroy(c->gifw);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
 }
@@ -2133,6 +2136,57 @@ int icx_tiff_save_to_file(icx_ctx* ctx, const char* path, const uint8_t* pixels,
     const int rc = icx_tiff_save_to_memory(ctx, pixels, width, height, d, compression, predictor, rows_per_strip, &mem, &size);
     if (rc != ICX_TIFF_OK) return rc;
     return write_file(ctx, "icx_tiff_save_to_file", path, mem, size, ICX_TIFF_OK, ICX_TIFF_INTERNAL_ERR);
+}
+
+// ------------------------------------------------------------ GIF write (Image::writeGif)
+size_t icx_gif_encode_bound(int width, int height, int segment_pixels) {
+    return (size_t)gifw_bound(width, height, segment_pixels);
+}
+
+int icx_gif_encode_device_batch(icx_ctx* ctx, int n, const uint8_t* const* d_src, const int32_t* widths,
+                                const int32_t* heights, int d, int segment_pixels, int dither, int palette_mode,
+                                uint8_t* d_out, uint64_t out_stride, uint64_t* d_sizes, int32_t* d_status, void* stream) {
+    if (!ctx) return ICX_GIF_INTERNAL_ERR;
+    GifwGeom g;  // (a 1 x 1 image tells whether d and the options are legal)
+    if (n < 0 || n > 65535 || !gifw_geom(1, 1, d, segment_pixels, dither, palette_mode, &g) ||
+        (n > 0 && (!d_src || !widths || !heights || !d_out || !d_sizes || !d_status)))
+        return ICX_GIF_INVALID_ARGUMENT;
+    if (n == 0) return ICX_GIF_OK;
+    return encode_batch_guarded(ctx, "icx_gif_encode_device_batch", ctx->gifw, gifw_ws_create, ICX_GIF_OK,
+                                ICX_GIF_INTERNAL_ERR, [&](GifwWs& ws, std::string& err) {
+                                    return gifw_encode_batch(stream ? (hipStream_t)stream : ctx->stream, ws, n, d_src, widths,
+                                                             heights, d, segment_pixels, dither, palette_mode, d_out,
+                                                             out_stride, d_sizes, d_status, err);
+                                });
+}
+
+int icx_gif_save_to_memory(icx_ctx* ctx, const uint8_t* pixels, int width, int height, int d, int segment_pixels,
+                           int dither, int palette_mode, uint8_t** out, size_t* size) {
+    if (out) *out = nullptr;
+    if (size) *size = 0;
+    if (!ctx) return ICX_GIF_INTERNAL_ERR;
+    GifwGeom g;
+    if (!pixels || !out || !size || !gifw_geom(width, height, d, segment_pixels, dither, palette_mode, &g))
+        return ICX_GIF_INVALID_ARGUMENT;
+    const uint64_t bound = gifw_bound(width, height, segment_pixels);
+    const int32_t w = width, h = height;
+    return save_one<uint8_t>(ctx, "icx_gif_save_to_memory", pixels, (uint64_t)width * height * d, bound, out, size,
+                             ICX_GIF_OK, ICX_GIF_INTERNAL_ERR,
+                             [&](const uint8_t* const* src, uint8_t* d_file, uint64_t* d_size, int32_t* d_status, hipStream_t st) {
+                                 return icx_gif_encode_device_batch(ctx, 1, src, &w, &h, d, segment_pixels, dither,
+                                                                    palette_mode, d_file, bound, d_size, d_status, st);
+                             });
+}
+
+int icx_gif_save_to_file(icx_ctx* ctx, const char* path, const uint8_t* pixels, int width, int height, int d,
+                         int segment_pixels, int dither, int palette_mode) {
+    if (!ctx) return ICX_GIF_INTERNAL_ERR;
+    if (!path) return ICX_GIF_INVALID_ARGUMENT;
+    uint8_t* mem = nullptr;
+    size_t size = 0;
+    const int rc = icx_gif_save_to_memory(ctx, pixels, width, height, d, segment_pixels, dither, palette_mode, &mem, &size);
+    if (rc != ICX_GIF_OK) return rc;
+    return write_file(ctx, "icx_gif_save_to_file", path, mem, size, ICX_GIF_OK, ICX_GIF_INTERNAL_ERR);
 }
 
 }  // extern "C"

@@ -535,6 +535,15 @@ int tiffw_encode_batch(hipStream_t st, TiffwWs& ws, int n, const uint8_t* const*
                        const int32_t* heights, int d, int comp, int pred, int rows_per_strip, uint8_t* d_out,
                        uint64_t out_stride, uint64_t* d_sizes, int32_t* d_status, std::string& err);
 
+// ---- GIF write (icx_gifw.hip; contract in include/icx.h, serial part in icx_gifw_core.h) ----
+struct GifwWs;
+GifwWs* gifw_ws_create();
+void gifw_ws_destroy(GifwWs* w);
+// 0, or -1 with err set
+int gifw_encode_batch(hipStream_t st, GifwWs& ws, int n, const uint8_t* const* d_src, const int32_t* widths,
+                      const int32_t* heights, int d, int segment_pixels, int dither, int palette_mode, uint8_t* d_out,
+                      uint64_t out_stride, uint64_t* d_sizes, int32_t* d_status, std::string& err);
+
 // ---- OpenEXR read (icx_exr.hip) ----
 // tinyexr's LoadEXRFromMemory; returns its code (-100: HIP failure, err says which).
 struct ExrWs;

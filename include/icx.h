@@ -961,7 +961,8 @@ enum icx_gif_result {
                                 palette at all                                                       */
     ICX_GIF_BAD_DATA = 4,    /* minimum code size outside 2..8; an invalid code                      */
     ICX_GIF_TRUNCATED = 5,   /* the file ends first                                                  */
-    ICX_GIF_TOO_LARGE = 6,   /* larger than the batch workspace                                      */
+    ICX_GIF_TOO_LARGE = 6,   /* larger than the batch workspace; the write: longer than out_stride   */
+    ICX_GIF_INVALID_ARGUMENT = 7, /* the write only: see "GIF write" below                             */
     ICX_GIF_INTERNAL_ERR = -1 /* HIP failure (see icx_last_error)                                    */
 };
 /* The container walk up to the first image descriptor (host only, no GPU touched): the canvas
@@ -1140,6 +1141,69 @@ int icx_tiff_encode_device_batch(icx_ctx* ctx, int n, const uint8_t* const* d_sr
                                  const int32_t* heights, int d, int compression, int predictor, int rows_per_strip,
                                  uint8_t* d_out, uint64_t out_stride, uint64_t* d_sizes, int32_t* d_status,
                                  void* hip_stream);
+
+/* ---- GIF write (Image::writeGif, codecs.cpp:544-594) ------------------------------------------------
+ * The reference pairs a grey-ramp palette with channel-planar bytes; the file written here is a
+ * contract of its own: one GIF89a frame, a global colour table, no extensions, not interlaced. A
+ * file written here reads back, through icx_gif_decode, to the table's colours at the pixels'
+ * indices: the pixels themselves when they have 256 colours or fewer.
+ * pixels: width*height*d bytes, rows top-down, d = 1 (grey: v is the colour v,v,v), 3 (R,G,B) or 4
+ * (R,G,B,A: alpha is ignored, as the read returns three channels). width, height: 1..65535.
+ * ICX_GIF_INVALID_ARGUMENT (and a bound of 0): a width, height, d, dither, palette_mode or
+ * segment_pixels outside what is stated here; a null pointer; more than 2^30 pixels; more than
+ * 65535 images.
+ * Palette, one rule for every d:
+ *   exact  the image has n <= 256 distinct colours: the table holds them in ascending order of
+ *          R<<16 | G<<8 | B, a pixel's index is its colour's rank (so the table does not depend on
+ *          the order of the pixels). Table bits tb = max(1, ceil(log2 n)), 2^tb entries, those from
+ *          n on 0,0,0; minimum code size m = max(2, tb).
+ *   cube   more than 256 distinct colours, or palette_mode = ICX_GIF_PALETTE_CUBE: 6 x 7 x 6 levels
+ *          of R, G, B, 252 entries, entries 252..255 0,0,0, tb = 8, m = 8. Level k of L is the value
+ *          (255*k + (L-1)/2) / (L-1) in integer arithmetic (0,51,..,255 and 0,43,85,128,170,213,255).
+ *          A channel value c has level k = (32*c*(L-1) + 255*T) / 8160 in integer arithmetic, with
+ *          T = 16 (round half up) without dithering and T = 2*B4[y&3][x&3] + 1 with ordered
+ *          dithering, B4 = {{0,8,2,10},{12,4,14,6},{3,11,1,9},{15,7,13,5}}. Index (kr*7 + kg)*6 + kb.
+ * Options: segment_pixels: 0 is the default (65536), -1 one segment for the whole image, any other
+ * value must be >= 64 (a value >= width*height is one segment). dither: 0 or 1, used only where the
+ * cube is. palette_mode: ICX_GIF_PALETTE_AUTO (the rule above) or ICX_GIF_PALETTE_CUBE.
+ * Code stream: LSB first; Clear = 2^m, stop = Clear + 1, first free entry Clear + 2; codes are m + 1
+ * bits wide after a Clear and one bit wider once the decoder's next free entry equals 2^width, up
+ * to 12. The stream is a leading Clear; then for each segment of segment_pixels consecutive indices
+ * (row-major, the last one shorter) the greedy longest-match codes of that segment alone, with a
+ * Clear immediately after the code whose emission adds entry 4095 (the dictionary restarts); after
+ * a segment's last pending code a Clear, after the last segment's the stop code; then zero bits to
+ * the byte. A Clear that ends a segment has the width the decoder holds there, so a segment's bit
+ * string depends on its own indices and m only: segments are coded independently and their bit
+ * strings concatenated. Cutting costs compression: a dictionary restarts at every segment.
+ * Container: "GIF89a"; width, height (little-endian), flags 0x80 | (tb-1)<<4 | (tb-1), background
+ * 0, aspect 0; the table; ',' 0 0 0 0 width height flags 0; the byte m; the payload in sub-blocks of
+ * 255 bytes, the last one shorter (no empty sub-block when the payload is a multiple of 255); a
+ * zero terminator; ';'. Nothing follows.
+ * icx_gif_encode_bound: an upper bound of the file's size (0: refused arguments), independent of
+ * the content and of d: at most N + nseg + 1 + floor(N/3838) codes (one per pixel, a Clear or stop
+ * per segment, the leading Clear, a table-full Clear per 3838 codes at least) of 12 bits, the
+ * sub-block length bytes, 13 + 768 + 10 + 1 bytes of header, table, descriptor and code size, the
+ * terminator and the trailer. The proof is in icx_gifw_core.h. */
+enum icx_gif_palette_mode { ICX_GIF_PALETTE_AUTO = 0, ICX_GIF_PALETTE_CUBE = 1 };
+size_t icx_gif_encode_bound(int width, int height, int segment_pixels);
+/* One image, host in / host out: *out receives the file (malloc()'d, free with icx_free). */
+int icx_gif_save_to_memory(icx_ctx* ctx, const uint8_t* pixels, int width, int height, int d, int segment_pixels,
+                           int dither, int palette_mode, uint8_t** out, size_t* size);
+/* The same bytes written to path; ICX_GIF_INTERNAL_ERR when the file cannot be written. */
+int icx_gif_save_to_file(icx_ctx* ctx, const char* path, const uint8_t* pixels, int width, int height, int d,
+                         int segment_pixels, int dither, int palette_mode);
+/* Device-resident batch: image i's pixels at d_src[i] (device, any alignment), its file at
+ * d_out + i*out_stride (any alignment), its size in d_sizes[i] and its code in d_status[i]: OK;
+ * INVALID_ARGUMENT (a null d_src[i] or a refused size; size 0); ICX_GIF_TOO_LARGE when the file is
+ * longer than out_stride (nothing of it is written; d_sizes[i] says what it needs). The call
+ * returns ICX_GIF_INVALID_ARGUMENT for n < 0, n > 65535, a refused d / segment_pixels / dither /
+ * palette_mode or a null array with n > 0, otherwise ICX_GIF_OK or ICX_GIF_INTERNAL_ERR. All images
+ * go through each kernel in one launch; the palette mode, m and every size stay on the device; the
+ * call synchronises hip_stream (NULL = the context's stream) and reads nothing back. */
+int icx_gif_encode_device_batch(icx_ctx* ctx, int n, const uint8_t* const* d_src, const int32_t* widths,
+                                const int32_t* heights, int d, int segment_pixels, int dither, int palette_mode,
+                                uint8_t* d_out, uint64_t out_stride, uint64_t* d_sizes, int32_t* d_status,
+                                void* hip_stream);
 
 #ifdef __cplusplus
 }

@@ -29,7 +29,11 @@
  *               top-down, on the GPU (readGif, codecs.cpp:507-542 -> icx_gif_decode): global and
  *               local palettes, transparency, interlace, frames smaller than or clipped by the
  *               canvas. A file the read refuses (codes in include/icx.h) leaves pixels_ null and
- *               read() throws "Could not read image data". write(".gif") stays outside this path.
+ *               read() throws "Could not read image data".
+ *               writeGif(path, segment_pixels, dither) writes one GIF89a frame on the GPU (writeGif,
+ *               codecs.cpp:544-594 -> icx_gif_save_to_file; the file is the contract of include/icx.h
+ *               "GIF write", not the reference's grey ramp over planar bytes), called by name.
+ *               write(".gif") still throws std::invalid_argument.
  *               ".tif"/".tiff" decode the first IFD of a TIFF, 8 bits per sample, rows top-down, on
  *               the GPU (readTiff, codecs.cpp:1439-1484 -> icx_tiff_decode): strips or tiles,
  *               uncompressed, LZW, zlib or PackBits, predictor 2, grey (either polarity), palette,
@@ -632,6 +636,31 @@ public:
         const int rc = icx_tiff_save_to_file(c, path.c_str(), pixels_, w_, h_, d_, compression, predictor, rows_per_strip);
         last_write_ok_ = rc == ICX_TIFF_OK;
         if (!last_write_ok_) std::fprintf(stderr, "icx_tiff_save_to_file -> %d %s\n", rc, icx_last_error(c));
+    }
+    // writeGif (private in the reference, codecs.cpp:544-594) called by name, whatever the path's
+    // extension: d = 1, 3, 4, Type::UBYTE only; the file is the one of include/icx.h "GIF write" (the
+    // image's own colours when there are 256 or fewer, else a 6 x 7 x 6 cube, ordered dithering on
+    // request). write() does not dispatch ".gif" to it: that name still throws there. Nothing is
+    // thrown here: a failure -- no usable GPU, another element type or a path that cannot be opened
+    // included -- only prints the message; lastWriteOk() tells.
+    void writeGif(const std::string& path, int segment_pixels = 0, bool dither = false) {
+        auto& P = detail::icx_process();
+        std::lock_guard<std::mutex> lock(P.mu);
+        last_write_ok_ = false;
+        if (type_ != Type::UBYTE) {
+            std::fprintf(stderr, "writeGif: only UBYTE images are written\n");
+            return;
+        }
+        icx_ctx* c = nullptr;
+        try {
+            c = P.get();
+        } catch (const std::runtime_error& e) {
+            std::fprintf(stderr, "%s\n", e.what());
+            return;
+        }
+        const int rc = icx_gif_save_to_file(c, path.c_str(), pixels_, w_, h_, d_, segment_pixels, dither ? 1 : 0, ICX_GIF_PALETTE_AUTO);
+        last_write_ok_ = rc == ICX_GIF_OK;
+        if (!last_write_ok_) std::fprintf(stderr, "icx_gif_save_to_file -> %d %s\n", rc, icx_last_error(c));
     }
     // flip (codecs.h:80, codecs.cpp:162-196): reverse the row order in place.
     void flip() {
